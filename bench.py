@@ -14,7 +14,7 @@ workload: N = 1 -- configs[1] (C2): Cornell box + 1M-triangle displaced blob, Pa
           honoured as given.  Expected run time (one GPU renders C3 in 27.6 s per step, 623 Msamples/s: profiles/r06_c3_one_gpu.json): a step is
           ~28 s / N -- N = 8: 3.6 s, N = 4: 7.1 s, N = 2: 14.3 s -- so the driver's `--steps 20 --warmup 5` (+ the first
           render) is ~1.6 min at N = 8, ~3.1 min at N = 4 and ~6.2 min at N = 2, plus ~15 s of scene build per process.
-          The same C2 scene per GPU as the N = 1 line is appended as "extra_configs"[0] ("scaling": "weak": the C2 view at
+          With --full the same C2 scene per GPU as the N = 1 line is appended as "extra_configs"[0] ("scaling": "weak": the C2 view at
           256 spp on a square image with N x the pixels, side 1024 sqrt(N) in whole 32-pixel tiles, 2 timed steps of
           ~0.45 s; --no-extra skips it), so that a per-GPU-like-for-like figure sits next to the N = 1 line's.
           Options: --scaling weak (that image as the headline), --scaling strong-c2 (the 1024x1024 image itself
@@ -26,16 +26,19 @@ procedural scene, no files.  The FIRST render of a scene allocates the path-stat
 host pays) and runs the library's traversal-kernel pilot: it is timed separately ("first_render_ms", "pilot_ms") and is not one of the
 W + K steps.  The SECOND render grows the workspace to one batch per image ("second_render_ms"): it is the first warm-up step.
 The printed line carries numbers only (< 8 000 bytes); the full result is written to the sidecar file the line names ("detail").
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last timed step
+computed (the image and the film: DIR/rgb.npy, DIR/film.npy, float32; a fixed, seeded pixel sample of both above 64 MB).
 
-Extra objects: "roofline" for the dominant kernel (the per-lane closest-hit BVH traversal): "achieved" = ALGORITHMIC bytes (32 B per
+Extra objects, with --full only: "roofline" for the dominant kernel (the per-lane closest-hit BVH traversal): "achieved" = ALGORITHMIC bytes (32 B per
 node visit + 48 B per triangle test, counted on the device) / the kernel's summed HIP-event time, "frac" = that against the 8 TB/s
 spec.  Algorithmic bytes are mostly served by L1 / L2 / the Infinity Cache, so next to it, from the committed rocprofv3 --pmc passes
 of the same command AND ONLY when they were taken with the library that is running (kernel-source hashes; otherwise
 "stale_profile"): "traffic" (memory-side bytes per launch), "frac_physical_of_copy", "binding" / "frac_of_binding_ceiling" (the
 throughput ceilings); "roofline_others" likewise for the camera kernel, shading and the sampler; "cpu_baseline": the CPU oracle (a C++
 port of the reference path) on one host core on a strided pixel subset; "cpu_baseline_threads": the same oracle, one OS thread per
-GetSubWindow task rectangle (the reference's isolate-per-task model); "extra_configs": short C4 and C5 runs (3 steps each, N = 1
-only, after the headline's timed region).  Glossary of every key: profiles/README.md.
+GetSubWindow task rectangle (the reference's isolate-per-task model); "replay_Msamples_s": the reference's serial sample stream
+replayed; "extra_configs": short C4 and C5 runs (3 steps each, N = 1 only, after the headline's timed region); N > 1: "reduce_ms".
+Glossary of every key: profiles/README.md.
 """
 import argparse
 import json
@@ -536,6 +539,28 @@ def load_detail(path):
         return json.loads(text.splitlines()[-1])
 
 
+DUMP_LIMIT = 64 << 20  # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(directory, images, limit=DUMP_LIMIT, seed=0):
+    """--dump-outputs: what a caller of the timed path receives from its last step (images [H, W, C] by name) as
+    DIR/<name>.npy, float32 / float64.  Above `limit` bytes in all, every image is cut down to the same fixed, seeded
+    sample of pixels ([n, C], in pixel order), so that two runs of the same command can be compared file by file."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    images = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float32)) for k, v in images.items()}
+    h, w = next(iter(images.values())).shape[:2]
+    per_pixel = sum(v.nbytes for v in images.values()) // (h * w)
+    pick = None
+    if per_pixel * h * w > limit - 4096 * len(images):  # (room for the .npy headers)
+        n = (limit - 4096 * len(images)) // per_pixel
+        pick = np.sort(np.random.default_rng(seed).choice(h * w, n, replace=False))
+    for name, v in images.items():
+        if pick is not None:
+            v = v.reshape(h * w, -1)[pick]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(v))
+
+
 def emit(d):
     """Sidecar first, then the line -- the LAST thing this process writes to stdout."""
     path = write_detail(d)
@@ -552,7 +577,7 @@ def main():
     ap.add_argument("--res", type=int, default=0)
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the short C4 / C5 runs appended at N = 1")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the short C4 / C5 runs appended at N = 1")
     ap.add_argument("--scaling", default=None, choices=["c3", "weak", "strong-c2", "samples"],
                     help="N > 1: c3 (default) = BASELINE configs[2] verbatim, tiles of the 4096^2 x 1024 spp image over the N ranks; weak = "
                          "tiles of the C2 image with N x the pixels (the N = 1 workload per GPU); strong-c2 = tiles of the 1024^2 image; "
@@ -562,6 +587,10 @@ def main():
                                                  "instead of 1000,500 -- e.g. 180,90 = 32 400 triangles, a tree that fits one XCD's L2; the line says so")
     ap.add_argument("--from-detail", default=None, help="no run: print the line of a committed / sidecar detail file (CPU)")
     ap.add_argument("--trace-kernels", default=None, help="A/B runs: force the traversal kernels (closest,any), e.g. 2,3 (default: the scene's pilot)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: CPU baselines, the replay leg, the extra configs, the HBM "
+                                                         "copy rate and the roofline objects, the N-rank reduce timing")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps: the last step's image and film as DIR/rgb.npy, "
+                                                                         "DIR/film.npy (float32; a fixed pixel sample above 64 MB)")
     args = ap.parse_args()
 
     if args.from_detail:
@@ -588,8 +617,10 @@ def main():
     cfg, res, spp, mode = pl["headline"]
     run = Run(cfg, res, spp, rank, world, mode, args)
     out = run.headline(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rgb": run.rgb.cpu().numpy(), "film": run.film.cpu().numpy()})
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(run.prims, run.renderer, args.cpu_pixels, run.H, run.W, spp)
             out["cpu_baseline_threads"] = cpu_baseline_threads(run.prims, run.renderer, run.H, run.W, spp)
@@ -607,7 +638,7 @@ def main():
                 del r
                 torch.cuda.empty_cache()
             out["extra_configs"] = extra
-    if world > 1 and pl["extras"]:
+    if world > 1 and pl["extras"] and args.full:
         # next to the N-rank headline (configs[2]): the N = 1 line's workload per GPU -- the C2 view at 256 spp on a square image
         # with N x the pixels, tiles over the N ranks, one reduce per step ("weak") -- every rank takes part; after the
         # headline's timed region, like C4 / C5 at N = 1; first render + one warm-up + 2 timed steps of ~0.45 s.
@@ -683,6 +714,7 @@ class Run:
         import torch
         from dartray_amd import _abi, dist as drdist
         args, world, rank = self.args, self.world, self.rank
+        full = getattr(args, "full", False)  # (the measurements beyond the headline: copy rate, reduce timing, roofline objects)
         # The first render of a scene: workspace allocation + the traversal-kernel pilot (MEASUREMENTS.md) -- what a
         # one-shot render pays on top of a steady-state step; timed on its own, not one of the W + K steps.
         torch.cuda.synchronize()
@@ -723,7 +755,7 @@ class Run:
         own_min = -drdist.max_over_ranks(-dt_own)
         st = self.dev.stats()
         reduce_ms = None
-        if world > 1:  # the collective alone (after the timed region): three reduces of a scratch film, barrier-bracketed
+        if world > 1 and full:  # the collective alone (after the timed region): three reduces of a scratch film, barrier-bracketed
             scratch = torch.zeros_like(self.film)
             torch.cuda.synchronize()
             drdist.barrier()
@@ -736,7 +768,8 @@ class Run:
         if rank != 0:
             return None
         copy = C.c_double(0.0)
-        _abi.check(self.lib.dr_copy_bandwidth(1 << 30, 10, C.byref(copy)))  # measured HBM denominator (float4 copy, 2 GiB moved per pass)
+        if full:
+            _abi.check(self.lib.dr_copy_bandwidth(1 << 30, 10, C.byref(copy)))  # measured HBM denominator (float4 copy, 2 GiB moved per pass)
         samples_per_step = self.H * self.W * self.spp * (world if (self.mode == "samples" and world > 1) else 1)
         value = samples_per_step * steps / dt / 1e6
         picked = self.dev.trace_kernels()  # (closest, any): 2 = k_trace, 3 = k_trace3 / k_trace3a, 5 = k_trace3c (the pilot's choice for this scene)
@@ -805,13 +838,14 @@ class Run:
                        "sampler_mode": "DR_SAMPLER_COUNTER (keyed per-pixel streams, bit-exact vs the oracle's same mode); the reference's "
                                        "single serial Random(taskNum) stream is replayed bit-exactly through DR_SAMPLER_HOST_BUFFER in the "
                                        "tests but is not a throughput mode (one serial stream; 148 B + RNG tail per sample over PCIe)"},
-            "roofline": roof,
-            "roofline_shade": shade,
-            "roofline_gen": gen,
-            "roofline_camera": cam,
+            # (--full only: the copy rate they are read against is a run of its own)
+            "roofline": roof if full else None,
+            "roofline_shade": shade if full else None,
+            "roofline_gen": gen if full else None,
+            "roofline_camera": cam if full else None,
             # per traversal kernel of this line, from the committed PMC passes of the same command (not this run): where the lanes and
             # the wave-cycles go -- the figures that move when a traversal kernel gets better or worse
-            "trace_kernels_profiled": kernel_profile(self.cfg, knames, profile),
+            "trace_kernels_profiled": kernel_profile(self.cfg, knames, profile) if full else None,
             "kernel_ms_per_step": dict({k: round(st[k] / steps, 2) for k in ("closest_ms", "any_ms", "shade_ms", "gen_ms", "film_ms", "total_ms")},
                                        note="a stage's any-hit launch runs beside its closest-hit launch (second stream): any_ms is its time "
                                             "after the closest-hit launch ended" if os.environ.get("DARTRAY_OVERLAP_ANY", "1") != "0" else "one kernel at a time"),
@@ -849,7 +883,7 @@ class Run:
                 out["trace_kernels_per_rank"] = [list(p) for p in picks_per_rank]
             out["per_rank_step_ms"] = {"min": round(own_min / steps * 1e3, 3), "max": round(own_max / steps * 1e3, 3),
                                        "note": "each rank's own clock before the closing barrier (rank 0's includes waiting for the reduce)"}
-            out["reduce_ms"] = round(reduce_ms, 3)
+            out["reduce_ms"] = round(reduce_ms, 3) if reduce_ms is not None else None
             out["film_bytes_reduced_per_step"] = int(self.H * self.W * 16)
             out["one_gpu_same_workload"] = one_gpu_reference(self.mode, self.cfg)
         return out

@@ -216,14 +216,15 @@ setUint32 setUint64 setUint8 toNativeUtf8 addStream asFloat32List asUint8List cr
 lengthInBytes openWrite readAsString rename resolvedExecutable stderr systemTemp toFilePath writeAsBytes writeAsString""".split())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/lib"), reason="the reference is only present in the build container")
 def test_dart_integration_uses_only_names_the_reference_declares():
     """Without an SDK nothing can type-check integration/*.dart; this is the check a text search allows: every capitalised name
     the two files use is a class / function of the reference, of the Dart SDK, or their own, and every `.member` they access is a
-    word of the reference's sources, an SDK member, or their own -- a misspelt field of Scene / BVHAccel / Camera would show here."""
-    import glob
-    ref = "\n".join(open(f, errors="ignore").read() for f in glob.glob("/root/reference/lib/**/*.dart", recursive=True))
-    ref_words = set(re.findall(r"\b[A-Za-z_]\w*\b", ref))
+    word of the reference's sources, an SDK member, or their own -- a misspelt field of Scene / BVHAccel / Camera would show here.
+    The reference's words are tests/golden/reference_dart_names.json (those of its lib/**/*.dart that the two files contain;
+    tests/golden/make_reference_names.py writes it from a reference checkout)."""
+    import json
+    ref_words = set(json.load(open(os.path.join(GOLDEN, "reference_dart_names.json")))["names"])
+    assert len(ref_words) > 400
     texts, own = {}, set()
     for name in ("hip_sampler_renderer.dart", "hip_render_manager.dart"):
         t = open(os.path.join(ROOT, "integration", name)).read()

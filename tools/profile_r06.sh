@@ -40,7 +40,7 @@ RD="TCC_EA0_RDREQ TCC_EA0_RDREQ_32B TCC_EA0_RDREQ_64B TCC_EA0_RDREQ_128B"
 SQ="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_SALU"
 TCC="TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum"
 LDS="SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVES"
-X="--no-cpu-baseline --no-extra"
+X="--full --no-cpu-baseline --no-extra"  # (--full: the sidecar's roofline objects feed tools/make_traffic.py)
 for cfg in $cfgs; do
   case $cfg in
     c2) a=""; s="--steps 3 --warmup 1";;
