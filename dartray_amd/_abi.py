@@ -16,6 +16,8 @@ DR_INTEGRATOR_PATH = 1
 DR_INTEGRATOR_DIRECT_ONE = 2
 DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
+DR_SAMPLER_STRATIFIED = 2
+DR_SAMPLER_STRATIFIED_NOJITTER = 3
 DR_LIGHT_DIFFUSE_AREA = 0
 DR_LIGHT_INFINITE = 1
 DR_LIGHT_POINT = 2
@@ -109,6 +111,7 @@ class DrRenderDesc(C.Structure):
                 ("seed", C.c_int64),
                 ("task_num", C.c_int32), ("task_count", C.c_int32),
                 ("tile_rank", C.c_int32), ("tile_count", C.c_int32), ("tile_size", C.c_int32),
+                ("strat_xsamples", C.c_int32),
                 ("nsamples", C.c_int64),
                 ("pixel_xy", C.c_void_p), ("sample_vec", C.c_void_p), ("sample_stride", C.c_int32),
                 ("tail", C.c_void_p), ("max_tail", C.c_int32), ("tail_offsets", C.c_void_p)]
@@ -129,7 +132,7 @@ class DrRenderStats(C.Structure):
 
 
 DR_COMM_ID_BYTES = 128
-DR_ABI_VERSION = 7  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
+DR_ABI_VERSION = 8  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
 
 
 # name -> (restype, argtypes): every symbol include/dartray_hip.h declares.
@@ -157,6 +160,7 @@ EXPORTS = {
     "dr_render_sharded": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_int32, C.c_void_p, C.c_void_p]),
     "dr_film_resolve_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dr_enumerate_pixels": (C.c_int, [C.POINTER(DrRenderDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dr_generate_samples": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32]),
     "dr_get_stats": (C.c_int, [C.c_void_p, C.POINTER(DrRenderStats)]),
     "dr_reset_stats": (C.c_int, [C.c_void_p]),
     "dr_copy_bandwidth": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_double)]),

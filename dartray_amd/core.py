@@ -1059,6 +1059,23 @@ class DartRandom:
             if self.lo != 0xffffffff:
                 return self.lo
 
+    def randomFloat(self):  # Random.nextDouble(): 26 + 27 bits from two steps
+        self._step()
+        a = self.lo & ((1 << 26) - 1)
+        self._step()
+        return (a * 134217728.0 + (self.lo & ((1 << 27) - 1))) / 9007199254740992.0
+
+
+def GetSubWindow(w, h, num, count):  # common.dart:52-73 -> (x0, x1, y0, y1), from 0 as the reference computes them
+    nx, ny = count, 1
+    while (nx & 1) == 0 and 2 * w * ny < h * nx:
+        nx >>= 1
+        ny <<= 1
+    xo, yo = num % nx, num // nx
+    lerp = lambda t, v1, v2: v1 * (1.0 - t) + v2 * t
+    return (math.floor(lerp(xo / nx, 0, w)), min(math.floor(lerp((xo + 1) / nx, 0, w)), w),
+            math.floor(lerp(yo / ny, 0, h)), min(math.floor(lerp((yo + 1) / ny, 0, h)), h))
+
 
 class LinearPixelSampler:
     """Pixels "linear" (pixel_samplers/linear_pixel_sampler.dart:29-40): rows top to bottom."""
@@ -1129,6 +1146,120 @@ class LowDiscrepancySampler:
 
     def roundSize(self, size):
         return RoundUpPow2(size)
+
+
+ONE_MINUS_EPSILON = 0.9999999403953552  # montecarlo.dart:23
+
+
+class StratifiedSampler:
+    """samplers/stratified_sampler.dart:38-128: xsamples x ysamples jittered strata per pixel for the image and the lens
+    sample, xsamples * ysamples strata for the time sample, the lens and time samples shuffled, and a LatinHypercube per
+    integrator slot.  On the device (DR_SAMPLER_STRATIFIED / _NOJITTER) every pixel and every sample owns a keyed stream
+    (DESIGN.md 2.7); serial_samples() walks the reference's ONE serial RNG(taskNum) instead and
+    returns the vectors as a HostBufferSampler.  The device needs xsamples * ysamples to be a power of two."""
+
+    def __init__(self, camera, xsamples=2, ysamples=2, jitter=True, seed=5489, pixels=None):
+        self.camera = camera
+        self.xPixelSamples, self.yPixelSamples = int(xsamples), int(ysamples)
+        if self.xPixelSamples < 1 or self.yPixelSamples < 1:
+            raise ValueError("StratifiedSampler: xsamples and ysamples must be positive")
+        self.samplesPerPixel = self.xPixelSamples * self.yPixelSamples
+        self.jitterSamples = bool(jitter)
+        self.seed = int(seed)
+        self.pixelSampler = pixels or LinearPixelSampler()
+
+    def roundSize(self, size):  # :63-65
+        return size
+
+    def maximumSampleCount(self):  # :126-128
+        return self.samplesPerPixel
+
+    def pixel_samples(self, px, py, n1D, n2D, pixel_rng, sample_rng):
+        """getMoreSamples (:67-124) for the pixel (px, py): [spp, 5 + sum(n1D) + 2 sum(n2D)] f32 in the C ABI's field order, the
+        image sample as its fraction inside the pixel (f32(f32(u) + px) - px: the shift happens inside the Float32List, :97-100).
+        pixel_rng draws the strata and the two shuffles; sample_rng(i) is the generator of sample i's LatinHypercube draws
+        (the same object everywhere: the reference's serial stream)."""
+        f32 = np.float32
+        xs, ys, spp, jit = self.xPixelSamples, self.yPixelSamples, self.samplesPerPixel, self.jitterSamples
+
+        def strat2d():  # StratifiedSample2D, montecarlo.dart:279-292
+            out = np.zeros((spp, 2), f32)
+            dx, dy = 1.0 / xs, 1.0 / ys
+            for i in range(spp):
+                x, y = i % xs, i // xs
+                jx = pixel_rng.randomFloat() if jit else 0.5
+                jy = pixel_rng.randomFloat() if jit else 0.5
+                out[i] = (min((x + jx) * dx, ONE_MINUS_EPSILON), min((y + jy) * dy, ONE_MINUS_EPSILON))
+            return out
+
+        def shuffle(a):  # Shuffle, montecarlo.dart:294-303 (rows of `a` are the dims-tuples)
+            for i in range(len(a)):
+                other = i + pixel_rng.randomUint() % (len(a) - i)
+                a[[i, other]] = a[[other, i]]
+
+        image, lens = strat2d(), strat2d()
+        time = np.zeros((spp, 1), f32)
+        for i in range(spp):  # StratifiedSample1D, montecarlo.dart:270-277
+            time[i, 0] = min((i + (pixel_rng.randomFloat() if jit else 0.5)) * (1.0 / spp), ONE_MINUS_EPSILON)
+        fp = np.array([px, py], f32)
+        image = (image + fp) - fp  # f32 arithmetic: the reference's imageX is f32(f32(u) + px)
+        shuffle(lens)
+        shuffle(time)
+        nf = 5 + sum(n1D) + 2 * sum(n2D)
+        vec = np.zeros((spp, nf), f32)
+        vec[:, 0:2], vec[:, 2:4], vec[:, 4:5] = image, lens, time
+        for i in range(spp):
+            rng, o = sample_rng(i), 5
+            for n, dims in [(n, 1) for n in n1D] + [(n, 2) for n in n2D]:  # LatinHypercube, montecarlo.dart:305-325
+                v = np.zeros((n, dims), f32)
+                for j in range(n):
+                    for d in range(dims):
+                        v[j, d] = min((j + rng.randomFloat()) * (1.0 / n), ONE_MINUS_EPSILON)
+                for d in range(dims):
+                    for j in range(n):
+                        other = j + rng.randomUint() % (n - j)
+                        v[j, d], v[other, d] = v[other, d], v[j, d]
+                vec[i, o:o + n * dims] = v.reshape(-1)
+                o += n * dims
+        return vec
+
+    def slot_counts(self, renderer, scene):
+        """(n1D, n2D): entries of the 1-D and 2-D sample slots the integrators request, in request order."""
+        kind = renderer.surfaceIntegrator.kind
+        if kind == _abi.DR_INTEGRATOR_PATH:
+            return [1] * 14, [1] * 9
+        if kind == _abi.DR_INTEGRATOR_DIRECT_ONE:
+            return [1] * 5, [1] * 2
+        ns = [self.roundSize(L.nSamples) for L in scene.lights]
+        return [n for k in ns for n in (k, k)] + [1, 1], [n for k in ns for n in (k, k)]
+
+    def serial_samples(self, renderer, scene, li_draws=None):
+        """The reference's own stream: ONE RNG(taskNum) (sampler_renderer.dart:137) threaded through the sampler, pixel after pixel in
+        the pixel sampler's order, and through Li.  Returns a HostBufferSampler.  li_draws(px, py, vector, rng) -> the
+        randomFloat() values Li draws for that sample, taken from rng (PathIntegrator beyond its third vertex; the host has
+        no integrator of its own to count them): required for a PathIntegrator with maxDepth >= 3, unused otherwise."""
+        integ = renderer.surfaceIntegrator
+        needs_tail = integ.kind == _abi.DR_INTEGRATOR_PATH and integ.maxDepth >= 3
+        if needs_tail and li_draws is None:
+            raise ValueError("serial_samples: a PathIntegrator with maxDepth >= 3 draws inside Li; pass li_draws")
+        n1D, n2D = self.slot_counts(renderer, scene)
+        e = renderer.camera.film.getSampleExtent()
+        x0, x1, y0, y1 = GetSubWindow(e[1] - e[0], e[3] - e[2], renderer.taskNum, max(1, renderer.taskCount))
+        pixels = self.pixelSampler.setup(x0, y0, x1 - x0, y1 - y0)
+        rng = DartRandom(renderer.taskNum)
+        vecs, tails = [], []
+        for px, py in pixels:
+            v = self.pixel_samples(int(px), int(py), n1D, n2D, rng, lambda i: rng)
+            vecs.append(v)
+            if needs_tail:
+                tails += [list(li_draws(int(px), int(py), v[i], rng)) for i in range(len(v))]
+        tail = cnt = None
+        if needs_tail:
+            cnt = np.array([len(t) for t in tails], np.int32)
+            tail = np.zeros((len(tails), max(1, int(cnt.max()))), np.float64)
+            for i, t in enumerate(tails):
+                tail[i, :len(t)] = t
+        return HostBufferSampler(self.camera, self.samplesPerPixel, pixels, np.concatenate(vecs), tail, cnt)
 
 
 class HostBufferSampler:
@@ -1241,10 +1372,24 @@ class SamplerRenderer:
                 else:
                     d.max_tail = s.tail.shape[1]
             keep = [s.pixel_xy, s.sample_vec, s.tail, s.tail_offsets]
+        elif isinstance(self.sampler, StratifiedSampler):
+            d.sampler_mode = _abi.DR_SAMPLER_STRATIFIED if self.sampler.jitterSamples else _abi.DR_SAMPLER_STRATIFIED_NOJITTER
+            d.strat_xsamples = self.sampler.xPixelSamples
+            d.seed = self.sampler.seed
         else:
             d.sampler_mode = _abi.DR_SAMPLER_COUNTER
             d.seed = self.sampler.seed
         return d, keep
+
+    def generate_samples(self, scene, pixels):
+        """dr_generate_samples: the device sampler's vectors for the raster pixels `pixels` ([n, 2]) -> [n * spp, nFloats] f32."""
+        d, keep = self.describe()
+        dev = scene._device()
+        pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        nf = _abi.lib().dr_scene_sample_floats(dev.handle, d.integrator)
+        out = np.zeros((len(pixels) * d.spp, nf), dtype=np.float32)
+        _abi.check(_abi.lib().dr_generate_samples(dev.handle, C.byref(d), pixels.ctypes.data, len(pixels), out.ctypes.data, nf))
+        return out
 
     def render(self, scene):
         film = self.camera.film
@@ -1321,6 +1466,7 @@ def RegisterStandardPlugins():
     Plugin.register("volumeIntegrator", "emission", lambda ps=None: EmissionIntegrator((ps or {}).get("stepsize", 1.0)))
     Plugin.register("renderer", "sampler", SamplerRenderer)
     Plugin.register("sampler", "lowdiscrepancy", LowDiscrepancySampler)
+    Plugin.register("sampler", "stratified", StratifiedSampler)
     Plugin.register("film", "image", ImageFilm)
     Plugin.register("pixelSampler", "linear", lambda ps=None: LinearPixelSampler())
     Plugin.register("pixelSampler", "tile", lambda ps=None: TilePixelSampler((ps or {}).get("tilesize", 32), (ps or {}).get("random", True)))

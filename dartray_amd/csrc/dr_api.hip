@@ -509,6 +509,8 @@ struct LayoutOps {
   decltype(&launch_trace_coherent) trace_coherent;
   decltype(&trace_kernel_id) trace_kernel_id;
   decltype(&launch_gen_samples) gen_samples;
+  decltype(&launch_gen_strat) gen_strat;
+  decltype(&launch_export_samples) export_samples;
   decltype(&launch_mark_alive) mark_alive;
   decltype(&launch_sum_alive) sum_alive;
   decltype(&launch_transpose_samples) transpose_samples;
@@ -521,9 +523,9 @@ struct LayoutOps {
   int stateWords;  // 4-byte words of fixed path state per slot in this layout (a tile is 64 of them + the sample region):
                    // what the kernels' own translation unit was compiled with (layout_state_words), not a constant repeated here
 };
-static const LayoutOps kLayout64 = {&launch_trace, &launch_trace_coherent, &trace_kernel_id, &launch_gen_samples, &launch_mark_alive, &launch_sum_alive, &launch_transpose_samples, &launch_raygen, &launch_shade_path,
+static const LayoutOps kLayout64 = {&launch_trace, &launch_trace_coherent, &trace_kernel_id, &launch_gen_samples, &launch_gen_strat, &launch_export_samples, &launch_mark_alive, &launch_sum_alive, &launch_transpose_samples, &launch_raygen, &launch_shade_path,
                                     &launch_env, &launch_shade_direct, &launch_shade_spec, &launch_film, layout_state_words()};
-static const LayoutOps kLayoutSp4 = {&sp4::launch_trace, &sp4::launch_trace_coherent, &sp4::trace_kernel_id, &sp4::launch_gen_samples, &sp4::launch_mark_alive, &sp4::launch_sum_alive, &sp4::launch_transpose_samples, &sp4::launch_raygen,
+static const LayoutOps kLayoutSp4 = {&sp4::launch_trace, &sp4::launch_trace_coherent, &sp4::trace_kernel_id, &sp4::launch_gen_samples, &sp4::launch_gen_strat, &sp4::launch_export_samples, &sp4::launch_mark_alive, &sp4::launch_sum_alive, &sp4::launch_transpose_samples, &sp4::launch_raygen,
                                      &sp4::launch_shade_path, &sp4::launch_env, &sp4::launch_shade_direct, &sp4::launch_shade_spec,
                                      &sp4::launch_film, sp4::layout_state_words()};
 
@@ -552,7 +554,7 @@ int dr_set_option(const char* name, const char* value) {
   else g_options.erase(n);          // null: back to the environment's value
   return DR_OK;
 }
-const char* dr_version(void) { return "dartray_amd 0.6 (gfx950, abi 7)"; }
+const char* dr_version(void) { return "dartray_amd 0.6 (gfx950, abi 8)"; }
 int32_t dr_abi_version(void) { return DR_ABI_VERSION; }
 
 int dr_init(int device) {
@@ -1475,6 +1477,10 @@ struct RenderPlan {
   const LayoutOps* L = nullptr;  // state layout of the NEXT batch (the layout pilot decides it after the first calibration batch)
   int spp = 0;
   bool direct = false, dlSpec = false, envStage = false, hostBuf = false, packedTail = false;
+  bool strat = false;     // DR_SAMPLER_STRATIFIED(_NOJITTER): the device sampler writes the float sample form
+  int stratX = 0;         //   xPixelSamples (yPixelSamples = spp / stratX)
+  // the device sampler's launches for one batch (BatchRunner::loadSamples, dr_generate_samples)
+  void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
   int needTail = 0;       // RNG draws a path can make beyond the sample vector (host-buffer mode: the recorded tail)
   bool layoutKnown = false;
   int maxStateWords = 0;  // words per slot the workspace is sized for (both layouts while the layout is not known)
@@ -1491,11 +1497,19 @@ struct RenderPlan {
   bool calibrate() const { return calibrateTrace || measureLayout; }
 };
 
+void RenderPlan::genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const {
+  if (strat) L->gen_strat(rpB, st, np, stratX, s);
+  else L->gen_samples(rpB, st, np, s);
+}
+
 // What the call asks for, checked, as RenderParams + the flags every later unit reads; which pixels it traces.
 int planRender(RenderPlan& P) {
   DrScene* sc = P.sc;
   const DrRenderDesc* rd = P.rd;
   const int spp = P.spp = rd->spp;
+  P.strat = rd->sampler_mode == DR_SAMPLER_STRATIFIED || rd->sampler_mode == DR_SAMPLER_STRATIFIED_NOJITTER;
+  if (P.strat && (spp <= 0 || (spp & (spp - 1)) != 0 || spp > 4096))
+    return fail(DR_ERR_UNSUPPORTED, "stratified sampler: xsamples * ysamples must be a power of two, at most 4096 (the slot -> pixel maps of the batches are shifts)");
   if (spp <= 0 || (spp & (spp - 1)) != 0) return fail(DR_ERR_INVALID, "spp must be a power of two (low_discrepancy_sampler.dart:43-49)");
   if (spp > 4096) return fail(DR_ERR_UNSUPPORTED, "spp > 4096 (one pixel's shuffle table of a 16-pixel sampler group would not fit the LDS)");
   if (rd->integrator != DR_INTEGRATOR_PATH && rd->integrator != DR_INTEGRATOR_DIRECT_ALL && rd->integrator != DR_INTEGRATOR_DIRECT_ONE)
@@ -1547,7 +1561,20 @@ int planRender(RenderPlan& P) {
   rp.deferredNee = rd->integrator == DR_INTEGRATOR_PATH ? 1 : 0;
   rp.genMask = 0ull;
   rp.genSlowDraws = dr_opt("DARTRAY_GEN_SLOW_DRAWS").set ? 1 : 0;
-  if (rd->integrator == DR_INTEGRATOR_PATH && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
+  if (P.strat) {
+    // StratifiedSampler (stratified_sampler.dart:39-54): xs * ys samples per pixel.  The slot -> pixel maps of the batch machinery are
+    // shifts, hence the power of two (checked above); roundSize is the identity (:63-65) while the scene's DirectLighting slot layout is
+    // LowDiscrepancySampler's rounded one, so a light's nsamples must be its own rounding.
+    const int xs = rd->strat_xsamples;
+    if (xs <= 0 || spp % xs != 0)
+      return fail(DR_ERR_INVALID, "stratified sampler: strat_xsamples must be positive and divide spp (spp = xsamples * ysamples)");
+    if (rd->integrator == DR_INTEGRATOR_DIRECT_ALL)
+      for (int n : sc->lightNSamples)
+        if (n > 1 && (n & (n - 1)) != 0)
+          return fail(DR_ERR_UNSUPPORTED, "stratified sampler: a light's nsamples must be a power of two (StratifiedSampler.roundSize is the identity, the scene's sample layout is the rounded one)");
+    P.stratX = xs;
+  }
+  if (!P.strat && rd->integrator == DR_INTEGRATOR_PATH && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
     // What the path kernels read of a pixel sample (dr_kernels.hip: k_raygen, load_shade_in, k_film): the image sample,
     // the lens sample of a thin-lens camera, and per SAMPLE_DEPTH level b <= maxDepth the light number, the light
     // sample (component + position), the BSDF and path directions; the two uComponent slots only where a material has
@@ -1581,7 +1608,7 @@ int planRender(RenderPlan& P) {
     const int64_t np = rd->nsamples / spp;
     P.pixels.resize(np);
     for (int64_t i = 0; i < np; ++i) P.pixels[i] = make_int2(rd->pixel_xy[2 * i], rd->pixel_xy[2 * i + 1]);
-  } else if (rd->sampler_mode == DR_SAMPLER_COUNTER) {
+  } else if (rd->sampler_mode == DR_SAMPLER_COUNTER || P.strat) {
     enumeratePixels(rp, rd, P.pixels);
   } else {
     return fail(DR_ERR_INVALID, "unknown sampler mode");
@@ -1605,8 +1632,8 @@ int planBatches(RenderPlan& P) {
   // Sample vectors: the on-device LD sampler stores permuted indices + scrambles (compact form) whenever every LD block
   // has one entry per pixel sample; host buffers and multi-entry blocks (DirectLighting with nsamples > 1) use floats.
   SampleForm& sf = P.sf;
-  sf.compact = !P.hostBuf && rp.blocks == nullptr;
-  if (!sf.compact && !P.hostBuf && spp > 1024)
+  sf.compact = !P.hostBuf && !P.strat && rp.blocks == nullptr;  // (the stratified sampler's values are no function of an index: floats)
+  if (!sf.compact && !P.hostBuf && !P.strat && spp > 1024)
     return fail(DR_ERR_UNSUPPORTED, "spp > 1024 with LD blocks of several entries per sample (DirectLighting with nsamples > 1): the float-form sampler's table exceeds the LDS");
   sf.nFloats = rp.nFloats;
   sf.nBlocks = 3 + rp.n1D + (rp.nFloats - 5 - rp.n1D) / 2;
@@ -1868,7 +1895,7 @@ int BatchRunner::loadSamples() {
     st.markAlive = w.alive.p;  // k_trace_pk: the groups whose camera rays hit something
     st.markShift = (uint32_t)rp.sppShift + 6u;
   } else {
-    L.gen_samples(rp, st, np, s);
+    P.genSamples(rp, st, np);
     if (P.sf.compact && rp.genMask) {
       sc->genDoneHost += (unsigned long long)np * (unsigned)__builtin_popcountll(rp.genMask);
       sc->genNamed += (unsigned long long)np * (unsigned)__builtin_popcountll(rp.genMask);
@@ -2296,6 +2323,43 @@ int dr_enumerate_pixels(const DrRenderDesc* rd, int32_t* out_xy, uint64_t cap, u
       out_xy[2 * i] = pixels[i].x;
       out_xy[2 * i + 1] = pixels[i].y;
     }
+  }
+  return DR_OK;
+}
+
+int dr_generate_samples(DrScene* sc, const DrRenderDesc* rd, const int32_t* pixel_xy, uint64_t npix, float* out, int32_t stride) {
+  if (!sc || !rd || !pixel_xy || !out) return fail(DR_ERR_INVALID, "null argument");
+  if (rd->sampler_mode == DR_SAMPLER_HOST_BUFFER) return fail(DR_ERR_INVALID, "dr_generate_samples: the host-buffer mode has no device sampler");
+  if (npix == 0) return DR_OK;
+  RenderPlan P;
+  P.sc = sc;
+  P.rd = rd;
+  int rc = planRender(P);
+  if (rc) return rc;
+  if (stride < P.rp.nFloats) return fail(DR_ERR_INVALID, "dr_generate_samples: stride smaller than the sample vector");
+  if (npix * (uint64_t)P.spp >= (1ull << 31)) return fail(DR_ERR_UNSUPPORTED, "dr_generate_samples: more than 2^31 samples in one call");
+  // the plan of a render of these pixels: the same sample form, batches and launches (launch_gen_samples), every LD block produced
+  P.rp.genMask = 0ull;
+  P.pixels.resize(npix);
+  for (uint64_t i = 0; i < npix; ++i) P.pixels[i] = make_int2(pixel_xy[2 * i], pixel_xy[2 * i + 1]);
+  P.npixTotal = P.pixels.size();
+  rc = planBatches(P);
+  if (rc) return rc;
+  rc = allocWorkspace(sc, sc->ws, P.cap, P.sf, P.pixPerBatch, rd->max_tail, false, P.maxStateWords);
+  if (rc) return rc;
+  HIP_TRY(sc->ws.pix.alloc(P.npixTotal));
+  HIP_TRY(hipMemcpyAsync(sc->ws.pix.p, P.pixels.data(), P.npixTotal * sizeof(int2), hipMemcpyHostToDevice, P.s));
+  DevBuf<float> aos;
+  HIP_TRY(aos.alloc((size_t)P.cap * stride));
+  HIP_TRY(hipMemsetAsync(aos.p, 0, (size_t)P.cap * stride * sizeof(float), P.s));  // (the words of a row behind the vector)
+  for (size_t p0 = 0; p0 < P.npixTotal; p0 += P.pixPerBatch) {
+    const uint32_t np = (uint32_t)std::min<size_t>(P.pixPerBatch, P.npixTotal - p0), nslots = np * (uint32_t)P.spp;
+    const BatchState st = makeState(sc->ws, P.sf, sc->ws.pix.p + p0, nslots, false, P.L->stateWords);
+    P.genSamples(P.rp, st, np);
+    P.L->export_samples(P.rp, st, aos.p, stride, P.s);
+    HIP_TRY(hipGetLastError());  // (a launch that could not start)
+    HIP_TRY(hipMemcpyAsync(out + p0 * P.spp * (size_t)stride, aos.p, (size_t)nslots * stride * sizeof(float), hipMemcpyDeviceToHost, P.s));
+    HIP_TRY(hipStreamSynchronize(P.s));
   }
   return DR_OK;
 }

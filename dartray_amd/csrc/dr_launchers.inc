@@ -13,6 +13,9 @@ bool launch_trace_coherent(const DScene& sc, const BatchState& st, const uint32_
 // the kernel launch_trace would pick right now for this scene and ray kind, as a kernel id (1 / 2 / 3 / 5; switches included)
 int trace_kernel_id(const DScene& sc, int anyHit);
 void launch_gen_samples(const RenderParams& rp, const BatchState& st, uint32_t npix, hipStream_t s);
+// dr_sampler_strat.hip: the stratified device sampler (xsamples x spp / xsamples strata; jitter: rp.samplerMode) and dr_generate_samples' dump
+void launch_gen_strat(const RenderParams& rp, const BatchState& st, uint32_t npix, int xsamples, hipStream_t s);
+void launch_export_samples(const RenderParams& rp, const BatchState& st, float* out, int stride, hipStream_t s);
 void launch_mark_alive(const uint32_t* list, const uint32_t* nList, uint32_t shift, uint8_t* alive, hipStream_t s);
 void launch_sum_alive(const uint8_t* alive, uint32_t nGroups, uint32_t npix, const uint32_t nb[3], TraceCounters* ctr, hipStream_t s);
 void launch_transpose_samples(const float* aos, int stride, const BatchState& st, int nFloats, hipStream_t s);

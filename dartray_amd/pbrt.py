@@ -910,11 +910,10 @@ class DartRay:
         o = self.opt
         if o["rendererName"] != "sampler":
             raise UnsupportedFeature(f"Renderer \"{o['rendererName']}\": only 'sampler' is on the path")
-        if o["samplerName"] != "lowdiscrepancy":
-            raise UnsupportedFeature(f"Sampler \"{o['samplerName']}\": only 'lowdiscrepancy' is on the path")
+        if o["samplerName"] not in ("lowdiscrepancy", "stratified"):
+            raise UnsupportedFeature(f"Sampler \"{o['samplerName']}\": only 'lowdiscrepancy' and 'stratified' are on the path")
         film = self._makeFilm()
         camera = self._makeCamera(film)
-        nsamp = int(self.overrides.get("pixelsamples", o["samplerParams"].findOneInt("pixelsamples", 4)))
         pname, pps = o["pixelSamplerName"], o["pixelSamplerParams"]          # dartray.dart:980-996
         if pname == "tile":                                                  # tile_pixel_sampler.dart:102-106
             pixels = core.TilePixelSampler(pps.findOneInt("tilesize", 32), pps.findOneBool("random", True))
@@ -924,7 +923,19 @@ class DartRay:
             pixels = core.LinearPixelSampler()
         else:
             raise UnsupportedFeature(f"Pixels \"{pname}\"")
-        sampler = core.LowDiscrepancySampler(camera, nsamp, int(self.overrides.get("seed", 5489)), pixels)
+        seed = int(self.overrides.get("seed", 5489))
+        if o["samplerName"] == "stratified":                                 # StratifiedSampler.Create, stratified_sampler.dart:130-150
+            sp = o["samplerParams"]
+            both = sp.findOneInt("pixelsamples", None)  # sets BOTH xsamples and ysamples (the `pixelsamples` override is the LD sampler's count)
+            xs = int(both) if both is not None else sp.findOneInt("xsamples", 2)
+            ys = int(both) if both is not None else sp.findOneInt("ysamples", 2)
+            if xs < 1 or ys < 1 or (xs * ys) & (xs * ys - 1) or xs * ys > 4096:
+                raise UnsupportedFeature(f"Sampler \"stratified\" with {xs} x {ys} samples: xsamples * ysamples must be a power of two, "
+                                         "at most 4096 (the device's slot -> pixel maps are shifts)")
+            sampler = core.StratifiedSampler(camera, xs, ys, sp.findOneBool("jitter", True), seed, pixels)
+        else:
+            nsamp = int(self.overrides.get("pixelsamples", o["samplerParams"].findOneInt("pixelsamples", 4)))
+            sampler = core.LowDiscrepancySampler(camera, nsamp, seed, pixels)
         kw = dict(taskNum=self.overrides.get("taskNum", 0), taskCount=self.overrides.get("taskCount", 1))
         kw.update(renderer_kw)
         return core.SamplerRenderer(sampler, camera, self._makeSurfaceIntegrator(), core.EmissionIntegrator(), **kw)

@@ -222,6 +222,14 @@ typedef struct DrFilm {
 
 #define DR_SAMPLER_HOST_BUFFER 0 /* caller supplies sample vectors (+ the in-Li RNG draws) */
 #define DR_SAMPLER_COUNTER 1     /* on-device LD sampler, keyed per (pixel, block) / (pixel, sample) */
+/* On-device StratifiedSampler (stratified_sampler.dart:67-124) on keyed streams: one per pixel (the jittered image / lens / time strata
+ * and the two shuffles) and one per (pixel, sample) (the LatinHypercube draws of the integrator's slots); DESIGN.md section 2.7.
+ * spp = xsamples * ysamples with xsamples = DrRenderDesc.strat_xsamples; spp must be a power of two (<= 4096), and under
+ * DR_INTEGRATOR_DIRECT_ALL every light's nsamples must be a power of two as well (StratifiedSampler.roundSize is the identity, the scene's slot layout
+ * is the rounded one): DR_ERR_UNSUPPORTED otherwise.  _NOJITTER: `jitter false` -- every stratum's centre; the shuffles and the
+ * LatinHypercube draws stay random. */
+#define DR_SAMPLER_STRATIFIED 2
+#define DR_SAMPLER_STRATIFIED_NOJITTER 3
 
 /* Everything SamplerRenderer.render needs besides the Scene
  * (lib/renderers/sampler_renderer.dart:29-31,36-65). */
@@ -230,7 +238,7 @@ typedef struct DrRenderDesc {
   DrFilm film;
   int32_t integrator;
   int32_t max_depth; /* PathIntegrator.maxDepth / DirectLightingIntegrator.maxDepth (default 5) */
-  int32_t spp;       /* LowDiscrepancySampler.nPixelSamples, power of two */
+  int32_t spp;       /* LowDiscrepancySampler.nPixelSamples or StratifiedSampler's xPixelSamples * yPixelSamples, power of two */
   int32_t sampler_mode;
   int64_t seed; /* DR_SAMPLER_COUNTER */
   /* Work split.  task_*: the reference's GetSubWindow rectangle of the sampler
@@ -239,6 +247,7 @@ typedef struct DrRenderDesc {
    * round-robin over ranks; tile_count <= 1 disables it. */
   int32_t task_num, task_count;
   int32_t tile_rank, tile_count, tile_size;
+  int32_t strat_xsamples; /* DR_SAMPLER_STRATIFIED(_NOJITTER): xPixelSamples; yPixelSamples = spp / strat_xsamples, exactly.  Else ignored */
   /* DR_SAMPLER_HOST_BUFFER: nsamples camera samples, in reference order
    * (pixel-major, all spp of a pixel adjacent). */
   int64_t nsamples;
@@ -400,6 +409,14 @@ int dr_render_device(DrScene* scene, const DrRenderDesc* desc, void* film_dev, v
  * rank's round-robin tiles).  Host-only; out_xy may be NULL to query the count. */
 int dr_enumerate_pixels(const DrRenderDesc* desc, int32_t* out_xy, uint64_t cap, uint64_t* n_out);
 
+/* Diagnostics and tests: runs ONLY the device sampler of `desc` (DR_SAMPLER_COUNTER or DR_SAMPLER_STRATIFIED*) for the npix raster
+ * pixels pixel_xy[npix][2] -- the launches a render of those pixels makes, into the render's own workspace -- and copies the camera-sample
+ * vectors back: out[npix * spp][stride] in reference field order (imageU, imageV, lensU, lensV, time, oneD..., twoD...; the image
+ * sample as its fraction inside the pixel), stride >= dr_scene_sample_floats.  Every LD block is produced (a render may skip blocks no
+ * kernel reads).  The film window, the task / tile split and the seed of `desc` are read as a render reads them: the streams are keyed by
+ * a pixel's position in the full sampler extent. */
+int dr_generate_samples(DrScene* scene, const DrRenderDesc* desc, const int32_t* pixel_xy, uint64_t npix, float* out, int32_t stride);
+
 /* ImageFilm.writeImage on a device film: XYZ -> RGB, divide by weightSum. */
 int dr_film_resolve_device(const void* film_dev, int64_t npixels, void* rgb_dev, void* hip_stream);
 
@@ -448,8 +465,9 @@ const char* dr_version(void);
 /* The layout version of this header's structs and the meaning of its entry points.  A host compares dr_abi_version() of the library it
  * loaded with the DR_ABI_VERSION it was built against BEFORE it passes a struct: the structs carry no size field, so a host built against
  * an older header would hand the library a shorter object than it reads (version 5 -> 6: DrRenderDesc grew by tail_offsets, 1344 -> 1352
- * bytes; version 6 -> 7: DR_INTEGRATOR_DIRECT_ONE, dr_scene_workspace_bytes, the switch list of dr_set_option). */
-#define DR_ABI_VERSION 7
+ * bytes; version 6 -> 7: DR_INTEGRATOR_DIRECT_ONE, dr_scene_workspace_bytes, the switch list of dr_set_option;
+ * 8: DR_SAMPLER_STRATIFIED, strat_xsamples -- the former padding at offset 1292 -- and dr_generate_samples). */
+#define DR_ABI_VERSION 8
 int32_t dr_abi_version(void);
 
 /* Tuning / diagnostic switches.  Every switch is also an environment variable of the same name (DARTRAY_<NAME>); a
@@ -544,6 +562,7 @@ DR_ABI_OFFSET(DrRenderDesc, integrator, 1248);
 DR_ABI_OFFSET(DrRenderDesc, seed, 1264);
 DR_ABI_OFFSET(DrRenderDesc, task_num, 1272);
 DR_ABI_OFFSET(DrRenderDesc, tile_rank, 1280);
+DR_ABI_OFFSET(DrRenderDesc, strat_xsamples, 1292);
 DR_ABI_OFFSET(DrRenderDesc, nsamples, 1296);
 DR_ABI_OFFSET(DrRenderDesc, pixel_xy, 1304);
 DR_ABI_OFFSET(DrRenderDesc, sample_vec, 1312);

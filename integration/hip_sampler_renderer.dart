@@ -30,7 +30,7 @@
  * TriangleMesh / Sphere / Disk shapes, matte / mirror / glass / plastic
  * materials with constant textures, DiffuseAreaLight / InfiniteAreaLight /
  * point, spot and distant lights, PathIntegrator and DirectLightingIntegrator
- * ("all"), LowDiscrepancySampler, ImageFilm with any Filter, the three
+ * ("all"), the low-discrepancy and the stratified sampler, ImageFilm with any Filter, the three
  * cameras.  Anything else is reported through LogSevere (log.dart:42-47),
  * never approximated.
  ****************************************************************************/
@@ -150,6 +150,7 @@ const int OFF_DrRenderDesc_task_count = 1276;
 const int OFF_DrRenderDesc_tile_rank = 1280;
 const int OFF_DrRenderDesc_tile_count = 1284;
 const int OFF_DrRenderDesc_tile_size = 1288;
+const int OFF_DrRenderDesc_strat_xsamples = 1292;  // DR_SAMPLER_STRATIFIED(_NOJITTER): xPixelSamples
 const int OFF_DrRenderDesc_nsamples = 1296;
 const int OFF_DrRenderDesc_pixel_xy = 1304;
 const int OFF_DrRenderDesc_sample_vec = 1312;
@@ -168,6 +169,8 @@ const int DR_PRIM_QUADRIC = 0xFFFFFFFF, DR_QUADRIC_SPHERE = 1, DR_QUADRIC_DISK =
 const int DR_CAMERA_PERSPECTIVE = 0, DR_CAMERA_ORTHOGRAPHIC = 1, DR_CAMERA_ENVIRONMENT = 2;
 const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2;
 const int DR_SAMPLER_COUNTER = 1;
+const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
+const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
 
 typedef _InitC = Int32 Function(Int32);
 typedef _InitD = int Function(int);
@@ -237,12 +240,14 @@ class HipSamplerRenderer extends Renderer {
   static final _InitD _init = _lib.lookupFunction<_InitC, _InitD>('dr_init');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
   /// library of another layout version is refused before any struct crosses the boundary.
-  static const int ABI_VERSION = 7;
+  static const int ABI_VERSION = 8;
   static DynamicLibrary _open() {
     DynamicLibrary l = DynamicLibrary.open('libdartray_hip.so');
     _CommVoidD abi = l.lookupFunction<_CommVoidC, _CommVoidD>('dr_abi_version');
     if (abi() != ABI_VERSION) {
-      LogSevere('libdartray_hip.so has ABI version ${abi()}, this binding was written against $ABI_VERSION');
+      String msg = 'libdartray_hip.so has ABI version ${abi()}, this binding was written against $ABI_VERSION';
+      LogSevere(msg);
+      throw new StateError(msg);  // (a logger installed by the host need not throw: log.dart:42-47 is the default's behaviour)
     }
     return l;
   }
@@ -769,13 +774,27 @@ class HipSamplerRenderer extends Renderer {
       } else {
         _unsupported('surface integrator ${surfaceIntegrator.runtimeType}');
       }
-      if (sampler is! LowDiscrepancySampler) {
+      // The sampler object decides the mode, and a stratified sampler's own public fields (samplers/stratified_sampler.dart:152-155)
+      // are the one source of its strata.  (The class is told by its name: on the VM, where dart:ffi runs, runtimeType prints it.)
+      final bool stratified = '${sampler.runtimeType}' == 'StratifiedSampler';
+      if (!stratified && sampler is! LowDiscrepancySampler) {
         _unsupported('sampler ${sampler.runtimeType}');
       }
-      rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
-      // The device runs the same LD sampler with one keyed RNG stream per (pixel, LD block) / (pixel, sample) instead
-      // of the task's single serial Random(taskNum) (sampler_renderer.dart:137): same estimator, different numbers.
-      rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_COUNTER);
+      // The device runs the same LD / stratified sampler with one keyed RNG stream per (pixel, LD block) / pixel / (pixel, sample)
+      // instead of the task's single serial Random(taskNum) (sampler_renderer.dart:137): same estimator, different numbers.
+      if (stratified) {
+        dynamic strat = sampler;
+        int xPixelSamples = strat.xPixelSamples;
+        int yPixelSamples = strat.yPixelSamples;
+        bool jitterSamples = strat.jitterSamples;
+        // xPixelSamples * yPixelSamples must be a power of two (the library answers DR_ERR_UNSUPPORTED otherwise)
+        rd.i32(OFF_DrRenderDesc_spp, xPixelSamples * yPixelSamples);
+        rd.i32(OFF_DrRenderDesc_sampler_mode, jitterSamples ? DR_SAMPLER_STRATIFIED : DR_SAMPLER_STRATIFIED_NOJITTER);
+        rd.i32(OFF_DrRenderDesc_strat_xsamples, xPixelSamples);
+      } else {
+        rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
+        rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_COUNTER);
+      }
       rd.i64(OFF_DrRenderDesc_seed, seed);
       rd.i32(OFF_DrRenderDesc_task_num, taskNum);         // GetSubWindow rectangle (common.dart:52-73)
       rd.i32(OFF_DrRenderDesc_task_count, taskCount);
