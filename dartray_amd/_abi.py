@@ -18,6 +18,7 @@ DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
 DR_SAMPLER_STRATIFIED = 2
 DR_SAMPLER_STRATIFIED_NOJITTER = 3
+DR_SAMPLER_ADAPTIVE = 4  # spp = maxSamples, strat_xsamples = minSamples
 DR_LIGHT_DIFFUSE_AREA = 0
 DR_LIGHT_INFINITE = 1
 DR_LIGHT_POINT = 2
@@ -132,7 +133,7 @@ class DrRenderStats(C.Structure):
 
 
 DR_COMM_ID_BYTES = 128
-DR_ABI_VERSION = 8  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
+DR_ABI_VERSION = 9  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
 
 
 # name -> (restype, argtypes): every symbol include/dartray_hip.h declares.
@@ -160,6 +161,7 @@ EXPORTS = {
     "dr_render_sharded": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_int32, C.c_void_p, C.c_void_p]),
     "dr_film_resolve_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dr_enumerate_pixels": (C.c_int, [C.POINTER(DrRenderDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "dr_scene_get_adaptive_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dr_generate_samples": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32]),
     "dr_get_stats": (C.c_int, [C.c_void_p, C.POINTER(DrRenderStats)]),
     "dr_reset_stats": (C.c_int, [C.c_void_p]),

@@ -665,6 +665,16 @@ class _DeviceScene:
                 "pilot_batches": int(arr[4]), "batches": int(arr[5]), "trace_wg_per_cu": int(arr[6]), "overlap_any": int(arr[7]) & 1,
                 "coherent_camera": (int(arr[7]) >> 1) & 1, "lazy_gen": (int(arr[7]) >> 3) & 1}
 
+    def adaptive_pixels(self):
+        """Raster pixels ([n, 2] int32, no particular order) the last render of this scene supersampled (dr_scene_get_adaptive_pixels:
+        an AdaptiveSampler's pixels traced at maxSamples; empty after any other sampler's render)."""
+        n = C.c_uint64(0)
+        _abi.check(_abi.lib().dr_scene_get_adaptive_pixels(self.handle, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 2), dtype=np.int32)
+        if n.value:
+            _abi.check(_abi.lib().dr_scene_get_adaptive_pixels(self.handle, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     def workspace_bytes(self):
         """Device memory the scene's path-state workspace holds right now (dr_scene_workspace_bytes)."""
         n = C.c_uint64(0)
@@ -1262,6 +1272,49 @@ class StratifiedSampler:
         return HostBufferSampler(self.camera, self.samplesPerPixel, pixels, np.concatenate(vecs), tail, cnt)
 
 
+class AdaptiveSampler:
+    """samplers/adaptive_sampler.dart:36-220: every pixel gets minSamples low-discrepancy samples; a pixel whose samples' contrast
+    exceeds 0.5 (needsSupersampling, method "contrast") is sampled again with maxSamples, and only that second set reaches the
+    film.  On the device (DR_SAMPLER_ADAPTIVE) both passes are the LD sampler's keyed streams and the decision is a
+    kernel.  The constructor applies the reference's rules (:40-83) in its order: swap, round each up to a power of two, at least two
+    initial samples, more maximum than minimum samples."""
+
+    METHODS = ("contrast", "shapeid")
+
+    def __init__(self, camera, minsamples=4, maxsamples=32, method="contrast", seed=5489, pixels=None):
+        if method == "shapeid":
+            raise ValueError("AdaptiveSampler method 'shapeid' is not supported: the camera hit's shape and primitive ids are not "
+                             "kept per sample on the device (method 'contrast' is)")
+        if method != "contrast":
+            raise ValueError("AdaptiveSampler method must be 'contrast' (got %r)" % (method,))
+        self.camera = camera
+        self.method = method
+        mins, maxs = int(minsamples), int(maxsamples)
+        if mins < 1 or maxs < 1:
+            raise ValueError("AdaptiveSampler: minsamples and maxsamples must be positive")
+        self.samplesPerPixel = RoundUpPow2(max(mins, maxs))  # the Sampler base class's count, from the arguments as given (:42-43)
+        if mins > maxs:
+            mins, maxs = maxs, mins
+        self.minSamples = RoundUpPow2(mins)
+        self.maxSamples = RoundUpPow2(maxs)
+        if self.minSamples < 2:
+            self.minSamples = 2
+        if self.minSamples == self.maxSamples:
+            self.maxSamples *= 2
+        if self.minSamples > self.maxSamples:  # (maxsamples 1: the two initial samples exceed it and nothing in the reference mends that)
+            raise ValueError("AdaptiveSampler needs more maximum than minimum samples (got minsamples %d, maxsamples %d)" % (int(minsamples), int(maxsamples)))
+        if self.maxSamples > 4096:
+            raise ValueError("AdaptiveSampler: maxsamples %d exceeds the device sampler's 4096" % self.maxSamples)
+        self.seed = int(seed)
+        self.pixelSampler = pixels or LinearPixelSampler()
+
+    def roundSize(self, size):  # :93-95
+        return RoundUpPow2(size)
+
+    def maximumSampleCount(self):  # :97-99
+        return self.maxSamples
+
+
 class HostBufferSampler:
     """Explicit camera samples: pixel_xy [npix,2] int32, sample_vec [npix*spp, nfloats] f32
     (imageU, imageV, lensU, lensV, time, oneD..., twoD...), tail [npix*spp, max_tail] f64 =
@@ -1376,18 +1429,25 @@ class SamplerRenderer:
             d.sampler_mode = _abi.DR_SAMPLER_STRATIFIED if self.sampler.jitterSamples else _abi.DR_SAMPLER_STRATIFIED_NOJITTER
             d.strat_xsamples = self.sampler.xPixelSamples
             d.seed = self.sampler.seed
+        elif isinstance(self.sampler, AdaptiveSampler):
+            d.sampler_mode = _abi.DR_SAMPLER_ADAPTIVE
+            d.spp = self.sampler.maxSamples
+            d.strat_xsamples = self.sampler.minSamples  # (the field doubles as minSamples in this mode)
+            d.seed = self.sampler.seed
         else:
             d.sampler_mode = _abi.DR_SAMPLER_COUNTER
             d.seed = self.sampler.seed
         return d, keep
 
     def generate_samples(self, scene, pixels):
-        """dr_generate_samples: the device sampler's vectors for the raster pixels `pixels` ([n, 2]) -> [n * spp, nFloats] f32."""
+        """dr_generate_samples: the device sampler's vectors for the raster pixels `pixels` ([n, 2]) -> [n * spp, nFloats] f32
+        (AdaptiveSampler: the first pass's, spp = minSamples)."""
         d, keep = self.describe()
         dev = scene._device()
         pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
         nf = _abi.lib().dr_scene_sample_floats(dev.handle, d.integrator)
-        out = np.zeros((len(pixels) * d.spp, nf), dtype=np.float32)
+        spp = d.strat_xsamples if d.sampler_mode == _abi.DR_SAMPLER_ADAPTIVE else d.spp
+        out = np.zeros((len(pixels) * spp, nf), dtype=np.float32)
         _abi.check(_abi.lib().dr_generate_samples(dev.handle, C.byref(d), pixels.ctypes.data, len(pixels), out.ctypes.data, nf))
         return out
 
@@ -1402,6 +1462,10 @@ class SamplerRenderer:
         del keep
         self.last_stats = dev.stats()
         return OutputImage(film.left, film.top, film.width, film.height, out_rgb, out_film)
+
+    def supersampled_pixels(self, scene):
+        """The raster pixels the last render of `scene` traced at maxSamples ([n, 2] int32, no particular order; AdaptiveSampler)."""
+        return scene._device().adaptive_pixels()
 
     def render_sharded(self, scene, root=0):
         """One rank's part of a sharded render (dr_render_sharded): this renderer's tile / task share, ONE film reduce over
@@ -1467,6 +1531,7 @@ def RegisterStandardPlugins():
     Plugin.register("renderer", "sampler", SamplerRenderer)
     Plugin.register("sampler", "lowdiscrepancy", LowDiscrepancySampler)
     Plugin.register("sampler", "stratified", StratifiedSampler)
+    Plugin.register("sampler", "adaptive", AdaptiveSampler)
     Plugin.register("film", "image", ImageFilm)
     Plugin.register("pixelSampler", "linear", lambda ps=None: LinearPixelSampler())
     Plugin.register("pixelSampler", "tile", lambda ps=None: TilePixelSampler((ps or {}).get("tilesize", 32), (ps or {}).get("random", True)))

@@ -78,6 +78,8 @@ struct Workspace {
   DevBuf<float> specFrames;         //   [maxDepth][cap] SpecFrame
   DevBuf<int32_t> specSp;           //   [cap]
   DevBuf<int2> pix;
+  DevBuf<int2> adaptList;       // DR_SAMPLER_ADAPTIVE: the raster pixels the first pass flagged (k_adaptive_decide), the second pass's pixel array
+  DevBuf<uint32_t> adaptCount;  //   [0] their number, [1] those inside the film window
   DevBuf<float> filterTable, aosSamples;
   int spillGrid = 0;
 };
@@ -150,6 +152,7 @@ struct DrScene {
   // what the last dr_render_device call actually ran with (dr_scene_last_render_info): state layout, the traversal kernels of
   // its last batch, a reserved word (-1), calibration batches, workgroups per CU
   int32_t lastInfo[8] = {0, 0, 0, -1, 0, 0, 0, 0};
+  uint32_t adaptiveN = 0;  // dr_scene_get_adaptive_pixels: entries of ws.adaptList the last render left (0 after any other sampler's render)
   std::vector<int32_t> lightNSamples;
   bool hasSpecular = false;  // some material is a mirror / glass
   bool hasDeltaLight = false;
@@ -511,6 +514,7 @@ struct LayoutOps {
   decltype(&launch_gen_samples) gen_samples;
   decltype(&launch_gen_strat) gen_strat;
   decltype(&launch_export_samples) export_samples;
+  decltype(&launch_adaptive_decide) adaptive_decide;
   decltype(&launch_mark_alive) mark_alive;
   decltype(&launch_sum_alive) sum_alive;
   decltype(&launch_transpose_samples) transpose_samples;
@@ -523,9 +527,9 @@ struct LayoutOps {
   int stateWords;  // 4-byte words of fixed path state per slot in this layout (a tile is 64 of them + the sample region):
                    // what the kernels' own translation unit was compiled with (layout_state_words), not a constant repeated here
 };
-static const LayoutOps kLayout64 = {&launch_trace, &launch_trace_coherent, &trace_kernel_id, &launch_gen_samples, &launch_gen_strat, &launch_export_samples, &launch_mark_alive, &launch_sum_alive, &launch_transpose_samples, &launch_raygen, &launch_shade_path,
+static const LayoutOps kLayout64 = {&launch_trace, &launch_trace_coherent, &trace_kernel_id, &launch_gen_samples, &launch_gen_strat, &launch_export_samples, &launch_adaptive_decide, &launch_mark_alive, &launch_sum_alive, &launch_transpose_samples, &launch_raygen, &launch_shade_path,
                                     &launch_env, &launch_shade_direct, &launch_shade_spec, &launch_film, layout_state_words()};
-static const LayoutOps kLayoutSp4 = {&sp4::launch_trace, &sp4::launch_trace_coherent, &sp4::trace_kernel_id, &sp4::launch_gen_samples, &sp4::launch_gen_strat, &sp4::launch_export_samples, &sp4::launch_mark_alive, &sp4::launch_sum_alive, &sp4::launch_transpose_samples, &sp4::launch_raygen,
+static const LayoutOps kLayoutSp4 = {&sp4::launch_trace, &sp4::launch_trace_coherent, &sp4::trace_kernel_id, &sp4::launch_gen_samples, &sp4::launch_gen_strat, &sp4::launch_export_samples, &sp4::launch_adaptive_decide, &sp4::launch_mark_alive, &sp4::launch_sum_alive, &sp4::launch_transpose_samples, &sp4::launch_raygen,
                                      &sp4::launch_shade_path, &sp4::launch_env, &sp4::launch_shade_direct, &sp4::launch_shade_spec,
                                      &sp4::launch_film, sp4::layout_state_words()};
 
@@ -554,7 +558,7 @@ int dr_set_option(const char* name, const char* value) {
   else g_options.erase(n);          // null: back to the environment's value
   return DR_OK;
 }
-const char* dr_version(void) { return "dartray_amd 0.6 (gfx950, abi 8)"; }
+const char* dr_version(void) { return "dartray_amd 0.6 (gfx950, abi 9)"; }
 int32_t dr_abi_version(void) { return DR_ABI_VERSION; }
 
 int dr_init(int device) {
@@ -1405,7 +1409,7 @@ int dr_scene_workspace_bytes(const DrScene* sc, uint64_t* bytes_out) {
   const Workspace& w = sc->ws;
   *bytes_out = w.tiles.bytes() + w.scr.bytes() + w.genState.bytes() + w.tail.bytes() + w.tailOff.bytes() + w.activeA.bytes() + w.activeB.bytes() +
                w.closestQ.bytes() + w.anyQ.bytes() + w.counters.bytes() + w.spill.bytes() + w.envQ.bytes() + w.alive.bytes() + w.roundA.bytes() +
-               w.roundB.bytes() + w.specFrames.bytes() + w.specSp.bytes() + w.pix.bytes() + w.filterTable.bytes() + w.aosSamples.bytes();
+               w.roundB.bytes() + w.specFrames.bytes() + w.specSp.bytes() + w.pix.bytes() + w.adaptList.bytes() + w.adaptCount.bytes() + w.filterTable.bytes() + w.aosSamples.bytes();
   return DR_OK;
 }
 
@@ -1481,6 +1485,14 @@ struct RenderPlan {
   int stratX = 0;         //   xPixelSamples (yPixelSamples = spp / stratX)
   // the device sampler's launches for one batch (BatchRunner::loadSamples, dr_generate_samples)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
+  // DR_SAMPLER_ADAPTIVE: two counter-mode passes.  This plan is the first (every pixel at adMin samples: spp,
+  // rp and sf are that pass's; its batches end with k_adaptive_decide); secondPass() derives the plan of the flagged pixels at adMax.
+  int adaptivePass = 0;   // 0: another sampler; 1 / 2: which pass of an adaptive render this plan runs
+  int adMin = 0, adMax = 0;
+  uint32_t adPixCap = 0;  // pixels of a second-pass batch at most (planBatches: against the workspace both passes share)
+  // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'
+  uint32_t wsCap = 0, wsPix = 0;
+  SampleForm wsSf;
   int needTail = 0;       // RNG draws a path can make beyond the sample vector (host-buffer mode: the recorded tail)
   bool layoutKnown = false;
   int maxStateWords = 0;  // words per slot the workspace is sized for (both layouts while the layout is not known)
@@ -1506,7 +1518,17 @@ void RenderPlan::genSamples(const RenderParams& rpB, const BatchState& st, uint3
 int planRender(RenderPlan& P) {
   DrScene* sc = P.sc;
   const DrRenderDesc* rd = P.rd;
-  const int spp = P.spp = rd->spp;
+  P.adaptivePass = rd->sampler_mode == DR_SAMPLER_ADAPTIVE ? 1 : 0;
+  if (P.adaptivePass) {
+    // AdaptiveSampler (adaptive_sampler.dart:53-83) after its own normalisation, which the host does: maxSamples in spp, minSamples in
+    // strat_xsamples.  Powers of two: both passes are LDPixelSample, and the slot -> pixel maps of the batches are shifts.
+    const int mn = rd->strat_xsamples, mx = rd->spp;
+    if (mn < 2 || mx > 4096 || mn >= mx || (mn & (mn - 1)) != 0 || (mx & (mx - 1)) != 0)
+      return fail(DR_ERR_INVALID, "adaptive sampler: minSamples (strat_xsamples) and maxSamples (spp) must be powers of two with 2 <= minSamples < maxSamples <= 4096");
+    P.adMin = mn;
+    P.adMax = mx;
+  }
+  const int spp = P.spp = P.adaptivePass ? P.adMin : rd->spp;  // (adaptive: this plan is the first pass)
   P.strat = rd->sampler_mode == DR_SAMPLER_STRATIFIED || rd->sampler_mode == DR_SAMPLER_STRATIFIED_NOJITTER;
   if (P.strat && (spp <= 0 || (spp & (spp - 1)) != 0 || spp > 4096))
     return fail(DR_ERR_UNSUPPORTED, "stratified sampler: xsamples * ysamples must be a power of two, at most 4096 (the slot -> pixel maps of the batches are shifts)");
@@ -1588,7 +1610,9 @@ int planRender(RenderPlan& P) {
     }
     rp.genMask = m;
   }
-  rp.samplerMode = rd->sampler_mode;
+  rp.samplerMode = P.adaptivePass ? DR_SAMPLER_COUNTER : rd->sampler_mode;  // (both adaptive passes are the LD sampler's keyed streams)
+  if (P.adaptivePass && rp.blocks && P.adMax > 1024)
+    return fail(DR_ERR_UNSUPPORTED, "adaptive sampler: maxSamples > 1024 with LD blocks of several entries per sample (DirectLighting with nsamples > 1): the float-form sampler's table exceeds the LDS");
   rp.seed = (uint64_t)rd->seed;
   const int perNee = rp.nLights > 0 ? 7 : 0;
   P.needTail = rd->integrator == DR_INTEGRATOR_PATH && rd->max_depth >= 3 ? (rd->max_depth - 2) * (perNee + 3) + std::max(0, rd->max_depth - 3) : 0;
@@ -1608,7 +1632,7 @@ int planRender(RenderPlan& P) {
     const int64_t np = rd->nsamples / spp;
     P.pixels.resize(np);
     for (int64_t i = 0; i < np; ++i) P.pixels[i] = make_int2(rd->pixel_xy[2 * i], rd->pixel_xy[2 * i + 1]);
-  } else if (rd->sampler_mode == DR_SAMPLER_COUNTER || P.strat) {
+  } else if (rd->sampler_mode == DR_SAMPLER_COUNTER || P.strat || P.adaptivePass) {
     enumeratePixels(rp, rd, P.pixels);
   } else {
     return fail(DR_ERR_INVALID, "unknown sampler mode");
@@ -1638,6 +1662,9 @@ int planBatches(RenderPlan& P) {
   sf.nFloats = rp.nFloats;
   sf.nBlocks = 3 + rp.n1D + (rp.nFloats - 5 - rp.n1D) / 2;
   sf.idxShift = spp > 256 ? 1 : 0;
+  // what the workspace's sample region is sized for: this form; adaptive: the second pass's (same blocks, wider indices above 256 spp)
+  P.wsSf = sf;
+  if (P.adaptivePass) P.wsSf.idxShift = P.adMax > 256 ? 1 : 0;
   // Camera samples in flight per batch.  The throughput end is one batch per image (2^28 slots: C2's whole sampler window, 64 GB of a
   // 288 GB MI355X); a scene's FIRST big render -- all a one-shot host ever does (Renderer.render once per task, dartray.dart:574) --
   // stays at 2^27 (C2: three batches, 21 GB, whose hipMalloc does not wait for the driver to scrub 64 GB: profiles/r05_alloc_probe.txt)
@@ -1652,7 +1679,7 @@ int planBatches(RenderPlan& P) {
     const uint64_t tailPerSlot = !(P.hostBuf && P.needTail > 0) ? 0ull
                                  : (P.packedTail ? 16ull + 8ull * ((rd->tail_offsets[rd->nsamples] - rd->tail_offsets[0]) / (uint64_t)rd->nsamples + 1ull)
                                                  : (uint64_t)rd->max_tail * 8);
-    const uint64_t perSlot = (uint64_t)P.maxStateWords * 4 + (uint64_t)(sf.svWords() + 15) / 16 + 20 + tailPerSlot + (P.hostBuf ? (uint64_t)rd->sample_stride * 4 : 0) +
+    const uint64_t perSlot = (uint64_t)P.maxStateWords * 4 + (uint64_t)(P.wsSf.svWords() + 15) / 16 + 20 + tailPerSlot + (P.hostBuf ? (uint64_t)rd->sample_stride * 4 : 0) +
                              (sf.compact ? (uint64_t)(16 * sf.nBlocks + spp - 1) / spp : 0) +  // scramble words + generator states, per (block, pixel)
                              (P.dlSpec ? (uint64_t)std::max(1, rd->max_depth) * sizeof(SpecFrame) + 12 : 0);
     size_t freeB = 0, totalB = 0;
@@ -1670,7 +1697,44 @@ int planBatches(RenderPlan& P) {
   if (P.nBatches > 1 && P.npixTotal <= pixCapBatch + pixCapBatch / 4) P.nBatches = 1;
   P.pixPerBatch = (uint32_t)((P.npixTotal + P.nBatches - 1) / P.nBatches);
   P.cap = P.pixPerBatch * (uint32_t)spp;
+  P.wsCap = P.cap;
+  P.wsPix = P.pixPerBatch;
+  if (P.adaptivePass) {
+    // The second pass runs in the workspace of the first: how many pixels are flagged is only known once the first pass has run, and
+    // a workspace sized for the worst case (every pixel at maxSamples) would be max / min times the first pass's.  Its batches hold
+    // as many slots as a first-pass batch -- or 2^22 where those are smaller, so that a small image's flagged pixels still go as a
+    // few launches -- and never more than every pixel of the render at maxSamples, nor less than one pixel.
+    const uint64_t worst = (uint64_t)P.npixTotal * (uint64_t)P.adMax;
+    const uint64_t slots2 = std::max<uint64_t>((uint64_t)P.adMax, std::min<uint64_t>(worst, std::max<uint64_t>(P.cap, std::min<uint64_t>(1ull << 22, maxSlots))));
+    P.adPixCap = (uint32_t)(slots2 / (uint64_t)P.adMax);
+    P.wsCap = std::max(P.cap, P.adPixCap * (uint32_t)P.adMax);
+    P.wsPix = std::max(P.pixPerBatch, P.adPixCap);
+  }
   return DR_OK;
+}
+
+// The second pass of an adaptive render: the nFlagged pixels of the device list at maxSamples, as ordinary counter-mode batches.
+// Everything that depends on the sample count is derived again; no pilot runs (the first pass's choices stand).
+bool lazyGenFor(const RenderPlan& P);
+RenderPlan secondPass(const RenderPlan& P, uint32_t nFlagged) {
+  RenderPlan Q = P;
+  Q.adaptivePass = 2;
+  Q.spp = Q.rp.spp = P.adMax;
+  Q.rp.sppShift = 0;
+  while ((1 << Q.rp.sppShift) < Q.spp) ++Q.rp.sppShift;
+  Q.sf = P.wsSf;
+  Q.lazyGen = lazyGenFor(Q);
+  Q.calibrateTrace = Q.measureLayout = false;
+  Q.npixTotal = nFlagged;
+  Q.nBatches = ((uint64_t)nFlagged + P.adPixCap - 1) / P.adPixCap;
+  Q.pixPerBatch = (uint32_t)(((uint64_t)nFlagged + Q.nBatches - 1) / Q.nBatches);
+  Q.cap = Q.pixPerBatch * (uint32_t)Q.spp;
+  return Q;
+}
+
+bool lazyGenFor(const RenderPlan& P) {
+  return !P.hostBuf && P.sf.compact && P.rp.genMask != 0ull && P.rd->integrator == DR_INTEGRATOR_PATH && P.coherentCamera && !P.sc->d.nquads && P.spp >= 64 &&
+         !dr_opt("DARTRAY_LAZY_GEN").isZero();
 }
 
 // Workspace, streams, the pilot decision (which reorders the pixels), and the uploads every batch reads.
@@ -1680,7 +1744,7 @@ int prepareRender(RenderPlan& P) {
   const int spp = P.spp;
   const auto tAlloc0 = std::chrono::steady_clock::now();
   const uint32_t capBefore = sc->ws.cap;
-  int rc = allocWorkspace(sc, sc->ws, P.cap, P.sf, P.pixPerBatch, rd->max_tail, P.hostBuf && P.needTail > 0 && !P.packedTail, P.maxStateWords);
+  int rc = allocWorkspace(sc, sc->ws, P.wsCap, P.wsSf, P.wsPix, rd->max_tail, P.hostBuf && P.needTail > 0 && !P.packedTail, P.maxStateWords);
   if (rc) return rc;
   if (dr_opt("DARTRAY_VERBOSE") && sc->ws.cap != capBefore) {
     (void)hipDeviceSynchronize();
@@ -1702,8 +1766,7 @@ int prepareRender(RenderPlan& P) {
   P.coherentCamera = !dr_opt("DARTRAY_COHERENT_CAMERA").isZero() && !P.dlSpec;
   // lazy sample generation (DARTRAY_LAZY_GEN=0: every block for every pixel up front): needs the device sampler's compact form, the keyed
   // per-(pixel, block) streams (a block that is left out disturbs no other) and k_trace_pk's marks of the camera rays that hit
-  P.lazyGen = !P.hostBuf && P.sf.compact && P.rp.genMask != 0ull && rd->integrator == DR_INTEGRATOR_PATH && P.coherentCamera && !sc->d.nquads && spp >= 64 &&
-              !dr_opt("DARTRAY_LAZY_GEN").isZero();
+  P.lazyGen = lazyGenFor(P);
   // a stage's any-hit launch beside its closest-hit launch, on a second stream (DARTRAY_OVERLAP_ANY=0: one after the other)
   P.overlapAny = !dr_opt("DARTRAY_OVERLAP_ANY").isZero() && !P.dlSpec;
   if (P.overlapAny && !sc->s3) HIP_TRY(hipStreamCreateWithFlags(&sc->s3, hipStreamNonBlocking));
@@ -1746,6 +1809,11 @@ int prepareRender(RenderPlan& P) {
   }
   HIP_TRY(sc->ws.pix.alloc(P.npixTotal));
   HIP_TRY(hipMemcpyAsync(sc->ws.pix.p, P.pixels.data(), P.npixTotal * sizeof(int2), hipMemcpyHostToDevice, P.s));
+  if (P.adaptivePass) {  // the list of flagged pixels: every pixel of the render at most
+    HIP_TRY(sc->ws.adaptList.alloc(P.npixTotal));
+    HIP_TRY(sc->ws.adaptCount.alloc(2));
+    HIP_TRY(hipMemsetAsync(sc->ws.adaptCount.p, 0, 2 * sizeof(uint32_t), P.s));
+  }
   HIP_TRY(hipMemcpyAsync(sc->ws.filterTable.p, rd->film.filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, P.s));
   HIP_TRY(hipStreamSynchronize(P.s));  // (the copies read host memory the caller and this plan own)
   return DR_OK;
@@ -2067,6 +2135,9 @@ int BatchRunner::finish() {
   }
   hipEvent_t evF = sc->getEvent();
   (void)hipEventRecord(evF, s);
+  // adaptive, first pass: the pixels that need maxSamples go to the list and leave this batch's film step (their entries of the
+  // render's pixel array, which no later batch reads, move outside every film window)
+  if (P.adaptivePass == 1) L.adaptive_decide(rp, st, np, w.pix.p + p0, w.adaptList.p, w.adaptCount.p, (uint32_t)P.npixTotal, s);
   L.film(rp, st, sc->ws.filterTable.p, np, P.film, s);
   timed(4, evF);
   sc->stats.batches++;
@@ -2270,6 +2341,7 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
     if (q == hipSuccess) sc->foldEvents();
     (void)hipGetLastError();  // hipErrorNotReady is not an error
   }
+  sc->adaptiveN = 0;
   sc->statsPending = true;
   hipEvent_t evStart = sc->getEvent(), evStop = sc->getEvent();
   sc->renderEvents.push_back({evStart, evStop});
@@ -2294,18 +2366,41 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
     rc = BatchRunner(P, sc->ws, sc->ws.pix.p + p0, p0, np, nullptr).run();
     if (rc) return rc;
   }
+  uint64_t cameraSamples = (uint64_t)P.npixTotal * P.spp, nBatches = P.nBatches;
+  bool lazy2 = false;
+  if (P.adaptivePass) {
+    // the one host round trip of the mode: how many pixels the first pass flagged (and how many of them the film holds)
+    uint32_t counts[2] = {0u, 0u};
+    HIP_TRY(hipMemcpyAsync(counts, sc->ws.adaptCount.p, sizeof(counts), hipMemcpyDeviceToHost, P.s));
+    HIP_TRY(hipStreamSynchronize(P.s));
+    const uint32_t nFlagged = (uint32_t)std::min<uint64_t>(counts[0], P.npixTotal);
+    sc->adaptiveN = nFlagged;
+    if (nFlagged) {
+      std::vector<int2>().swap(P.pixels);  // (uploaded; the second plan need not copy them)
+      RenderPlan Q = secondPass(P, nFlagged);
+      for (size_t p0 = 0; p0 < Q.npixTotal; p0 += Q.pixPerBatch) {
+        const uint32_t np = (uint32_t)std::min<size_t>(Q.pixPerBatch, Q.npixTotal - p0);
+        rc = BatchRunner(Q, sc->ws, sc->ws.adaptList.p + p0, p0, np, nullptr).run();
+        if (rc) return rc;
+      }
+      cameraSamples += (uint64_t)nFlagged * Q.spp;
+      P.filmSamples += (uint64_t)counts[1] * (uint64_t)(Q.spp - P.spp);  // (their first-pass samples were not added)
+      nBatches += Q.nBatches;
+      lazy2 = Q.lazyGen;
+    }
+  }
   HIP_TRY(hipEventRecord(evStop, P.s));
-  sc->stats.camera_samples += (uint64_t)P.npixTotal * P.spp;
+  sc->stats.camera_samples += cameraSamples;
   sc->stats.film_samples += P.filmSamples;
-  if ((uint64_t)P.npixTotal * P.spp >= (1ull << 25)) sc->bigRenders++;  // (planBatches: the next render of this scene may take the whole image as one batch)
+  if (cameraSamples >= (1ull << 25)) sc->bigRenders++;  // (planBatches: the next render of this scene may take the whole image as one batch)
   sc->lastInfo[0] = P.L == &kLayoutSp4 ? 4 : 64;
   sc->lastInfo[1] = P.L->trace_kernel_id(sc->d, 0);
   sc->lastInfo[2] = P.L->trace_kernel_id(sc->d, 1);
   sc->lastInfo[3] = -1;  // (reserved: rounds 4-5 reported the treelet-parked traversal's parking rounds here)
   sc->lastInfo[4] = pilot.setsRun;
-  sc->lastInfo[5] = (int32_t)std::min<uint64_t>(0x7fffffff, P.nBatches);
+  sc->lastInfo[5] = (int32_t)std::min<uint64_t>(0x7fffffff, nBatches);
   sc->lastInfo[6] = P.tgrid / std::max(1, g_numCU);
-  sc->lastInfo[7] = (P.overlapAny ? 1 : 0) | (P.coherentCamera && !sc->d.nquads ? 2 : 0) | (P.lazyGen ? 8 : 0);
+  sc->lastInfo[7] = (P.overlapAny ? 1 : 0) | (P.coherentCamera && !sc->d.nquads ? 2 : 0) | (P.lazyGen || lazy2 ? 8 : 0);
   return DR_OK;
 }
 
@@ -2323,6 +2418,17 @@ int dr_enumerate_pixels(const DrRenderDesc* rd, int32_t* out_xy, uint64_t cap, u
       out_xy[2 * i] = pixels[i].x;
       out_xy[2 * i + 1] = pixels[i].y;
     }
+  }
+  return DR_OK;
+}
+
+int dr_scene_get_adaptive_pixels(DrScene* sc, int32_t* out_xy, uint64_t cap, uint64_t* n_out) {
+  if (!sc || !n_out) return fail(DR_ERR_INVALID, "null argument");
+  *n_out = sc->adaptiveN;
+  if (out_xy && sc->adaptiveN) {
+    if (cap < sc->adaptiveN) return fail(DR_ERR_INVALID, "pixel buffer too small");
+    // (the render waited for the list's length before it started the second pass: the list is complete)
+    HIP_TRY(hipMemcpy(out_xy, sc->ws.adaptList.p, (size_t)sc->adaptiveN * sizeof(int2), hipMemcpyDeviceToHost));
   }
   return DR_OK;
 }

@@ -16,6 +16,10 @@ void launch_gen_samples(const RenderParams& rp, const BatchState& st, uint32_t n
 // dr_sampler_strat.hip: the stratified device sampler (xsamples x spp / xsamples strata; jitter: rp.samplerMode) and dr_generate_samples' dump
 void launch_gen_strat(const RenderParams& rp, const BatchState& st, uint32_t npix, int xsamples, hipStream_t s);
 void launch_export_samples(const RenderParams& rp, const BatchState& st, float* out, int stride, hipStream_t s);
+// dr_sampler_adaptive.hip: AdaptiveSampler.needsSupersampling for the npix pixels of a first-pass batch, in front of its film step --
+// flagged pixels are appended to list (counts[0]: its length, counts[1]: those inside the film window) and retired from pix
+void launch_adaptive_decide(const RenderParams& rp, const BatchState& st, uint32_t npix, int2* pix, int2* list, uint32_t* counts,
+                            uint32_t listCap, hipStream_t s);
 void launch_mark_alive(const uint32_t* list, const uint32_t* nList, uint32_t shift, uint8_t* alive, hipStream_t s);
 void launch_sum_alive(const uint8_t* alive, uint32_t nGroups, uint32_t npix, const uint32_t nb[3], TraceCounters* ctr, hipStream_t s);
 void launch_transpose_samples(const float* aos, int stride, const BatchState& st, int nFloats, hipStream_t s);

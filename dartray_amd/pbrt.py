@@ -554,6 +554,10 @@ class DartRay:
         self.opt["pixelSamplerParams"] = ps
 
     def sampler(self, name, ps):
+        # (refused here, at the directive, so that the message carries its file and line)
+        if name == "adaptive" and ps.findOneString("method", "contrast") == "shapeid":
+            raise UnsupportedFeature("Sampler \"adaptive\" method \"shapeid\": the camera hit's shape and primitive ids are not kept "
+                                     "per sample on the device; method \"contrast\" is on the path")
         self.opt["samplerName"], self.opt["samplerParams"] = name, ps
 
     def accelerator(self, name, ps):
@@ -910,8 +914,8 @@ class DartRay:
         o = self.opt
         if o["rendererName"] != "sampler":
             raise UnsupportedFeature(f"Renderer \"{o['rendererName']}\": only 'sampler' is on the path")
-        if o["samplerName"] not in ("lowdiscrepancy", "stratified"):
-            raise UnsupportedFeature(f"Sampler \"{o['samplerName']}\": only 'lowdiscrepancy' and 'stratified' are on the path")
+        if o["samplerName"] not in ("lowdiscrepancy", "stratified", "adaptive"):
+            raise UnsupportedFeature(f"Sampler \"{o['samplerName']}\": only 'lowdiscrepancy', 'stratified' and 'adaptive' are on the path")
         film = self._makeFilm()
         camera = self._makeCamera(film)
         pname, pps = o["pixelSamplerName"], o["pixelSamplerParams"]          # dartray.dart:980-996
@@ -933,6 +937,14 @@ class DartRay:
                 raise UnsupportedFeature(f"Sampler \"stratified\" with {xs} x {ys} samples: xsamples * ysamples must be a power of two, "
                                          "at most 4096 (the device's slot -> pixel maps are shifts)")
             sampler = core.StratifiedSampler(camera, xs, ys, sp.findOneBool("jitter", True), seed, pixels)
+        elif o["samplerName"] == "adaptive":                                 # AdaptiveSampler.Create, adaptive_sampler.dart:189-208
+            sp = o["samplerParams"]
+            mins, maxs = sp.findOneInt("minsamples", 4), sp.findOneInt("maxsamples", 32)
+            sp.findOneString("method", "contrast")  # an unknown metric falls back to 'contrast' (:200-203); 'shapeid' was refused at the directive
+            try:
+                sampler = core.AdaptiveSampler(camera, mins, maxs, "contrast", seed, pixels)
+            except ValueError as e:
+                raise UnsupportedFeature(f"Sampler \"adaptive\": {e}") from None
         else:
             nsamp = int(self.overrides.get("pixelsamples", o["samplerParams"].findOneInt("pixelsamples", 4)))
             sampler = core.LowDiscrepancySampler(camera, nsamp, seed, pixels)

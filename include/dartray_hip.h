@@ -230,6 +230,15 @@ typedef struct DrFilm {
  * LatinHypercube draws stay random. */
 #define DR_SAMPLER_STRATIFIED 2
 #define DR_SAMPLER_STRATIFIED_NOJITTER 3
+/* On-device AdaptiveSampler (adaptive_sampler.dart:101-187, method "contrast", FULL_SAMPLING) on the keyed streams of DR_SAMPLER_COUNTER;
+ * DESIGN.md section 2.8.  Pass 1 traces every pixel of the call's window exactly as DR_SAMPLER_COUNTER does at minSamples.  A pixel whose
+ * samples' luminances (after the renderer's NaN / negative / infinite guards) satisfy |lum_i - Lavg| / Lavg > 0.5 for some i (f64, Lavg summed
+ * in sample order; a black pixel never does) is traced again exactly as DR_SAMPLER_COUNTER does at maxSamples, and ONLY that second set reaches
+ * the film: film == counter render of the other pixels at minSamples + counter render of these at maxSamples.  maxSamples = DrRenderDesc.spp,
+ * minSamples = DrRenderDesc.strat_xsamples; both powers of two, 2 <= minSamples < maxSamples <= 4096 (the host applies the constructor's
+ * swapping / rounding / doubling, adaptive_sampler.dart:53-83): DR_ERR_INVALID otherwise.  Method "shapeid" does not exist here (the camera
+ * hit's ids are not kept per sample).  One host round trip per call (the number of flagged pixels); dr_scene_get_adaptive_pixels lists them. */
+#define DR_SAMPLER_ADAPTIVE 4
 
 /* Everything SamplerRenderer.render needs besides the Scene
  * (lib/renderers/sampler_renderer.dart:29-31,36-65). */
@@ -238,7 +247,7 @@ typedef struct DrRenderDesc {
   DrFilm film;
   int32_t integrator;
   int32_t max_depth; /* PathIntegrator.maxDepth / DirectLightingIntegrator.maxDepth (default 5) */
-  int32_t spp;       /* LowDiscrepancySampler.nPixelSamples or StratifiedSampler's xPixelSamples * yPixelSamples, power of two */
+  int32_t spp;       /* LowDiscrepancySampler.nPixelSamples, StratifiedSampler's xPixelSamples * yPixelSamples or AdaptiveSampler.maxSamples, power of two */
   int32_t sampler_mode;
   int64_t seed; /* DR_SAMPLER_COUNTER */
   /* Work split.  task_*: the reference's GetSubWindow rectangle of the sampler
@@ -247,7 +256,8 @@ typedef struct DrRenderDesc {
    * round-robin over ranks; tile_count <= 1 disables it. */
   int32_t task_num, task_count;
   int32_t tile_rank, tile_count, tile_size;
-  int32_t strat_xsamples; /* DR_SAMPLER_STRATIFIED(_NOJITTER): xPixelSamples; yPixelSamples = spp / strat_xsamples, exactly.  Else ignored */
+  int32_t strat_xsamples; /* DR_SAMPLER_STRATIFIED(_NOJITTER): xPixelSamples; yPixelSamples = spp / strat_xsamples, exactly.
+                           * DR_SAMPLER_ADAPTIVE: the field doubles as AdaptiveSampler.minSamples.  Else ignored */
   /* DR_SAMPLER_HOST_BUFFER: nsamples camera samples, in reference order
    * (pixel-major, all spp of a pixel adjacent). */
   int64_t nsamples;
@@ -417,6 +427,11 @@ int dr_enumerate_pixels(const DrRenderDesc* desc, int32_t* out_xy, uint64_t cap,
  * a pixel's position in the full sampler extent. */
 int dr_generate_samples(DrScene* scene, const DrRenderDesc* desc, const int32_t* pixel_xy, uint64_t npix, float* out, int32_t stride);
 
+/* Diagnostics and tests: the raster pixels the scene's LAST render call supersampled (DR_SAMPLER_ADAPTIVE: those traced at maxSamples;
+ * any other sampler: none), out_xy[n][2] in no particular order.  *n_out is always written; out_xy may be NULL to query the count,
+ * cap < n with out_xy set is DR_ERR_INVALID. */
+int dr_scene_get_adaptive_pixels(DrScene* scene, int32_t* out_xy, uint64_t cap, uint64_t* n_out);
+
 /* ImageFilm.writeImage on a device film: XYZ -> RGB, divide by weightSum. */
 int dr_film_resolve_device(const void* film_dev, int64_t npixels, void* rgb_dev, void* hip_stream);
 
@@ -466,8 +481,9 @@ const char* dr_version(void);
  * loaded with the DR_ABI_VERSION it was built against BEFORE it passes a struct: the structs carry no size field, so a host built against
  * an older header would hand the library a shorter object than it reads (version 5 -> 6: DrRenderDesc grew by tail_offsets, 1344 -> 1352
  * bytes; version 6 -> 7: DR_INTEGRATOR_DIRECT_ONE, dr_scene_workspace_bytes, the switch list of dr_set_option;
- * 8: DR_SAMPLER_STRATIFIED, strat_xsamples -- the former padding at offset 1292 -- and dr_generate_samples). */
-#define DR_ABI_VERSION 8
+ * 8: DR_SAMPLER_STRATIFIED, strat_xsamples -- the former padding at offset 1292 -- and dr_generate_samples;
+ * 9: DR_SAMPLER_ADAPTIVE -- minSamples travels in strat_xsamples, no layout change -- and dr_scene_get_adaptive_pixels). */
+#define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
 /* Tuning / diagnostic switches.  Every switch is also an environment variable of the same name (DARTRAY_<NAME>); a

@@ -30,7 +30,7 @@
  * TriangleMesh / Sphere / Disk shapes, matte / mirror / glass / plastic
  * materials with constant textures, DiffuseAreaLight / InfiniteAreaLight /
  * point, spot and distant lights, PathIntegrator and DirectLightingIntegrator
- * ("all"), the low-discrepancy and the stratified sampler, ImageFilm with any Filter, the three
+ * ("all"), the low-discrepancy, the stratified and the adaptive sampler, ImageFilm with any Filter, the three
  * cameras.  Anything else is reported through LogSevere (log.dart:42-47),
  * never approximated.
  ****************************************************************************/
@@ -150,7 +150,7 @@ const int OFF_DrRenderDesc_task_count = 1276;
 const int OFF_DrRenderDesc_tile_rank = 1280;
 const int OFF_DrRenderDesc_tile_count = 1284;
 const int OFF_DrRenderDesc_tile_size = 1288;
-const int OFF_DrRenderDesc_strat_xsamples = 1292;  // DR_SAMPLER_STRATIFIED(_NOJITTER): xPixelSamples
+const int OFF_DrRenderDesc_strat_xsamples = 1292;  // DR_SAMPLER_STRATIFIED(_NOJITTER): xPixelSamples; DR_SAMPLER_ADAPTIVE: minSamples
 const int OFF_DrRenderDesc_nsamples = 1296;
 const int OFF_DrRenderDesc_pixel_xy = 1304;
 const int OFF_DrRenderDesc_sample_vec = 1312;
@@ -171,6 +171,7 @@ const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DI
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
 const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
+const int DR_SAMPLER_ADAPTIVE = 4;             // AdaptiveSampler (contrast) on the LD sampler's keyed streams; spp = maxSamples
 
 typedef _InitC = Int32 Function(Int32);
 typedef _InitD = int Function(int);
@@ -200,6 +201,8 @@ typedef _KernelsC = Int32 Function(Pointer<Void>, Pointer<Uint32>);
 typedef _KernelsD = int Function(Pointer<Void>, Pointer<Uint32>);
 typedef _GetLayoutC = Int32 Function(Pointer<Void>, Pointer<Int32>, Pointer<Float>);
 typedef _GetLayoutD = int Function(Pointer<Void>, Pointer<Int32>, Pointer<Float>);
+typedef _AdaptivePixelsC = Int32 Function(Pointer<Void>, Pointer<Int32>, Uint64, Pointer<Uint64>);
+typedef _AdaptivePixelsD = int Function(Pointer<Void>, Pointer<Int32>, int, Pointer<Uint64>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -240,7 +243,7 @@ class HipSamplerRenderer extends Renderer {
   static final _InitD _init = _lib.lookupFunction<_InitC, _InitD>('dr_init');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
   /// library of another layout version is refused before any struct crosses the boundary.
-  static const int ABI_VERSION = 8;
+  static const int ABI_VERSION = 9;
   static DynamicLibrary _open() {
     DynamicLibrary l = DynamicLibrary.open('libdartray_hip.so');
     _CommVoidD abi = l.lookupFunction<_CommVoidC, _CommVoidD>('dr_abi_version');
@@ -267,6 +270,22 @@ class HipSamplerRenderer extends Renderer {
   static final _GetLayoutD _getStateLayout = _lib.lookupFunction<_GetLayoutC, _GetLayoutD>('dr_scene_get_state_layout');
   static final _KernelsD _getTraceKernels = _lib.lookupFunction<_KernelsC, _KernelsD>('dr_scene_get_trace_kernels');
   static final _KernelsD _setTraceKernels = _lib.lookupFunction<_KernelsC, _KernelsD>('dr_scene_set_trace_kernels');
+  static final _AdaptivePixelsD _getAdaptivePixels =
+      _lib.lookupFunction<_AdaptivePixelsC, _AdaptivePixelsD>('dr_scene_get_adaptive_pixels');
+
+  /// How many pixels the last render of this renderer traced a second time at the adaptive sampler's maximum count
+  /// (dr_scene_get_adaptive_pixels; 0 under every other sampler).
+  int lastSupersampledPixels = 0;
+
+  void _readSupersampled(Pointer<Void> scene) {
+    Pointer<Uint64> count = calloc<Uint64>(1);
+    try {
+      _check(_getAdaptivePixels(scene, nullptr, 0, count));
+      lastSupersampledPixels = count.value;
+    } finally {
+      calloc.free(count);
+    }
+  }
 
   /// What the library's pilot picked for a scene: [closest-hit kernel, any-hit kernel, state layout] (include/dartray_hip.h:
   /// dr_scene_get_trace_kernels / dr_scene_get_state_layout).  A render of a big scene measures them on its first batches; a host
@@ -777,7 +796,8 @@ class HipSamplerRenderer extends Renderer {
       // The sampler object decides the mode, and a stratified sampler's own public fields (samplers/stratified_sampler.dart:152-155)
       // are the one source of its strata.  (The class is told by its name: on the VM, where dart:ffi runs, runtimeType prints it.)
       final bool stratified = '${sampler.runtimeType}' == 'StratifiedSampler';
-      if (!stratified && sampler is! LowDiscrepancySampler) {
+      final bool adaptive = '${sampler.runtimeType}' == 'AdaptiveSampler';
+      if (!stratified && !adaptive && sampler is! LowDiscrepancySampler) {
         _unsupported('sampler ${sampler.runtimeType}');
       }
       // The device runs the same LD / stratified sampler with one keyed RNG stream per (pixel, LD block) / pixel / (pixel, sample)
@@ -791,6 +811,15 @@ class HipSamplerRenderer extends Renderer {
         rd.i32(OFF_DrRenderDesc_spp, xPixelSamples * yPixelSamples);
         rd.i32(OFF_DrRenderDesc_sampler_mode, jitterSamples ? DR_SAMPLER_STRATIFIED : DR_SAMPLER_STRATIFIED_NOJITTER);
         rd.i32(OFF_DrRenderDesc_strat_xsamples, xPixelSamples);
+      } else if (adaptive) {
+        // the sampler's own fields after its constructor's swapping / rounding / doubling (samplers/adaptive_sampler.dart:53-83,
+        // 213-214): powers of two with 2 <= minSamples < maxSamples.  The decision on the device is the contrast test (:170-183).
+        dynamic adapt = sampler;
+        int minSamples = adapt.minSamples;
+        int maxSamples = adapt.maxSamples;
+        rd.i32(OFF_DrRenderDesc_spp, maxSamples);
+        rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_ADAPTIVE);
+        rd.i32(OFF_DrRenderDesc_strat_xsamples, minSamples);  // (the field doubles as minSamples in this mode)
       } else {
         rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
         rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_COUNTER);
@@ -819,6 +848,7 @@ class HipSamplerRenderer extends Renderer {
         _check(_render(handle.value, rd.ptr, lxyzw, rgb));
       }
       _readPilotPicks(handle.value);
+      _readSupersampled(handle.value);
       OutputImage out = new OutputImage(film.left, film.top, film.width, film.height,
                                         film.xResolution, film.yResolution,
                                         new Float32List.fromList(rgb.asTypedList(3 * npix)));
