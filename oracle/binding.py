@@ -55,7 +55,7 @@ class OrcRenderDesc(C.Structure):
 class OrcRecord(C.Structure):
     _fields_ = [("capacity", C.c_int64), ("count", C.c_int64), ("nfloats", C.c_int32), ("max_tail", C.c_int32),
                 ("pixel_xy", C.c_void_p), ("sample_vec", C.c_void_p), ("nfloats_cap", C.c_int32),
-                ("tail", C.c_void_p), ("tail_count", C.c_void_p), ("Ls", C.c_void_p)]
+                ("tail", C.c_void_p), ("tail_count", C.c_void_p), ("Ls", C.c_void_p), ("Ls_raw", C.c_void_p)]
 
 
 class OrcCounters(C.Structure):
@@ -286,7 +286,7 @@ class OracleScene:
 
     def render(self, rd, record=0, max_tail=40, want_film=True):
         """SamplerRenderer.render.  Returns dict(rgb, film, and -- if record > 0 -- the per-sample
-        recording: pixel_xy, sample_vec, tail, tail_count, Ls)."""
+        recording: pixel_xy, sample_vec, tail, tail_count, Ls, Ls_raw)."""
         l = lib()
         # ImageFilm window
         import math
@@ -312,6 +312,8 @@ class OracleScene:
             rec.tail = out["tail"].ctypes.data
             rec.tail_count = out["tail_count"].ctypes.data
             rec.Ls = out["Ls"].ctypes.data
+            out["Ls_raw"] = np.zeros((record, 3), np.float32)  # before the NaN / negative / infinite guards
+            rec.Ls_raw = out["Ls_raw"].ctypes.data
         rc = l.orc_render(self.h, C.byref(rd), rgb.ctypes.data, film.ctypes.data if want_film else None,
                           C.byref(rec) if rec is not None else None)
         if rc != 0:
@@ -320,7 +322,7 @@ class OracleScene:
         if rec is not None:
             n = rec.count
             out["count"] = n
-            for k in ("pixel_xy", "sample_vec", "tail", "tail_count", "Ls"):
+            for k in ("pixel_xy", "sample_vec", "tail", "tail_count", "Ls", "Ls_raw"):
                 out[k] = out[k][:n]
         return out
 

@@ -2516,6 +2516,7 @@ struct OrcRecord {  // optional per-sample recording (all host arrays sized by t
   double* tail;           // [capacity*max_tail]
   int32_t* tail_count;    // [capacity]
   float* Ls;              // [capacity*3] radiance after the NaN/neg/inf guards
+  float* Ls_raw;          // [capacity*3] or null: the same before the guards (what Li returned times rayWeight)
 };
 struct OrcCounters {
   uint64_t closest_rays, any_rays, closest_nodes, any_nodes, closest_tris, any_tris, light_tris, camera_samples;
@@ -2845,7 +2846,7 @@ int orc_sample_floats(void* h, int integrator, int max_depth) {
 // SamplerRenderer.Li for one camera sample (sampler_renderer.dart:67-98 + :165-193).
 static S li_one(const Scene& sc, const IntegratorCfg& cfg, const Camera& cam, const std::vector<int>& n1D,
                 const std::vector<int>& n2D, int px, int py, const float* sv, LiRng& rng, D shutterOpen,
-                D shutterClose, D* imageX, D* imageY) {
+                D shutterClose, D* imageX, D* imageY, S* rawLs = nullptr) {
   t_ctr.camera_samples++;
   *imageX = (D)px + (D)sv[0];   // montecarlo.dart:451-452
   *imageY = (D)py + (D)sv[1];
@@ -2867,6 +2868,7 @@ static S li_one(const Scene& sc, const IntegratorCfg& cfg, const Camera& cam, co
   }
   // T * Li + Lvi with T = 1, Lvi = 0 (emission_integrator.dart:39-42), then * rayWeight.
   S Ls = smulD(sadd(smul(S{1, 1, 1}, Li), S{0, 0, 0}), rayWeight);
+  if (rawLs) *rawLs = Ls;
   if (snan(Ls)) Ls = S{0, 0, 0};                       // sampler_renderer.dart:181-193
   else if (slum(Ls) < -1e-5) Ls = S{0, 0, 0};
   else if (std::isinf(slum(Ls))) Ls = S{0, 0, 0};
@@ -2996,7 +2998,8 @@ int orc_render(void* h, const OrcRenderDesc* rd, float* out_rgb, float* out_film
       tailRec.clear();
       if (rec) lr.record = &tailRec;
       const float* sv = &samples[(size_t)i * nFloats];
-      Ls[i] = li_one(*sc, cfg, cam, n1D, n2D, px, py, sv, lr, rd->shutter_open, rd->shutter_close, &ix[i], &iy[i]);
+      S raw;
+      Ls[i] = li_one(*sc, cfg, cam, n1D, n2D, px, py, sv, lr, rd->shutter_open, rd->shutter_close, &ix[i], &iy[i], &raw);
       if (rec && rec->count < rec->capacity) {
         int64_t k = rec->count++;
         if (rec->pixel_xy) { rec->pixel_xy[2 * k] = px; rec->pixel_xy[2 * k + 1] = py; }
@@ -3005,6 +3008,7 @@ int orc_render(void* h, const OrcRenderDesc* rd, float* out_rgb, float* out_film
         if (rec->tail) for (int t = 0; t < nt; ++t) rec->tail[k * rec->max_tail + t] = tailRec[t];
         if (rec->tail_count) rec->tail_count[k] = (int)tailRec.size();
         if (rec->Ls) { rec->Ls[3 * k] = (float)Ls[i].r; rec->Ls[3 * k + 1] = (float)Ls[i].g; rec->Ls[3 * k + 2] = (float)Ls[i].b; }
+        if (rec->Ls_raw) { rec->Ls_raw[3 * k] = (float)raw.r; rec->Ls_raw[3 * k + 1] = (float)raw.g; rec->Ls_raw[3 * k + 2] = (float)raw.b; }
       }
     }
     for (int i = 0; i < spp; ++i) film.addSample(ix[i], iy[i], Ls[i]);  // sampler_renderer.dart:199-203
