@@ -1,0 +1,311 @@
+// dr_host.h -- what the host units of the library share (internal; not part of the C ABI):
+//   dr_api.hip          options, the render planner (RenderPlan: planRender, planBatches, prepareRender), the entry points
+//   dr_scene_build.hip  dr_scene_create / dr_scene_destroy (SceneBuilder)
+//   dr_batch.hip        one batch through the stage loop (BatchRunner), the batch loop, the pilot
+// Whatever has external linkage here lives in namespace dr_host (each unit says `using namespace dr_host;`); what a single unit uses
+// stays in that unit's anonymous namespace.
+#ifndef DR_HOST_H
+#define DR_HOST_H
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "dr_kernels.h"
+
+namespace dr_host {
+
+extern int g_device;  // dr_init's device (-1 before it)
+
+int fail(int code, const std::string& msg);  // dr_api.hip: sets dr_last_error(), returns code
+#define HIP_TRY(expr)                                                                              \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ != hipSuccess)                                                                          \
+      return fail(DR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                  \
+  } while (0)
+
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  hipError_t alloc(size_t count) {
+    if (count <= n && p) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e == hipSuccess) n = count;
+    return e;
+  }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+  }
+  size_t bytes() const { return p ? std::max<size_t>(n, 1) * sizeof(T) : 0; }
+  ~DevBuf() { release(); }
+};
+
+struct Workspace {
+  uint32_t cap = 0;
+  int stateWords = 0;  // words per slot the tiles were sized for
+  int svWords = 0, maxTail = 0;  // svWords: 4-byte words of the sample region of one tile
+  uint32_t pixCap = 0;
+  DevBuf<float> tiles;  // the tiled path state (see BatchState in dr_kernels.h): cap/64 tiles of 64*41+svWords words
+  DevBuf<uint32_t> scr;  // compact samples: scramble words [2 * nBlocks][pixCap]
+  DevBuf<uint2> genState;  //   and the streams' generator states behind their burn-in draws [nBlocks][pixCap] (k_gen_burnin)
+  DevBuf<double> tail;
+  DevBuf<unsigned long long> tailOff;  // packed tail (DrRenderDesc.tail_offsets): the batch's nslots + 1 offsets
+  DevBuf<uint32_t> activeA, activeB, closestQ, anyQ, counters, spill;
+  DevBuf<uint32_t> envQ;  // plain-triangle scenes under an environment map: k_env's list of a stage (cap entries)
+  DevBuf<uint8_t> alive;  // lazy sample generation: [3][groups of 64 batch pixels] = a path of the group is alive at bounce 0 / 1 / 2
+  size_t spillHalf = 0;
+  DevBuf<uint32_t> roundA, roundB;  // DirectLighting over mirror / glass: the slots whose child ray is traced next round
+  DevBuf<float> specFrames;         //   [maxDepth][cap] SpecFrame
+  DevBuf<int32_t> specSp;           //   [cap]
+  DevBuf<int2> pix;
+  DevBuf<int2> adaptList;       // DR_SAMPLER_ADAPTIVE: the raster pixels the first pass flagged (k_adaptive_decide), the second pass's pixel array
+  DevBuf<uint32_t> adaptCount;  //   [0] their number, [1] those inside the film window
+  DevBuf<float> filterTable, aosSamples;
+  int spillGrid = 0;
+};
+
+// Where things live in Workspace::counters -- the only place that knows:
+//   [0, 4 * stagePitch): a stage's four queue counts (active out, closest, any, shade work), one row per kind, stagePitch words
+//                        apart: every wave adds to all four in one round trip (stage_flush), and same-line atomics serialise;
+//   the round words:     DirectLighting over mirror / glass, the counts of the two round lists and of k_shade_spec's two unused queues;
+//   [workBase, envBase): 8 per-XCD work counters per trace launch, DR_WORK_STRIDE words apart;
+//   [envBase, total):    the counts of k_env's lists, one cache line per stage.
+struct CounterLayout {
+  struct Range { uint32_t offset, length; };
+  static constexpr uint32_t stagePitch = 248;
+  static constexpr uint32_t stageCount(int j, int stage) { return stagePitch * (uint32_t)j + (uint32_t)stage; }
+  static constexpr uint32_t roundBase = 1008;
+  static constexpr uint32_t roundNext(int round) { return roundBase + (uint32_t)(round & 1); }
+  static constexpr uint32_t roundClosest = roundBase + 2, roundAny = roundBase + 3, roundEnd = roundBase + 4;
+  static constexpr uint32_t workBase = 1024, workPitch = 8 * DR_WORK_STRIDE, maxLaunches = 400;
+  static constexpr uint32_t workCounters(int launch) { return workBase + workPitch * (uint32_t)launch; }
+  static constexpr uint32_t envBase = workBase + workPitch * maxLaunches, envPitch = 64, maxEnvStages = 256;
+  static constexpr uint32_t envCount(int stage) { return envBase + envPitch * (uint32_t)stage; }
+  static constexpr uint32_t total = envBase + envPitch * maxEnvStages;
+  // A new round of the stage loop clears these.  Not the round words: the previous round's counts are still being read.
+  static constexpr Range roundReset[2] = {{0, 1000}, {workBase, total - workBase}};
+  // stages of a render at most: a row of stage counts each, and 1 + 2 * nStages trace launches
+  static constexpr int maxStages() { return (int)std::min(stagePitch, (maxLaunches - 1) / 2); }
+};
+static_assert(CounterLayout::stageCount(3, 0) + CounterLayout::stagePitch <= CounterLayout::roundReset[0].offset + CounterLayout::roundReset[0].length,
+              "the four stage rows lie inside the first reset range");
+static_assert(CounterLayout::roundReset[0].offset + CounterLayout::roundReset[0].length <= CounterLayout::roundNext(0), "a new round keeps the round words");
+static_assert(CounterLayout::roundEnd <= CounterLayout::workBase && CounterLayout::roundReset[1].offset == CounterLayout::workBase, "round words below the work counters");
+static_assert(CounterLayout::workCounters(CounterLayout::maxLaunches) == CounterLayout::envBase, "work counters end where k_env's counts begin");
+static_assert(CounterLayout::envCount(CounterLayout::maxEnvStages) == CounterLayout::total &&
+                  CounterLayout::roundReset[1].offset + CounterLayout::roundReset[1].length == CounterLayout::total, "k_env's counts end the buffer");
+static_assert(CounterLayout::maxStages() <= (int)CounterLayout::maxEnvStages, "every stage has a k_env count");
+
+// What a timed pair of events measured (DrScene::TraceEv, folded into DrRenderStats by DrScene::foldEvents).
+enum class TimedKind : int {
+  Closest = 0,         // a closest-hit traversal launch
+  Any = 1,             // an any-hit traversal launch
+  Shade = 2,
+  Gen = 3,             // sample generation + raygen
+  Film = 4,
+  Pilot = 5,           // the calibration batches as a whole (DrRenderStats.pilot_ms)
+  CoherentCamera = 6,  // k_trace_pk: part of the closest-hit time, and the pk* figures
+};
+
+}  // namespace dr_host
+
+struct DrScene {
+  template <class T>
+  using DevBuf = dr_host::DevBuf<T>;
+  using Workspace = dr_host::Workspace;
+  using TimedKind = dr_host::TimedKind;
+  DScene d;
+  DevBuf<uint4> nodes, pairs;
+  DevBuf<float4> tris, mats, shtris;
+  DevBuf<DLight> lights;
+  DevBuf<DLightTri> ltris;
+  DevBuf<DQuadric> quads;
+  std::vector<DQuadric> hostQuads;
+  DevBuf<float4> srec;
+  DevBuf<float> xforms;
+  DevBuf<float> lcdf;
+  DevBuf<float> envTexels, envCondFunc, envCondCdf, envCondInt, envMargFunc, envMargCdf;
+  DevBuf<uint16_t> envCondGuide;
+  DevBuf<TraceCounters> ctr;
+  uint32_t bvhDepth = 0;
+  bool traceCalibrated = false;
+  uint32_t bigRenders = 0;      // big renders this scene has finished (planBatches: the first one keeps its batches at 2^27 slots)
+  int stateLayout = 0;          // path-state layout of this scene's path renders: 0 = not measured yet, 64 / 4 (LayoutOps)
+  float layoutDensity = -1.f;   //   what decided it: the share of a pilot batch's slots still alive at the second bounce
+  float calibMs[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  // pilot of dr_render_device: [closest / any][v2 / v3 / v3c] ms
+  float calibFarFirst = 0.f;  // any-hit rays, far child first over the reference order: time per ray of k_trace<1> in the pilot's first two batches (0 = not measured)
+  float calibPerGB[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};  //   the same as ms per algorithmic GB (what the choice compares; 0 = not measured)
+  // what the last dr_render_device call actually ran with (dr_scene_last_render_info): state layout, the traversal kernels of
+  // its last batch, a reserved word (-1), calibration batches, workgroups per CU
+  int32_t lastInfo[8] = {0, 0, 0, -1, 0, 0, 0, 0};
+  uint32_t adaptiveN = 0;  // dr_scene_get_adaptive_pixels: entries of ws.adaptList the last render left (0 after any other sampler's render)
+  std::vector<int32_t> lightNSamples;
+  bool hasSpecular = false;  // some material is a mirror / glass
+  bool hasDeltaLight = false;
+  // DirectLighting sample layout (direct_lighting_integrator.dart:70-87), fixed by the lights' nsamples
+  DevBuf<LdBlock> dlBlocks;
+  DevBuf<DirectStage> dlStages;
+  int dlNBlocks = 0, dlNStages = 0, dlNFloats = 0, dlN1D = 0;
+  bool dlMulti = false;
+  Workspace ws;
+  hipStream_t s3 = nullptr;  // the any-hit launches of a stage, beside the closest-hit ones
+  // stats of the last render
+  DrRenderStats stats;
+  // after: set for an any-hit launch that ran beside the stage's closest-hit launch (its end): only the time AFTER that
+  // counts as any-hit time
+  struct TraceEv { hipEvent_t e0, e1; TimedKind kind; hipEvent_t after = nullptr; };
+  std::vector<TraceEv> traceEvents;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> renderEvents;
+  std::vector<hipEvent_t> eventPool;
+  size_t eventsUsed = 0;
+  bool statsPending = false;
+  hipEvent_t lastEvent = nullptr;
+  // dr_scene_get_coherent_stats: what k_trace_pk traced of the closest-hit totals since the last dr_reset_stats
+  double pkMs = 0.0;
+  uint64_t pkLaunches = 0;
+  unsigned long long pkRays = 0, pkNodes = 0, pkTris = 0;
+  // dr_scene_get_sampler_stats: (pixel, LD block) pairs the device sampler shuffled / that the path's reads name (rp.genMask), since the
+  // last dr_reset_stats (lazy generation: the first is smaller where paths end early -- sky pixels)
+  unsigned long long genDone = 0, genDoneHost = 0, genNamed = 0;
+  // Timings of finished launches are folded into `stats` and their events recycled, so a long-lived scene (a frame
+  // loop calling dr_render_device) does not grow the pool or the lists without bound.
+  void foldEvents() {
+    for (auto& ev : traceEvents) {
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, ev.after ? ev.after : ev.e0, ev.e1) != hipSuccess) continue;
+      if (t < 0.f) t = 0.f;  // (an any-hit launch that ended before the closest-hit one beside it)
+      switch (ev.kind) {  // (no default: -Wall names a kind this forgets)
+        case TimedKind::Any: stats.any_ms += t; stats.any_launches++; break;
+        case TimedKind::Closest: stats.closest_ms += t; stats.closest_launches++; break;
+        case TimedKind::CoherentCamera: stats.closest_ms += t; stats.closest_launches++; pkMs += t; pkLaunches++; break;  // k_trace_pk: part of the closest-hit time
+        case TimedKind::Shade: stats.shade_ms += t; break;
+        case TimedKind::Gen: stats.gen_ms += t; break;
+        case TimedKind::Pilot: stats.pilot_ms += t; break;
+        case TimedKind::Film: stats.film_ms += t; break;
+      }
+    }
+    for (auto& ev : renderEvents) {
+      float t = 0.f;
+      if (hipEventElapsedTime(&t, ev.first, ev.second) == hipSuccess) stats.total_ms += t;
+    }
+    stats.trace_ms = stats.closest_ms + stats.any_ms;
+    stats.trace_launches = stats.closest_launches + stats.any_launches;
+    traceEvents.clear();
+    renderEvents.clear();
+    eventsUsed = 0;
+  }
+  hipEvent_t getEvent() {
+    if (eventsUsed == eventPool.size()) {
+      hipEvent_t e;
+      (void)hipEventCreate(&e);
+      eventPool.push_back(e);
+    }
+    return eventPool[eventsUsed++];
+  }
+  ~DrScene() {
+    (void)hipDeviceSynchronize();  // nothing of this scene may still be in flight when its buffers and events go away
+    for (auto e : eventPool) (void)hipEventDestroy(e);
+    if (s3) (void)hipStreamDestroy(s3);
+  }
+};
+
+namespace dr_host {
+
+// How the sample vectors of one render are stored (see BatchState)
+struct SampleForm {
+  bool compact;
+  int nFloats, nBlocks, idxShift;
+  int svWords() const { return compact ? ((nBlocks * 64) << idxShift) / 4 : 64 * nFloats; }
+};
+
+// The kernels that read or write the path state exist twice: the default layout (every field of a tile's 64 slots one
+// 256-byte run) and sp4 (sub-tiles of four slots: a slot's 41 words within 656 contiguous bytes; the same sources compiled
+// with -DDR_SUB=4 -DDR_NS=sp4).  Dense stage lists are faster in the first; lists that thin out early -- open scenes under an
+// environment map, where most bounce rays leave -- in the second (C5: shade 711 -> 536 ms, MEASUREMENTS.md round 3).
+// A render picks one (dr_render_device); results do not depend on it.
+struct LayoutOps {
+  decltype(&launch_trace) trace;
+  decltype(&launch_trace_coherent) trace_coherent;
+  decltype(&trace_kernel_id) trace_kernel_id;
+  decltype(&launch_gen_samples) gen_samples;
+  decltype(&launch_gen_strat) gen_strat;
+  decltype(&launch_export_samples) export_samples;
+  decltype(&launch_adaptive_decide) adaptive_decide;
+  decltype(&launch_mark_alive) mark_alive;
+  decltype(&launch_sum_alive) sum_alive;
+  decltype(&launch_transpose_samples) transpose_samples;
+  decltype(&launch_raygen) raygen;
+  decltype(&launch_shade_path) shade_path;
+  decltype(&launch_env) env;
+  decltype(&launch_shade_direct) shade_direct;
+  decltype(&launch_shade_spec) shade_spec;
+  decltype(&launch_film) film;
+  int stateWords;  // 4-byte words of fixed path state per slot in this layout (a tile is 64 of them + the sample region):
+                   // what the kernels' own translation unit was compiled with (layout_state_words), not a constant repeated here
+};
+extern const LayoutOps kLayout64, kLayoutSp4;  // dr_api.hip
+
+struct RenderPlan {
+  DrScene* sc = nullptr;
+  const DrRenderDesc* rd = nullptr;
+  float* film = nullptr;
+  hipStream_t s = nullptr;
+  RenderParams rp;
+  SampleForm sf;
+  const LayoutOps* L = nullptr;  // state layout of the NEXT batch (the layout pilot decides it after the first calibration batch)
+  int spp = 0;
+  bool direct = false, dlSpec = false, envStage = false, hostBuf = false, packedTail = false;
+  bool strat = false;     // DR_SAMPLER_STRATIFIED(_NOJITTER): the device sampler writes the float sample form
+  int stratX = 0;         //   xPixelSamples (yPixelSamples = spp / stratX)
+  // the device sampler's launches for one batch (BatchRunner::loadSamples, dr_generate_samples)
+  void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
+  // DR_SAMPLER_ADAPTIVE: two counter-mode passes.  This plan is the first (every pixel at adMin samples: spp,
+  // rp and sf are that pass's; its batches end with k_adaptive_decide); secondPass() derives the plan of the flagged pixels at adMax.
+  int adaptivePass = 0;   // 0: another sampler; 1 / 2: which pass of an adaptive render this plan runs
+  int adMin = 0, adMax = 0;
+  uint32_t adPixCap = 0;  // pixels of a second-pass batch at most (planBatches: against the workspace both passes share)
+  // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'
+  uint32_t wsCap = 0, wsPix = 0;
+  SampleForm wsSf;
+  int needTail = 0;       // RNG draws a path can make beyond the sample vector (host-buffer mode: the recorded tail)
+  bool layoutKnown = false;
+  int maxStateWords = 0;  // words per slot the workspace is sized for (both layouts while the layout is not known)
+  bool coherentCamera = false, lazyGen = false, overlapAny = false;
+  bool calibrateTrace = false, measureLayout = false;
+  int pilotSets = 0;      // calibration batches: warm-up, k_trace timed, k_trace3 timed, k_trace3c timed; the layout alone: one
+  size_t calibPix = 0;    // pixels per calibration batch: the first pilotSets * calibPix entries of `pixels`
+  std::vector<int2> pixels;
+  size_t npixTotal = 0;
+  uint64_t filmSamples = 0;
+  uint32_t pixPerBatch = 0, cap = 0;
+  uint64_t nBatches = 0;
+  int tgrid = 0, sgrid = 0, nStages = 0;
+  bool calibrate() const { return calibrateTrace || measureLayout; }
+};
+
+// The calibration batches of a scene's first big render (prepareRender decided that there are some): part of the render -- nothing is
+// traced twice -- and the measurement that picks the state layout and, per ray kind, the traversal kernel.
+struct PilotResult {
+  int setsRun = 0;
+  double perByte[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};  // [closest / any][k_trace / k_trace3 / k_trace3c]: ms per algorithmic GB
+  float ms[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+  // any-hit rays of the first two batches, both through k_trace<1>: batch 0 far child first, batch 1 in the reference order
+  double anyMsPerRayFar = 0.0, anyMsPerRayRef = 0.0;
+};
+
+// ---- what the units call across files ----
+BatchState makeState(Workspace& w, const SampleForm& sf, const int2* pix, uint32_t nslots, bool useTail, int stateWords);  // dr_api.hip
+int runBatches(RenderPlan& plan, const int2* pixDev, size_t firstPixel);                                                    // dr_batch.hip
+int runPilot(RenderPlan& P, PilotResult& R);                                                                                // dr_batch.hip
+
+}  // namespace dr_host
+
+#endif

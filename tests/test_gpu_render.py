@@ -409,7 +409,7 @@ def test_traversal_pilot_leaves_results_and_counters_untouched():
 
 
 def test_both_state_layouts_render_the_same_film():
-    """The kernels that touch the path state are built twice (LayoutOps, dr_api.hip): 64-slot runs, and sub-tiles of four slots
+    """The kernels that touch the path state are built twice (LayoutOps, dr_host.h; the two tables: dr_api.hip): 64-slot runs, and sub-tiles of four slots
     (namespace sp4, picked by itself for plain-triangle scenes under an environment map).  DARTRAY_STATE_LAYOUT forces one: a
     closed scene, an open scene under a map, DirectLighting and a host-buffer replay give the same films either way."""
     import subprocess
