@@ -19,6 +19,7 @@ DR_SAMPLER_COUNTER = 1
 DR_SAMPLER_STRATIFIED = 2
 DR_SAMPLER_STRATIFIED_NOJITTER = 3
 DR_SAMPLER_ADAPTIVE = 4  # spp = maxSamples, strat_xsamples = minSamples
+DR_SAMPLER_HALTON = 5  # spp = pixelsamples, any integer >= 1
 DR_LIGHT_DIFFUSE_AREA = 0
 DR_LIGHT_INFINITE = 1
 DR_LIGHT_POINT = 2
@@ -163,6 +164,8 @@ EXPORTS = {
     "dr_enumerate_pixels": (C.c_int, [C.POINTER(DrRenderDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dr_scene_get_adaptive_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dr_generate_samples": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32]),
+    "dr_generate_halton_samples": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_int32, C.POINTER(C.c_uint64)]),
     "dr_get_stats": (C.c_int, [C.c_void_p, C.POINTER(DrRenderStats)]),
     "dr_reset_stats": (C.c_int, [C.c_void_p]),
     "dr_copy_bandwidth": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_double)]),

@@ -1315,6 +1315,113 @@ class AdaptiveSampler:
         return self.maxSamples
 
 
+def RadicalInverse(n, base):  # montecarlo.dart:327-339, as written: the next n is the truncated PRODUCT n * (1 / base)
+    val = 0.0
+    invBase = 1.0 / base
+    invBi = invBase
+    while n > 0:
+        d_i = n % base
+        val += d_i * invBi
+        n = int(n * invBase)
+        invBi *= invBase
+    return val
+
+
+def Lerp(t, v1, v2):  # common.dart:80-81
+    return v1 * (1.0 - t) + v2 * t
+
+
+class HaltonSampler:
+    """samplers/halton_sampler.dart:31-104: ONE sequence per task over the task's window -- sample k lands where RadicalInverse(k, 3) /
+    RadicalInverse(k, 2) put it in the delta x delta square over the window's corner (delta = max(width, height)) and is rejected when it
+    falls outside the window, so pixels receive different numbers of samples; pixelsamples is any positive integer.  On the device
+    (DR_SAMPLER_HALTON) the LatinHypercube draws of the integrator's slots and the draws inside Li come from streams keyed by
+    k; serial_samples() walks the reference's ONE serial RNG(taskNum) instead and returns the vectors as a HostBufferSampler."""
+
+    def __init__(self, camera, pixelsamples=4, seed=5489):
+        self.camera = camera
+        self.samplesPerPixel = int(pixelsamples)
+        if self.samplesPerPixel < 1:
+            raise ValueError("HaltonSampler: pixelsamples must be positive")
+        self.seed = int(seed)
+
+    def roundSize(self, size):  # :102-104
+        return size
+
+    def maximumSampleCount(self):  # :50-52
+        return 1
+
+    slot_counts = StratifiedSampler.slot_counts
+
+    @staticmethod
+    def window(renderer):
+        """(left, top, width, height) of the renderer's task: GetSubWindow's extents of the sampler extent, as the reference hands them on."""
+        e = renderer.camera.film.getSampleExtent()
+        x0, x1, y0, y1 = GetSubWindow(e[1] - e[0], e[3] - e[2], renderer.taskNum, max(1, renderer.taskCount))
+        return x0, y0, x1 - x0, y1 - y0
+
+    def accepted(self, left, top, width, height):
+        """The rejection loop (:63-83): yields (k, imageX, imageY) of every index of [0, pixelsamples * delta^2) inside the window."""
+        if width <= 0 or height <= 0:
+            return
+        delta = max(width, height)
+        right, bottom = left + width - 1, top + height - 1  # inclusive (sampler.dart:52-54)
+        for k in range(self.samplesPerPixel * delta * delta):
+            imageX = Lerp(RadicalInverse(k, 3), left, left + float(delta))
+            imageY = Lerp(RadicalInverse(k, 2), top, top + float(delta))
+            if imageX > right or imageY > bottom:
+                continue
+            yield k, imageX, imageY
+
+    def sample_vector(self, k, imageX, imageY, n1D, n2D, rng):
+        """(anchor pixel, vector) of the accepted index k in the C ABI's field order: the image sample as the f32 fraction behind
+        floor(imageX / imageY), lens and time the radical inverses of k + 1 (the reference increments currentSample first, :76-89; time raw:
+        the Lerp over the shutter is the consumer's), then LatinHypercube(oneD...), LatinHypercube(twoD...) drawn from rng (:91-97)."""
+        f32 = np.float32
+        px, py = math.floor(imageX), math.floor(imageY)
+        vec = np.zeros(5 + sum(n1D) + 2 * sum(n2D), f32)
+        vec[0:5] = (imageX - px, imageY - py, RadicalInverse(k + 1, 5), RadicalInverse(k + 1, 7), RadicalInverse(k + 1, 11))
+        o = 5
+        for n, dims in [(n, 1) for n in n1D] + [(n, 2) for n in n2D]:  # LatinHypercube, montecarlo.dart:305-325
+            v = np.zeros((n, dims), f32)
+            for j in range(n):
+                for d in range(dims):
+                    v[j, d] = min((j + rng.randomFloat()) * (1.0 / n), ONE_MINUS_EPSILON)
+            for d in range(dims):
+                for j in range(n):
+                    other = j + rng.randomUint() % (n - j)
+                    v[j, d], v[other, d] = v[other, d], v[j, d]
+            vec[o:o + n * dims] = v.reshape(-1)
+            o += n * dims
+        return (px, py), vec
+
+    def serial_samples(self, renderer, scene, li_draws=None):
+        """The reference's own stream: ONE RNG(taskNum) (sampler_renderer.dart:137) through the accepted samples' LatinHypercube draws and
+        through Li, in index order.  Returns a HostBufferSampler at one sample per pixel_xy row (samples are not grouped by pixel).
+        li_draws(px, py, vector, rng): as for StratifiedSampler.serial_samples."""
+        integ = renderer.surfaceIntegrator
+        needs_tail = integ.kind == _abi.DR_INTEGRATOR_PATH and integ.maxDepth >= 3
+        if needs_tail and li_draws is None:
+            raise ValueError("serial_samples: a PathIntegrator with maxDepth >= 3 draws inside Li; pass li_draws")
+        n1D, n2D = self.slot_counts(renderer, scene)
+        rng = DartRandom(renderer.taskNum)
+        pixels, vecs, tails = [], [], []
+        for k, imageX, imageY in self.accepted(*self.window(renderer)):
+            xy, v = self.sample_vector(k, imageX, imageY, n1D, n2D, rng)
+            pixels.append(xy)
+            vecs.append(v)
+            if needs_tail:
+                tails.append(list(li_draws(xy[0], xy[1], v, rng)))
+        tail = cnt = None
+        if needs_tail:
+            cnt = np.array([len(t) for t in tails], np.int32)
+            tail = np.zeros((len(tails), max(1, int(cnt.max()) if len(cnt) else 1)), np.float64)
+            for i, t in enumerate(tails):
+                tail[i, :len(t)] = t
+        nf = 5 + sum(n1D) + 2 * sum(n2D)
+        return HostBufferSampler(self.camera, 1, np.array(pixels, np.int32).reshape(-1, 2), np.array(vecs, np.float32).reshape(-1, nf), tail, cnt)
+
+
 class HostBufferSampler:
     """Explicit camera samples: pixel_xy [npix,2] int32, sample_vec [npix*spp, nfloats] f32
     (imageU, imageV, lensU, lensV, time, oneD..., twoD...), tail [npix*spp, max_tail] f64 =
@@ -1434,6 +1541,9 @@ class SamplerRenderer:
             d.spp = self.sampler.maxSamples
             d.strat_xsamples = self.sampler.minSamples  # (the field doubles as minSamples in this mode)
             d.seed = self.sampler.seed
+        elif isinstance(self.sampler, HaltonSampler):
+            d.sampler_mode = _abi.DR_SAMPLER_HALTON  # (spp = pixelsamples as given: nothing is rounded)
+            d.seed = self.sampler.seed
         else:
             d.sampler_mode = _abi.DR_SAMPLER_COUNTER
             d.seed = self.sampler.seed
@@ -1450,6 +1560,22 @@ class SamplerRenderer:
         out = np.zeros((len(pixels) * spp, nf), dtype=np.float32)
         _abi.check(_abi.lib().dr_generate_samples(dev.handle, C.byref(d), pixels.ctypes.data, len(pixels), out.ctypes.data, nf))
         return out
+
+    def generate_halton_samples(self, scene, first=0, count=None):
+        """dr_generate_halton_samples: the device sampler's accepted samples among the indices [first, first + count) of this task's
+        sequence (count None: to its end) -> (k [n] uint64, pixel_xy [n, 2] int32, vectors [n, nFloats] f32), in increasing k."""
+        d, keep = self.describe()
+        dev = scene._device()
+        if count is None:
+            _, _, w, h = HaltonSampler.window(self)
+            count = (d.spp * max(w, h) ** 2 if w > 0 and h > 0 else 0) - first
+        nf = _abi.lib().dr_scene_sample_floats(dev.handle, d.integrator)
+        k = np.zeros(max(1, count), np.uint64)
+        xy = np.zeros((max(1, count), 2), np.int32)
+        out = np.zeros((max(1, count), nf), np.float32)
+        n = C.c_uint64(0)
+        _abi.check(_abi.lib().dr_generate_halton_samples(dev.handle, C.byref(d), first, count, k.ctypes.data, xy.ctypes.data, out.ctypes.data, nf, C.byref(n)))
+        return k[:n.value].copy(), xy[:n.value].copy(), out[:n.value].copy()
 
     def render(self, scene):
         film = self.camera.film
@@ -1532,6 +1658,7 @@ def RegisterStandardPlugins():
     Plugin.register("sampler", "lowdiscrepancy", LowDiscrepancySampler)
     Plugin.register("sampler", "stratified", StratifiedSampler)
     Plugin.register("sampler", "adaptive", AdaptiveSampler)
+    Plugin.register("sampler", "halton", HaltonSampler)
     Plugin.register("film", "image", ImageFilm)
     Plugin.register("pixelSampler", "linear", lambda ps=None: LinearPixelSampler())
     Plugin.register("pixelSampler", "tile", lambda ps=None: TilePixelSampler((ps or {}).get("tilesize", 32), (ps or {}).get("random", True)))

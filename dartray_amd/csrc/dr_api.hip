@@ -199,9 +199,9 @@ void enumeratePixels(const RenderParams& rp, const DrRenderDesc* rd, std::vector
 namespace dr_host {
 
 // The two LayoutOps tables, defined once: layout_state_words() is evaluated here and nowhere else.
-const LayoutOps kLayout64 = {&launch_trace, &launch_trace_coherent, &trace_kernel_id, &launch_gen_samples, &launch_gen_strat, &launch_export_samples, &launch_adaptive_decide, &launch_mark_alive, &launch_sum_alive, &launch_transpose_samples, &launch_raygen, &launch_shade_path,
+const LayoutOps kLayout64 = {&launch_trace, &launch_trace_coherent, &trace_kernel_id, &launch_gen_samples, &launch_gen_strat, &launch_export_samples, &launch_adaptive_decide, &launch_halton_select, &launch_gen_halton, &launch_mark_alive, &launch_sum_alive, &launch_transpose_samples, &launch_raygen, &launch_shade_path,
                              &launch_env, &launch_shade_direct, &launch_shade_spec, &launch_film, layout_state_words()};
-const LayoutOps kLayoutSp4 = {&sp4::launch_trace, &sp4::launch_trace_coherent, &sp4::trace_kernel_id, &sp4::launch_gen_samples, &sp4::launch_gen_strat, &sp4::launch_export_samples, &sp4::launch_adaptive_decide, &sp4::launch_mark_alive, &sp4::launch_sum_alive, &sp4::launch_transpose_samples, &sp4::launch_raygen,
+const LayoutOps kLayoutSp4 = {&sp4::launch_trace, &sp4::launch_trace_coherent, &sp4::trace_kernel_id, &sp4::launch_gen_samples, &sp4::launch_gen_strat, &sp4::launch_export_samples, &sp4::launch_adaptive_decide, &sp4::launch_halton_select, &sp4::launch_gen_halton, &sp4::launch_mark_alive, &sp4::launch_sum_alive, &sp4::launch_transpose_samples, &sp4::launch_raygen,
                               &sp4::launch_shade_path, &sp4::launch_env, &sp4::launch_shade_direct, &sp4::launch_shade_spec,
                               &sp4::launch_film, sp4::layout_state_words()};
 
@@ -232,7 +232,8 @@ BatchState makeState(Workspace& w, const SampleForm& sf, const int2* pix, uint32
 }
 
 void RenderPlan::genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const {
-  if (strat) L->gen_strat(rpB, st, np, stratX, s);
+  if (halton) L->gen_halton(rpB, st, haltonWin, sc->ws.haltonIdx.p, sc->ws.pix.p, sc->ws.haltonKeyPix.p, s);
+  else if (strat) L->gen_strat(rpB, st, np, stratX, s);
   else L->gen_samples(rpB, st, np, s);
 }
 
@@ -354,7 +355,7 @@ int dr_scene_workspace_bytes(const DrScene* sc, uint64_t* bytes_out) {
   const Workspace& w = sc->ws;
   *bytes_out = w.tiles.bytes() + w.scr.bytes() + w.genState.bytes() + w.tail.bytes() + w.tailOff.bytes() + w.activeA.bytes() + w.activeB.bytes() +
                w.closestQ.bytes() + w.anyQ.bytes() + w.counters.bytes() + w.spill.bytes() + w.envQ.bytes() + w.alive.bytes() + w.roundA.bytes() +
-               w.roundB.bytes() + w.specFrames.bytes() + w.specSp.bytes() + w.pix.bytes() + w.adaptList.bytes() + w.adaptCount.bytes() + w.filterTable.bytes() + w.aosSamples.bytes();
+               w.roundB.bytes() + w.specFrames.bytes() + w.specSp.bytes() + w.pix.bytes() + w.adaptList.bytes() + w.adaptCount.bytes() + w.haltonIdx.bytes() + w.haltonKeyPix.bytes() + w.haltonBlk.bytes() + w.filterTable.bytes() + w.aosSamples.bytes();
   return DR_OK;
 }
 
@@ -430,7 +431,14 @@ int planRender(RenderPlan& P) {
     P.adMin = mn;
     P.adMax = mx;
   }
-  const int spp = P.spp = P.adaptivePass ? P.adMin : rd->spp;  // (adaptive: this plan is the first pass)
+  P.halton = rd->sampler_mode == DR_SAMPLER_HALTON;
+  if (P.halton) {
+    // HaltonSampler (halton_sampler.dart:31-48): any positive pixelsamples; ONE sequence per task over the task's own window, so the
+    // tile round-robin -- a share of the pixels -- has nothing to deal out
+    if (rd->spp < 1) return fail(DR_ERR_INVALID, "halton sampler: pixelsamples (spp) must be at least 1");
+    if (rd->tile_count > 1) return fail(DR_ERR_UNSUPPORTED, "halton sampler: tile_count > 1 (the tile round-robin deals out pixels; a task's Halton sequence is not bound to pixels: split by task_num / task_count)");
+  }
+  const int spp = P.spp = P.adaptivePass ? P.adMin : (P.halton ? 1 : rd->spp);  // (adaptive: this plan is the first pass; halton: one slot per accepted sample)
   P.strat = rd->sampler_mode == DR_SAMPLER_STRATIFIED || rd->sampler_mode == DR_SAMPLER_STRATIFIED_NOJITTER;
   if (P.strat && (spp <= 0 || (spp & (spp - 1)) != 0 || spp > 4096))
     return fail(DR_ERR_UNSUPPORTED, "stratified sampler: xsamples * ysamples must be a power of two, at most 4096 (the slot -> pixel maps of the batches are shifts)");
@@ -453,7 +461,7 @@ int planRender(RenderPlan& P) {
   // DARTRAY_STATE_LAYOUT=64|4 forces one, dr_scene_set_state_layout stores one; renders too small for a pilot keep round 3's
   // rule (plain-triangle scenes under an environment map: sp4).
   const DrOpt layoutEnv = dr_opt("DARTRAY_STATE_LAYOUT");
-  P.layoutKnown = layoutEnv || sc->stateLayout != 0 || rd->integrator != DR_INTEGRATOR_PATH;
+  P.layoutKnown = layoutEnv || sc->stateLayout != 0 || rd->integrator != DR_INTEGRATOR_PATH || P.halton;  // (halton: no pilot of its own)
   const bool sparseLayout = layoutEnv ? layoutEnv.toInt(0) == 4 : (sc->stateLayout ? sc->stateLayout == 4 : P.envStage);
   P.L = sparseLayout ? &kLayoutSp4 : &kLayout64;
   P.maxStateWords = P.layoutKnown ? P.L->stateWords : std::max(kLayout64.stateWords, kLayoutSp4.stateWords);
@@ -498,7 +506,11 @@ int planRender(RenderPlan& P) {
           return fail(DR_ERR_UNSUPPORTED, "stratified sampler: a light's nsamples must be a power of two (StratifiedSampler.roundSize is the identity, the scene's sample layout is the rounded one)");
     P.stratX = xs;
   }
-  if (!P.strat && rd->integrator == DR_INTEGRATOR_PATH && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
+  if (P.halton && rd->integrator == DR_INTEGRATOR_DIRECT_ALL)  // HaltonSampler.roundSize is the identity as well (halton_sampler.dart:102-104)
+    for (int n : sc->lightNSamples)
+      if (n > 1 && (n & (n - 1)) != 0)
+        return fail(DR_ERR_UNSUPPORTED, "halton sampler: a light's nsamples must be a power of two (HaltonSampler.roundSize is the identity, the scene's sample layout is the rounded one)");
+  if (!P.strat && !P.halton && rd->integrator == DR_INTEGRATOR_PATH && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
     // What the path kernels read of a pixel sample (dr_kernels.hip: k_raygen, load_shade_in, k_film): the image sample,
     // the lens sample of a thin-lens camera, and per SAMPLE_DEPTH level b <= maxDepth the light number, the light
     // sample (component + position), the BSDF and path directions; the two uComponent slots only where a material has
@@ -536,13 +548,32 @@ int planRender(RenderPlan& P) {
     for (int64_t i = 0; i < np; ++i) P.pixels[i] = make_int2(rd->pixel_xy[2 * i], rd->pixel_xy[2 * i + 1]);
   } else if (rd->sampler_mode == DR_SAMPLER_COUNTER || P.strat || P.adaptivePass) {
     enumeratePixels(rp, rd, P.pixels);
+  } else if (P.halton) {
+    // the task's window as the reference hands it to the sampler (GetSubWindow's extents as they are: see enumeratePixels)
+    int ext[4];
+    getSubWindow(rp.extW, rp.extH, rd->task_num, std::max(1, rd->task_count), ext);
+    const int w = ext[1] - ext[0], h = ext[3] - ext[2], delta = std::max(w, h);
+    P.pixels.clear();
+    const int32_t win[5] = {ext[0], ext[2], ext[0] + w - 1, ext[2] + h - 1, delta};
+    memcpy(P.haltonWin, win, sizeof(win));
+    const uint64_t wanted = w > 0 && h > 0 ? (uint64_t)rd->spp * (uint64_t)delta * (uint64_t)delta : 0ull;  // wantedSamples (halton_sampler.dart:35-36)
+    if (wanted >= (1ull << 53)) return fail(DR_ERR_UNSUPPORTED, "halton sampler: pixelsamples * max(width, height)^2 must stay below 2^53 (RadicalInverse takes the index through a double)");
+    // (the key pixel of index k is (extX0 + k % extW, extY0 + k / extW): k_gen_halton)
+    if (wanted / (uint64_t)std::max(1, rp.extW) >= (uint64_t)(0x7fffffff - std::abs(rp.extY0)))
+      return fail(DR_ERR_UNSUPPORTED, "halton sampler: pixelsamples * max(width, height)^2 must stay below 2^31 rows of the sampler extent (the in-Li streams are keyed by the index as a pixel of the extent)");
+    P.npixTotal = (size_t)wanted;
+    // film_samples, as for the other modes: the window's pixels that the film holds x pixelsamples (what the sequence aims at)
+    const int64_t fw = std::min(ext[1], rp.left + rp.width) - std::max(ext[0], rp.left), fh = std::min(ext[3], rp.top + rp.height) - std::max(ext[2], rp.top);
+    P.filmSamples = fw > 0 && fh > 0 ? (uint64_t)fw * (uint64_t)fh * (uint64_t)rd->spp : 0ull;
   } else {
     return fail(DR_ERR_INVALID, "unknown sampler mode");
   }
-  P.npixTotal = P.pixels.size();
-  P.filmSamples = 0;
-  for (const int2& p : P.pixels)
-    if (p.x >= rp.left && p.x < rp.left + rp.width && p.y >= rp.top && p.y < rp.top + rp.height) P.filmSamples += spp;
+  if (!P.halton) {
+    P.npixTotal = P.pixels.size();
+    P.filmSamples = 0;
+    for (const int2& p : P.pixels)
+      if (p.x >= rp.left && p.x < rp.left + rp.width && p.y >= rp.top && p.y < rp.top + rp.height) P.filmSamples += spp;
+  }
   P.sgrid = g_numCU;  // the shade launchers size their grid per CU (DR_SHADE_GRID), grid-stride over the active list
   P.nStages = rd->integrator == DR_INTEGRATOR_PATH ? rd->max_depth + 2 : rp.nDirectStages + 1;
   if (P.nStages > CounterLayout::maxStages()) return fail(DR_ERR_UNSUPPORTED, "too many stages");
@@ -558,7 +589,7 @@ int planBatches(RenderPlan& P) {
   // Sample vectors: the on-device LD sampler stores permuted indices + scrambles (compact form) whenever every LD block
   // has one entry per pixel sample; host buffers and multi-entry blocks (DirectLighting with nsamples > 1) use floats.
   SampleForm& sf = P.sf;
-  sf.compact = !P.hostBuf && !P.strat && rp.blocks == nullptr;  // (the stratified sampler's values are no function of an index: floats)
+  sf.compact = !P.hostBuf && !P.strat && !P.halton && rp.blocks == nullptr;  // (the stratified and Halton samplers' values are no function of an LD index: floats)
   if (!sf.compact && !P.hostBuf && !P.strat && spp > 1024)
     return fail(DR_ERR_UNSUPPORTED, "spp > 1024 with LD blocks of several entries per sample (DirectLighting with nsamples > 1): the float-form sampler's table exceeds the LDS");
   sf.nFloats = rp.nFloats;
@@ -596,7 +627,7 @@ int planBatches(RenderPlan& P) {
   // (the sampler window of a 1024 x 1024 film is 1025 x 1025 pixels -- 2^20 + 2049).
   const uint64_t pixCapBatch = std::max<uint64_t>(1, maxSlots / spp);
   P.nBatches = (P.npixTotal + pixCapBatch - 1) / pixCapBatch;
-  if (P.nBatches > 1 && P.npixTotal <= pixCapBatch + pixCapBatch / 4) P.nBatches = 1;
+  if (!P.halton && P.nBatches > 1 && P.npixTotal <= pixCapBatch + pixCapBatch / 4) P.nBatches = 1;  // (halton: a batch's range is its slot capacity at most)
   P.pixPerBatch = (uint32_t)((P.npixTotal + P.nBatches - 1) / P.nBatches);
   P.cap = P.pixPerBatch * (uint32_t)spp;
   P.wsCap = P.cap;
@@ -665,7 +696,7 @@ int prepareRender(RenderPlan& P) {
   rc = ensureSpill(sc, sc->ws, P.tgrid);
   if (rc) return rc;
   // the camera rays (a tile = 64 samples of one pixel) through the wave-coherent kernel k_trace_pk (DARTRAY_COHERENT_CAMERA=0: k_trace & co.)
-  P.coherentCamera = !dr_opt("DARTRAY_COHERENT_CAMERA").isZero() && !P.dlSpec;
+  P.coherentCamera = !dr_opt("DARTRAY_COHERENT_CAMERA").isZero() && !P.dlSpec && !P.halton;  // (halton: a tile's slots are samples of 64 pixels)
   // lazy sample generation (DARTRAY_LAZY_GEN=0: every block for every pixel up front): needs the device sampler's compact form, the keyed
   // per-(pixel, block) streams (a block that is left out disturbs no other) and k_trace_pk's marks of the camera rays that hit
   P.lazyGen = lazyGenFor(P);
@@ -681,7 +712,7 @@ int prepareRender(RenderPlan& P) {
   // on the choice; dr_scene_set_trace_kernels / DARTRAY_TRACE_IMPL fix it (an N-rank host measures on rank 0 and hands the choice on).
   const DrOpt pilotOpt = dr_opt("DARTRAY_PILOT");  // 0: never; force: also on renders too small to need one (tests)
   const bool bigJob = (sc->d.nnodes >= (1u << 20) && (uint64_t)P.npixTotal * spp >= (1ull << 25)) || pilotOpt.is("force");
-  const bool pilotOk = !pilotOpt.is("0") && !P.hostBuf && !P.dlSpec && bigJob && P.npixTotal >= 3 * 64 * 4;
+  const bool pilotOk = !pilotOpt.is("0") && !P.hostBuf && !P.dlSpec && !P.halton && bigJob && P.npixTotal >= 3 * 64 * 4;
   P.calibrateTrace = !sc->traceCalibrated && pilotOk && !dr_opt("DARTRAY_TRACE_IMPL") && sc->d.pairs && !sc->d.nquads;
   P.measureLayout = !P.layoutKnown && pilotOk;
   if (P.measureLayout) P.L = &kLayout64;  // the batch whose stage lists are measured runs in the 64-slot layout
@@ -709,8 +740,15 @@ int prepareRender(RenderPlan& P) {
     ordered.insert(ordered.end(), P.pixels.begin() + totalGroups * 64, P.pixels.end());
     P.pixels.swap(ordered);
   }
-  HIP_TRY(sc->ws.pix.alloc(P.npixTotal));
-  HIP_TRY(hipMemcpyAsync(sc->ws.pix.p, P.pixels.data(), P.npixTotal * sizeof(int2), hipMemcpyHostToDevice, P.s));
+  if (P.halton) {  // the pixel array is a batch's: k_gen_halton writes every slot's anchor pixel
+    HIP_TRY(sc->ws.pix.alloc(P.cap));
+    HIP_TRY(sc->ws.haltonIdx.alloc(P.cap));
+    HIP_TRY(sc->ws.haltonKeyPix.alloc(P.cap));
+    HIP_TRY(sc->ws.haltonBlk.alloc((size_t)(P.cap + 255u) / 256u + 1));
+  } else {
+    HIP_TRY(sc->ws.pix.alloc(P.npixTotal));
+    HIP_TRY(hipMemcpyAsync(sc->ws.pix.p, P.pixels.data(), P.npixTotal * sizeof(int2), hipMemcpyHostToDevice, P.s));
+  }
   if (P.adaptivePass) {  // the list of flagged pixels: every pixel of the render at most
     HIP_TRY(sc->ws.adaptList.alloc(P.npixTotal));
     HIP_TRY(sc->ws.adaptCount.alloc(2));
@@ -760,10 +798,13 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
     rc = runPilot(P, pilot);
     if (rc) return rc;
   }
-  // (a calibration set that was skipped left its pixels to the ordinary batches)
-  rc = runBatches(P, sc->ws.pix.p, (size_t)pilot.setsRun * P.calibPix);
-  if (rc) return rc;
   uint64_t cameraSamples = (uint64_t)P.npixTotal * P.spp, nBatches = P.nBatches;
+  if (P.halton) {  // one host wait per batch: how many indices of its range the window accepted
+    rc = runHaltonBatches(P, &cameraSamples);
+  } else {  // (a calibration set that was skipped left its pixels to the ordinary batches)
+    rc = runBatches(P, sc->ws.pix.p, (size_t)pilot.setsRun * P.calibPix);
+  }
+  if (rc) return rc;
   bool lazy2 = false;
   if (P.adaptivePass) {
     // the one host round trip of the mode: how many pixels the first pass flagged (and how many of them the film holds)
@@ -830,6 +871,7 @@ int dr_scene_get_adaptive_pixels(DrScene* sc, int32_t* out_xy, uint64_t cap, uin
 int dr_generate_samples(DrScene* sc, const DrRenderDesc* rd, const int32_t* pixel_xy, uint64_t npix, float* out, int32_t stride) {
   if (!sc || !rd || !pixel_xy || !out) return fail(DR_ERR_INVALID, "null argument");
   if (rd->sampler_mode == DR_SAMPLER_HOST_BUFFER) return fail(DR_ERR_INVALID, "dr_generate_samples: the host-buffer mode has no device sampler");
+  if (rd->sampler_mode == DR_SAMPLER_HALTON) return fail(DR_ERR_INVALID, "dr_generate_samples: the halton sampler's samples are not bound to pixels (dr_generate_halton_samples takes a range of the sequence)");
   if (npix == 0) return DR_OK;
   RenderPlan P;
   P.sc = sc;
@@ -861,6 +903,57 @@ int dr_generate_samples(DrScene* sc, const DrRenderDesc* rd, const int32_t* pixe
     HIP_TRY(hipMemcpyAsync(out + p0 * P.spp * (size_t)stride, aos.p, (size_t)nslots * stride * sizeof(float), hipMemcpyDeviceToHost, P.s));
     HIP_TRY(hipStreamSynchronize(P.s));
   }
+  return DR_OK;
+}
+
+int dr_generate_halton_samples(DrScene* sc, const DrRenderDesc* rd, uint64_t first_index, uint64_t count, uint64_t* k_out, int32_t* pixel_xy_out,
+                               float* out, int32_t stride, uint64_t* n_out) {
+  if (!sc || !rd || !n_out) return fail(DR_ERR_INVALID, "null argument");
+  *n_out = 0;
+  if (rd->sampler_mode != DR_SAMPLER_HALTON) return fail(DR_ERR_INVALID, "dr_generate_halton_samples: sampler_mode must be DR_SAMPLER_HALTON");
+  RenderPlan P;
+  P.sc = sc;
+  P.rd = rd;
+  int rc = planRender(P);
+  if (rc) return rc;
+  if (first_index > P.npixTotal || count > P.npixTotal - first_index)
+    return fail(DR_ERR_INVALID, "dr_generate_halton_samples: the range leaves the task's sequence (pixelsamples * max(width, height)^2 indices)");
+  if (count == 0) return DR_OK;
+  if (!k_out || !pixel_xy_out || !out) return fail(DR_ERR_INVALID, "null argument");
+  if (stride < P.rp.nFloats) return fail(DR_ERR_INVALID, "dr_generate_halton_samples: stride smaller than the sample vector");
+  // the plan of a render of these indices: the same sample form, ranges and launches
+  P.npixTotal = (size_t)count;
+  rc = planBatches(P);
+  if (rc) return rc;
+  rc = allocWorkspace(sc, sc->ws, P.cap, P.sf, P.pixPerBatch, rd->max_tail, false, P.maxStateWords);
+  if (rc) return rc;
+  Workspace& w = sc->ws;
+  HIP_TRY(w.pix.alloc(P.cap));
+  HIP_TRY(w.haltonIdx.alloc(P.cap));
+  HIP_TRY(w.haltonKeyPix.alloc(P.cap));
+  HIP_TRY(w.haltonBlk.alloc((size_t)(P.cap + 255u) / 256u + 1));
+  DevBuf<float> aos;
+  HIP_TRY(aos.alloc((size_t)P.cap * stride));
+  HIP_TRY(hipMemsetAsync(aos.p, 0, (size_t)P.cap * stride * sizeof(float), P.s));  // (the words of a row behind the vector)
+  uint64_t done = 0;
+  for (uint64_t i0 = 0; i0 < count; i0 += P.pixPerBatch) {
+    const uint32_t n = (uint32_t)std::min<uint64_t>(P.pixPerBatch, count - i0);
+    uint32_t accepted = 0;
+    rc = haltonSelect(P, first_index + i0, n, &accepted);
+    if (rc) return rc;
+    if (accepted > n) return fail(DR_ERR_HIP, "halton sampler: the selection accepted more indices than its range holds");
+    if (accepted == 0) continue;
+    const BatchState st = makeState(w, P.sf, w.pix.p, accepted, false, P.L->stateWords);
+    P.genSamples(P.rp, st, accepted);
+    P.L->export_samples(P.rp, st, aos.p, stride, P.s);
+    HIP_TRY(hipGetLastError());  // (a launch that could not start)
+    HIP_TRY(hipMemcpyAsync(out + done * (size_t)stride, aos.p, (size_t)accepted * stride * sizeof(float), hipMemcpyDeviceToHost, P.s));
+    HIP_TRY(hipMemcpyAsync(k_out + done, w.haltonIdx.p, (size_t)accepted * sizeof(uint64_t), hipMemcpyDeviceToHost, P.s));
+    HIP_TRY(hipMemcpyAsync(pixel_xy_out + 2 * done, w.pix.p, (size_t)accepted * sizeof(int2), hipMemcpyDeviceToHost, P.s));
+    HIP_TRY(hipStreamSynchronize(P.s));
+    done += accepted;
+  }
+  *n_out = done;
   return DR_OK;
 }
 

@@ -70,6 +70,13 @@ class BatchRunner {
   PilotTimes* pilot;
   uint32_t* C;  // the workspace's counters (CounterLayout)
   BatchState st;
+  // The state as the shade stages see it: st itself, but a Halton batch's pixel array is the slots' KEY pixels (k_gen_halton): the streams
+  // of the draws inside Li are keyed by the sample's sequence index, not by the pixel it is anchored in
+  BatchState shadeState() const {
+    BatchState s2 = st;
+    if (P.halton) s2.pix = w.haltonKeyPix.p;
+    return s2;
+  }
   uint32_t nGroups = 0;  // lazy generation: 64-pixel groups of this batch
   int wc = 0;            // trace launches of this round so far: each has its own work counters (CounterLayout::workCounters)
   int stageCounts = 0;
@@ -221,14 +228,15 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
   const bool log = stageCounts && round == 0;
   hipEvent_t evS = sc->getEvent();
   (void)hipEventRecord(evS, s);
-  if (rd->integrator == DR_INTEGRATOR_PATH) L.shade_path(sc->d, rp, st, q, b, P.sgrid, s);
-  else L.shade_direct(sc->d, rp, st, q, b, P.sgrid, s);
+  const BatchState stS = shadeState();
+  if (rd->integrator == DR_INTEGRATOR_PATH) L.shade_path(sc->d, rp, stS, q, b, P.sgrid, s);
+  else L.shade_direct(sc->d, rp, stS, q, b, P.sgrid, s);
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {
     evMid = sc->getEvent();
     (void)hipEventRecord(evMid, s);
   }
-  if (P.envStage) L.env(sc->d, rp, st, q, b, P.sgrid, s);
+  if (P.envStage) L.env(sc->d, rp, stS, q, b, P.sgrid, s);
   hipEvent_t evS1 = timed(TimedKind::Shade, evS);
   if (P.lazyGen && round == 0 && b < 2 && b + 1 <= rd->max_depth) {  // bounce b + 1's blocks for the groups in this stage's output list
     L.mark_alive(q.activeOut, q.nActiveOut, (uint32_t)rp.sppShift + 6u, w.alive.p + (size_t)(b + 1) * nGroups, s);
@@ -279,7 +287,7 @@ int BatchRunner::specRound(int round, const uint32_t*& roundQ, const uint32_t*& 
   q.ctr = sc->ctr.p;
   hipEvent_t evS = sc->getEvent();
   (void)hipEventRecord(evS, s);
-  L.shade_spec(sc->d, rp, st, q, P.sgrid, s);
+  L.shade_spec(sc->d, rp, shadeState(), q, P.sgrid, s);
   timed(TimedKind::Shade, evS);
   uint32_t live = 0;  // (a synchronous read-back per round: this is not the throughput path)
   HIP_TRY(hipMemcpyAsync(&live, nNext, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -430,6 +438,38 @@ int runBatches(RenderPlan& plan, const int2* pixDev, size_t firstPixel) {
   for (size_t p0 = firstPixel; p0 < plan.npixTotal; p0 += plan.pixPerBatch) {
     const uint32_t np = (uint32_t)std::min<size_t>(plan.pixPerBatch, plan.npixTotal - p0);
     const int rc = BatchRunner(plan, plan.sc->ws, pixDev + p0, p0, np, nullptr).run();
+    if (rc) return rc;
+  }
+  return DR_OK;
+}
+
+int haltonSelect(RenderPlan& P, uint64_t k0, uint32_t n, uint32_t* accepted) {
+  Workspace& w = P.sc->ws;
+  P.L->halton_select(P.haltonWin, k0, n, w.haltonBlk.p, w.haltonIdx.p, P.s);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(accepted, w.haltonBlk.p + (n + 255u) / 256u, sizeof(uint32_t), hipMemcpyDeviceToHost, P.s));
+  HIP_TRY(hipStreamSynchronize(P.s));
+  return DR_OK;
+}
+
+// The batches of a Halton render: equal ranges of the sequence's indices.  Per batch: the selection, its count read back, then an
+// ordinary batch of that many slots whose sample generation (RenderPlan::genSamples) also writes the slots' anchor pixels.
+int runHaltonBatches(RenderPlan& P, uint64_t* acceptedTotal) {
+  DrScene* sc = P.sc;
+  *acceptedTotal = 0;
+  for (uint64_t k0 = 0; k0 < P.npixTotal; k0 += P.pixPerBatch) {
+    const uint32_t n = (uint32_t)std::min<uint64_t>(P.pixPerBatch, P.npixTotal - k0);
+    hipEvent_t e0 = sc->getEvent(), e1 = sc->getEvent();
+    (void)hipEventRecord(e0, P.s);
+    uint32_t accepted = 0;
+    int rc = haltonSelect(P, k0, n, &accepted);
+    if (rc) return rc;
+    (void)hipEventRecord(e1, P.s);
+    sc->traceEvents.push_back({e0, e1, TimedKind::Gen});
+    if (accepted > n) return fail(DR_ERR_HIP, "halton sampler: the selection accepted more indices than its range holds");
+    *acceptedTotal += accepted;
+    if (accepted == 0) continue;
+    rc = BatchRunner(P, sc->ws, sc->ws.pix.p, 0, accepted, nullptr).run();
     if (rc) return rc;
   }
   return DR_OK;

@@ -68,6 +68,9 @@ struct Workspace {
   DevBuf<int2> pix;
   DevBuf<int2> adaptList;       // DR_SAMPLER_ADAPTIVE: the raster pixels the first pass flagged (k_adaptive_decide), the second pass's pixel array
   DevBuf<uint32_t> adaptCount;  //   [0] their number, [1] those inside the film window
+  DevBuf<unsigned long long> haltonIdx;  // DR_SAMPLER_HALTON: the sequence index of every slot of the batch,
+  DevBuf<int2> haltonKeyPix;             //   the pixel whose index in the sampler extent is that index: the shade stages' pixel array (k_gen_halton)
+  DevBuf<uint32_t> haltonBlk;            //   the selection's per-workgroup counts / offsets; the word behind them: the batch's slot count
   DevBuf<float> filterTable, aosSamples;
   int spillGrid = 0;
 };
@@ -239,6 +242,8 @@ struct LayoutOps {
   decltype(&launch_gen_strat) gen_strat;
   decltype(&launch_export_samples) export_samples;
   decltype(&launch_adaptive_decide) adaptive_decide;
+  decltype(&launch_halton_select) halton_select;
+  decltype(&launch_gen_halton) gen_halton;
   decltype(&launch_mark_alive) mark_alive;
   decltype(&launch_sum_alive) sum_alive;
   decltype(&launch_transpose_samples) transpose_samples;
@@ -265,6 +270,10 @@ struct RenderPlan {
   bool direct = false, dlSpec = false, envStage = false, hostBuf = false, packedTail = false;
   bool strat = false;     // DR_SAMPLER_STRATIFIED(_NOJITTER): the device sampler writes the float sample form
   int stratX = 0;         //   xPixelSamples (yPixelSamples = spp / stratX)
+  // DR_SAMPLER_HALTON: a "pixel" of this plan is an INDEX of the task's sequence (npixTotal = wanted, spp = 1: one slot
+  // per accepted sample); a batch is a range of indices, selected on the device before it runs with as many slots as were accepted
+  bool halton = false;
+  int32_t haltonWin[5] = {0, 0, 0, 0, 0};  // the task's window: left, top, right, bottom (inclusive), delta = max(width, height)
   // the device sampler's launches for one batch (BatchRunner::loadSamples, dr_generate_samples)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
   // DR_SAMPLER_ADAPTIVE: two counter-mode passes.  This plan is the first (every pixel at adMin samples: spp,
@@ -305,6 +314,9 @@ struct PilotResult {
 BatchState makeState(Workspace& w, const SampleForm& sf, const int2* pix, uint32_t nslots, bool useTail, int stateWords);  // dr_api.hip
 int runBatches(RenderPlan& plan, const int2* pixDev, size_t firstPixel);                                                    // dr_batch.hip
 int runPilot(RenderPlan& P, PilotResult& R);                                                                                // dr_batch.hip
+// DR_SAMPLER_HALTON: the accepted indices of [k0, k0 + n) into the workspace (haltonIdx), their number read back (the mode's host wait)
+int haltonSelect(RenderPlan& P, uint64_t k0, uint32_t n, uint32_t* accepted);                                               // dr_batch.hip
+int runHaltonBatches(RenderPlan& P, uint64_t* acceptedTotal);                                                               // dr_batch.hip
 
 }  // namespace dr_host
 

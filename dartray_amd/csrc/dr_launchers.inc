@@ -20,6 +20,14 @@ void launch_export_samples(const RenderParams& rp, const BatchState& st, float* 
 // flagged pixels are appended to list (counts[0]: its length, counts[1]: those inside the film window) and retired from pix
 void launch_adaptive_decide(const RenderParams& rp, const BatchState& st, uint32_t npix, int2* pix, int2* list, uint32_t* counts,
                             uint32_t listCap, hipStream_t s);
+// dr_sampler_halton.hip (DR_SAMPLER_HALTON).  win[5] = the task's window as HaltonSampler holds it: left, top, right, bottom (inclusive,
+// sampler.dart:52-54), delta = max(width, height).  launch_halton_select: the indices of [k0, k0 + n) of the task's sequence that fall inside the
+// window, in increasing order, to seqIdx (room for n); blk: (n + 255) / 256 + 1 words, the last receives their number.  launch_gen_halton: the
+// st.nslots accepted samples' float-form vectors, their anchor pixels (pix[slot]: k_raygen, k_film) and their KEY pixels (keyPix[slot]: the pixel
+// whose index in the sampler extent is the sample's sequence index -- what the in-Li streams of the shade kernels are keyed by)
+void launch_halton_select(const int32_t win[5], uint64_t k0, uint32_t n, uint32_t* blk, unsigned long long* seqIdx, hipStream_t s);
+void launch_gen_halton(const RenderParams& rp, const BatchState& st, const int32_t win[5], const unsigned long long* seqIdx, int2* pix, int2* keyPix,
+                       hipStream_t s);
 void launch_mark_alive(const uint32_t* list, const uint32_t* nList, uint32_t shift, uint8_t* alive, hipStream_t s);
 void launch_sum_alive(const uint8_t* alive, uint32_t nGroups, uint32_t npix, const uint32_t nb[3], TraceCounters* ctr, hipStream_t s);
 void launch_transpose_samples(const float* aos, int stride, const BatchState& st, int nFloats, hipStream_t s);

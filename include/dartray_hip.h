@@ -239,6 +239,20 @@ typedef struct DrFilm {
  * swapping / rounding / doubling, adaptive_sampler.dart:53-83): DR_ERR_INVALID otherwise.  Method "shapeid" does not exist here (the camera
  * hit's ids are not kept per sample).  One host round trip per call (the number of flagged pixels); dr_scene_get_adaptive_pixels lists them. */
 #define DR_SAMPLER_ADAPTIVE 4
+/* On-device HaltonSampler (halton_sampler.dart:31-104); DESIGN.md section 2.9.  The samples belong to the IMAGE, not to a pixel: with
+ * (left, top, width, height) the call's task window of the sampler extent and delta = max(width, height), index k of the task's own sequence,
+ * k in [0, spp * delta * delta), lands at imageX = Lerp(RadicalInverse(k, 3), left, left + delta), imageY = Lerp(RadicalInverse(k, 2), top,
+ * top + delta) (f64) and is REJECTED iff imageX > left + width - 1 || imageY > top + height - 1; lens and time are the radical inverses of
+ * k + 1 in bases 5, 7, 11 (the reference's increment comes first), the integrator's slots LatinHypercube draws on the keyed stream
+ * (seed, k, 0, kind 5), the draws inside Li the stream (seed, k, 0, kind 2).  Pixels receive different numbers of samples.
+ * DrRenderDesc.spp = pixelsamples: ANY integer >= 1 (DR_ERR_INVALID otherwise); strat_xsamples is ignored.  A task owns its own sequence over
+ * its own sub-window (task_num / task_count), as the reference builds one sampler per task; tile_count > 1 is DR_ERR_UNSUPPORTED (tiles deal out
+ * pixels), and so are spp * delta^2 >= 2^53 (or 2^31 rows of the sampler extent: the in-Li streams are keyed by the index as a pixel of the
+ * extent) and, under DR_INTEGRATOR_DIRECT_ALL, a light whose nsamples is no power of two (roundSize is the
+ * identity).  Departure from the reference, as for every sample vector here: image fraction, lens and time are rounded to f32 once (the image
+ * sample by at most 2^-25 pixel).  One host wait per batch of the call (the number of accepted samples of the batch's index range).
+ * DrRenderStats.camera_samples counts the accepted samples, film_samples the window's film pixels x spp. */
+#define DR_SAMPLER_HALTON 5
 
 /* Everything SamplerRenderer.render needs besides the Scene
  * (lib/renderers/sampler_renderer.dart:29-31,36-65). */
@@ -247,7 +261,8 @@ typedef struct DrRenderDesc {
   DrFilm film;
   int32_t integrator;
   int32_t max_depth; /* PathIntegrator.maxDepth / DirectLightingIntegrator.maxDepth (default 5) */
-  int32_t spp;       /* LowDiscrepancySampler.nPixelSamples, StratifiedSampler's xPixelSamples * yPixelSamples or AdaptiveSampler.maxSamples, power of two */
+  int32_t spp;       /* LowDiscrepancySampler.nPixelSamples, StratifiedSampler's xPixelSamples * yPixelSamples or AdaptiveSampler.maxSamples, power of two;
+                      * DR_SAMPLER_HALTON: pixelsamples, any integer >= 1 */
   int32_t sampler_mode;
   int64_t seed; /* DR_SAMPLER_COUNTER */
   /* Work split.  task_*: the reference's GetSubWindow rectangle of the sampler
@@ -408,10 +423,12 @@ int dr_render(DrScene* scene, const DrRenderDesc* desc, float* film_out, float* 
  * in front of later work of it; internally a stage's any-hit launch runs on a
  * stream of the scene's own, beside the closest-hit launch, tied to hip_stream
  * by events (DARTRAY_OVERLAP_ANY=0: everything on hip_stream).
- * The call returns with its kernels enqueued, except in three cases where it waits for hip_stream itself: the
+ * The call returns with its kernels enqueued, except in four cases where it waits for hip_stream itself: the
  * first big render of a big scene (the traversal-kernel pilot reads its counters back between its three batches),
- * DR_SAMPLER_HOST_BUFFER (the host sample buffers of a batch are staged before the next batch reuses the area), and
- * DirectLighting over mirror / glass materials (one count is read back per round of the specular recursion). */
+ * DR_SAMPLER_HOST_BUFFER (the host sample buffers of a batch are staged before the next batch reuses the area),
+ * DirectLighting over mirror / glass materials (one count is read back per round of the specular recursion), and
+ * DR_SAMPLER_HALTON (per batch, the number of samples its index range accepted is read back before the batch is launched;
+ * DR_SAMPLER_ADAPTIVE likewise reads one count between its passes). */
 int dr_render_device(DrScene* scene, const DrRenderDesc* desc, void* film_dev, void* hip_stream);
 
 /* The raster pixels a DR_SAMPLER_COUNTER render of `desc` traces, in trace
@@ -426,6 +443,15 @@ int dr_enumerate_pixels(const DrRenderDesc* desc, int32_t* out_xy, uint64_t cap,
  * kernel reads).  The film window, the task / tile split and the seed of `desc` are read as a render reads them: the streams are keyed by
  * a pixel's position in the full sampler extent. */
 int dr_generate_samples(DrScene* scene, const DrRenderDesc* desc, const int32_t* pixel_xy, uint64_t npix, float* out, int32_t stride);
+
+/* Diagnostics and tests: runs ONLY the device sampler of `desc` (DR_SAMPLER_HALTON; any other mode is DR_ERR_INVALID, as this mode is for
+ * dr_generate_samples) for the indices [first_index, first_index + count) of the task's sequence -- the selection and generation launches of a
+ * render, in the render's own workspace -- and copies back, for the *n_out <= count accepted samples in increasing index order: k_out[n] their
+ * indices, pixel_xy_out[n][2] their anchor pixels (floor(imageX), floor(imageY)) and out[n][stride] their sample vectors in reference field order
+ * (the image sample as its fraction behind the anchor pixel, time raw), stride >= dr_scene_sample_floats.  The caller sizes the three buffers for
+ * `count` entries.  A range that leaves [0, spp * delta * delta) is DR_ERR_INVALID. */
+int dr_generate_halton_samples(DrScene* scene, const DrRenderDesc* desc, uint64_t first_index, uint64_t count, uint64_t* k_out,
+                               int32_t* pixel_xy_out, float* out, int32_t stride, uint64_t* n_out);
 
 /* Diagnostics and tests: the raster pixels the scene's LAST render call supersampled (DR_SAMPLER_ADAPTIVE: those traced at maxSamples;
  * any other sampler: none), out_xy[n][2] in no particular order.  *n_out is always written; out_xy may be NULL to query the count,
@@ -482,7 +508,9 @@ const char* dr_version(void);
  * an older header would hand the library a shorter object than it reads (version 5 -> 6: DrRenderDesc grew by tail_offsets, 1344 -> 1352
  * bytes; version 6 -> 7: DR_INTEGRATOR_DIRECT_ONE, dr_scene_workspace_bytes, the switch list of dr_set_option;
  * 8: DR_SAMPLER_STRATIFIED, strat_xsamples -- the former padding at offset 1292 -- and dr_generate_samples;
- * 9: DR_SAMPLER_ADAPTIVE -- minSamples travels in strat_xsamples, no layout change -- and dr_scene_get_adaptive_pixels). */
+ * 9: DR_SAMPLER_ADAPTIVE -- minSamples travels in strat_xsamples, no layout change -- and dr_scene_get_adaptive_pixels.
+ * Still 9: DR_SAMPLER_HALTON and dr_generate_halton_samples are additive -- a new constant and a new entry point, no struct changes, no
+ * existing call means anything else; a host built against the earlier version-9 header runs unchanged). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 

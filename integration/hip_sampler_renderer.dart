@@ -172,6 +172,7 @@ const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
 const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
 const int DR_SAMPLER_ADAPTIVE = 4;             // AdaptiveSampler (contrast) on the LD sampler's keyed streams; spp = maxSamples
+const int DR_SAMPLER_HALTON = 5;               // HaltonSampler: one sequence per task, samples not bound to pixels; spp = samplesPerPixel, any count
 
 typedef _InitC = Int32 Function(Int32);
 typedef _InitD = int Function(int);
@@ -203,6 +204,10 @@ typedef _GetLayoutC = Int32 Function(Pointer<Void>, Pointer<Int32>, Pointer<Floa
 typedef _GetLayoutD = int Function(Pointer<Void>, Pointer<Int32>, Pointer<Float>);
 typedef _AdaptivePixelsC = Int32 Function(Pointer<Void>, Pointer<Int32>, Uint64, Pointer<Uint64>);
 typedef _AdaptivePixelsD = int Function(Pointer<Void>, Pointer<Int32>, int, Pointer<Uint64>);
+typedef _HaltonSamplesC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Uint64, Uint64, Pointer<Uint64>, Pointer<Int32>, Pointer<Float>, Int32,
+    Pointer<Uint64>);
+typedef _HaltonSamplesD = int Function(Pointer<Void>, Pointer<Uint8>, int, int, Pointer<Uint64>, Pointer<Int32>, Pointer<Float>, int,
+    Pointer<Uint64>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -272,6 +277,27 @@ class HipSamplerRenderer extends Renderer {
   static final _KernelsD _setTraceKernels = _lib.lookupFunction<_KernelsC, _KernelsD>('dr_scene_set_trace_kernels');
   static final _AdaptivePixelsD _getAdaptivePixels =
       _lib.lookupFunction<_AdaptivePixelsC, _AdaptivePixelsD>('dr_scene_get_adaptive_pixels');
+
+  static final _HaltonSamplesD _generateHaltonSamples =
+      _lib.lookupFunction<_HaltonSamplesC, _HaltonSamplesD>('dr_generate_halton_samples');
+
+  /// Diagnostics (dr_generate_halton_samples): how many of the indices [first, first + count) of a Halton render's sequence fall inside
+  /// the task's window.  [rd] is the render descriptor as render() fills it, [stride] the floats of a sample vector.
+  int _haltonAccepted(Pointer<Void> scene, _Blob rd, int first, int count, int stride) {
+    Pointer<Uint64> indices = calloc<Uint64>(count < 1 ? 1 : count);
+    Pointer<Int32> pixels = calloc<Int32>(count < 1 ? 2 : 2 * count);
+    Pointer<Float> vectors = calloc<Float>(count < 1 ? 1 : count * stride);
+    Pointer<Uint64> accepted = calloc<Uint64>(1);
+    try {
+      _check(_generateHaltonSamples(scene, rd.ptr, first, count, indices, pixels, vectors, stride, accepted));
+      return accepted.value;
+    } finally {
+      calloc.free(indices);
+      calloc.free(pixels);
+      calloc.free(vectors);
+      calloc.free(accepted);
+    }
+  }
 
   /// How many pixels the last render of this renderer traced a second time at the adaptive sampler's maximum count
   /// (dr_scene_get_adaptive_pixels; 0 under every other sampler).
@@ -797,7 +823,8 @@ class HipSamplerRenderer extends Renderer {
       // are the one source of its strata.  (The class is told by its name: on the VM, where dart:ffi runs, runtimeType prints it.)
       final bool stratified = '${sampler.runtimeType}' == 'StratifiedSampler';
       final bool adaptive = '${sampler.runtimeType}' == 'AdaptiveSampler';
-      if (!stratified && !adaptive && sampler is! LowDiscrepancySampler) {
+      final bool halton = '${sampler.runtimeType}' == 'HaltonSampler';
+      if (!stratified && !adaptive && !halton && sampler is! LowDiscrepancySampler) {
         _unsupported('sampler ${sampler.runtimeType}');
       }
       // The device runs the same LD / stratified sampler with one keyed RNG stream per (pixel, LD block) / pixel / (pixel, sample)
@@ -820,6 +847,11 @@ class HipSamplerRenderer extends Renderer {
         rd.i32(OFF_DrRenderDesc_spp, maxSamples);
         rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_ADAPTIVE);
         rd.i32(OFF_DrRenderDesc_strat_xsamples, minSamples);  // (the field doubles as minSamples in this mode)
+      } else if (halton) {
+        // pixelsamples as given (samplers/halton_sampler.dart:106-113): any positive count, nothing is rounded.  One sequence per task
+        // over the task's own window; the library refuses the tile split for this sampler (tileCount > 1: DR_ERR_UNSUPPORTED).
+        rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
+        rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_HALTON);
       } else {
         rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
         rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_COUNTER);
