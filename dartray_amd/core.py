@@ -1161,6 +1161,31 @@ class LowDiscrepancySampler:
 ONE_MINUS_EPSILON = 0.9999999403953552  # montecarlo.dart:23
 
 
+def _latin_hypercube_slots(n1D, n2D, rng):
+    """LatinHypercube (montecarlo.dart:305-325) of every 1-D slot, then of every 2-D slot, drawn from rng -> their f32 values in the C ABI's field order."""
+    out = []
+    for n, dims in [(n, 1) for n in n1D] + [(n, 2) for n in n2D]:
+        v = np.zeros((n, dims), np.float32)
+        for j in range(n):
+            for d in range(dims):
+                v[j, d] = min((j + rng.randomFloat()) * (1.0 / n), ONE_MINUS_EPSILON)
+        for d in range(dims):
+            for j in range(n):
+                other = j + rng.randomUint() % (n - j)
+                v[j, d], v[other, d] = v[other, d], v[j, d]
+        out.append(v.reshape(-1))
+    return np.concatenate(out) if out else np.zeros(0, np.float32)
+
+
+def _pack_tails(tails):
+    """The in-Li draws of every sample (lists of different lengths; possibly none) -> (tail [n, longest or 1] f64 zero filled, count [n])."""
+    cnt = np.array([len(t) for t in tails], np.int32)
+    tail = np.zeros((len(tails), max(1, int(cnt.max()) if len(cnt) else 1)), np.float64)
+    for i, t in enumerate(tails):
+        tail[i, :len(t)] = t
+    return tail, cnt
+
+
 class StratifiedSampler:
     """samplers/stratified_sampler.dart:38-128: xsamples x ysamples jittered strata per pixel for the image and the lens
     sample, xsamples * ysamples strata for the time sample, the lens and time samples shuffled, and a LatinHypercube per
@@ -1219,18 +1244,7 @@ class StratifiedSampler:
         vec = np.zeros((spp, nf), f32)
         vec[:, 0:2], vec[:, 2:4], vec[:, 4:5] = image, lens, time
         for i in range(spp):
-            rng, o = sample_rng(i), 5
-            for n, dims in [(n, 1) for n in n1D] + [(n, 2) for n in n2D]:  # LatinHypercube, montecarlo.dart:305-325
-                v = np.zeros((n, dims), f32)
-                for j in range(n):
-                    for d in range(dims):
-                        v[j, d] = min((j + rng.randomFloat()) * (1.0 / n), ONE_MINUS_EPSILON)
-                for d in range(dims):
-                    for j in range(n):
-                        other = j + rng.randomUint() % (n - j)
-                        v[j, d], v[other, d] = v[other, d], v[j, d]
-                vec[i, o:o + n * dims] = v.reshape(-1)
-                o += n * dims
+            vec[i, 5:] = _latin_hypercube_slots(n1D, n2D, sample_rng(i))
         return vec
 
     def slot_counts(self, renderer, scene):
@@ -1263,12 +1277,7 @@ class StratifiedSampler:
             vecs.append(v)
             if needs_tail:
                 tails += [list(li_draws(int(px), int(py), v[i], rng)) for i in range(len(v))]
-        tail = cnt = None
-        if needs_tail:
-            cnt = np.array([len(t) for t in tails], np.int32)
-            tail = np.zeros((len(tails), max(1, int(cnt.max()))), np.float64)
-            for i, t in enumerate(tails):
-                tail[i, :len(t)] = t
+        tail, cnt = _pack_tails(tails) if needs_tail else (None, None)
         return HostBufferSampler(self.camera, self.samplesPerPixel, pixels, np.concatenate(vecs), tail, cnt)
 
 
@@ -1381,18 +1390,7 @@ class HaltonSampler:
         px, py = math.floor(imageX), math.floor(imageY)
         vec = np.zeros(5 + sum(n1D) + 2 * sum(n2D), f32)
         vec[0:5] = (imageX - px, imageY - py, RadicalInverse(k + 1, 5), RadicalInverse(k + 1, 7), RadicalInverse(k + 1, 11))
-        o = 5
-        for n, dims in [(n, 1) for n in n1D] + [(n, 2) for n in n2D]:  # LatinHypercube, montecarlo.dart:305-325
-            v = np.zeros((n, dims), f32)
-            for j in range(n):
-                for d in range(dims):
-                    v[j, d] = min((j + rng.randomFloat()) * (1.0 / n), ONE_MINUS_EPSILON)
-            for d in range(dims):
-                for j in range(n):
-                    other = j + rng.randomUint() % (n - j)
-                    v[j, d], v[other, d] = v[other, d], v[j, d]
-            vec[o:o + n * dims] = v.reshape(-1)
-            o += n * dims
+        vec[5:] = _latin_hypercube_slots(n1D, n2D, rng)
         return (px, py), vec
 
     def serial_samples(self, renderer, scene, li_draws=None):
@@ -1412,12 +1410,7 @@ class HaltonSampler:
             vecs.append(v)
             if needs_tail:
                 tails.append(list(li_draws(xy[0], xy[1], v, rng)))
-        tail = cnt = None
-        if needs_tail:
-            cnt = np.array([len(t) for t in tails], np.int32)
-            tail = np.zeros((len(tails), max(1, int(cnt.max()) if len(cnt) else 1)), np.float64)
-            for i, t in enumerate(tails):
-                tail[i, :len(t)] = t
+        tail, cnt = _pack_tails(tails) if needs_tail else (None, None)
         nf = 5 + sum(n1D) + 2 * sum(n2D)
         return HostBufferSampler(self.camera, 1, np.array(pixels, np.int32).reshape(-1, 2), np.array(vecs, np.float32).reshape(-1, nf), tail, cnt)
 

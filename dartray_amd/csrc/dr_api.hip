@@ -199,11 +199,10 @@ void enumeratePixels(const RenderParams& rp, const DrRenderDesc* rd, std::vector
 namespace dr_host {
 
 // The two LayoutOps tables, defined once: layout_state_words() is evaluated here and nowhere else.
-const LayoutOps kLayout64 = {&launch_trace, &launch_trace_coherent, &trace_kernel_id, &launch_gen_samples, &launch_gen_strat, &launch_export_samples, &launch_adaptive_decide, &launch_halton_select, &launch_gen_halton, &launch_mark_alive, &launch_sum_alive, &launch_transpose_samples, &launch_raygen, &launch_shade_path,
-                             &launch_env, &launch_shade_direct, &launch_shade_spec, &launch_film, layout_state_words()};
-const LayoutOps kLayoutSp4 = {&sp4::launch_trace, &sp4::launch_trace_coherent, &sp4::trace_kernel_id, &sp4::launch_gen_samples, &sp4::launch_gen_strat, &sp4::launch_export_samples, &sp4::launch_adaptive_decide, &sp4::launch_halton_select, &sp4::launch_gen_halton, &sp4::launch_mark_alive, &sp4::launch_sum_alive, &sp4::launch_transpose_samples, &sp4::launch_raygen,
-                              &sp4::launch_shade_path, &sp4::launch_env, &sp4::launch_shade_direct, &sp4::launch_shade_spec,
-                              &sp4::launch_film, sp4::layout_state_words()};
+#define DR_LAYOUT_64(member, fn) &fn,
+#define DR_LAYOUT_SP4(member, fn) &sp4::fn,
+const LayoutOps kLayout64 = {DR_LAYOUT_LAUNCHERS(DR_LAYOUT_64) layout_state_words()};
+const LayoutOps kLayoutSp4 = {DR_LAYOUT_LAUNCHERS(DR_LAYOUT_SP4) sp4::layout_state_words()};
 
 BatchState makeState(Workspace& w, const SampleForm& sf, const int2* pix, uint32_t nslots, bool useTail, int stateWords) {
   BatchState st;
@@ -232,9 +231,12 @@ BatchState makeState(Workspace& w, const SampleForm& sf, const int2* pix, uint32
 }
 
 void RenderPlan::genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const {
-  if (halton) L->gen_halton(rpB, st, haltonWin, sc->ws.haltonIdx.p, sc->ws.pix.p, sc->ws.haltonKeyPix.p, s);
-  else if (strat) L->gen_strat(rpB, st, np, stratX, s);
-  else L->gen_samples(rpB, st, np, s);
+  switch (sampler) {  // (no default: -Wall names a kind this forgets)
+    case SamplerKind::HostBuffer: break;  // (the caller's vectors: BatchRunner::loadHostSamples)
+    case SamplerKind::LowDiscrepancy: case SamplerKind::Adaptive: L->gen_samples(rpB, st, np, s); break;
+    case SamplerKind::Stratified: L->gen_strat(rpB, st, np, strat.x, s); break;
+    case SamplerKind::Halton: L->gen_halton(rpB, st, halton.win, sc->ws.halton.idx.p, sc->ws.pix.p, sc->ws.halton.keyPix.p, s); break;
+  }
 }
 
 }  // namespace dr_host
@@ -352,10 +354,7 @@ int dr_scene_get_pairs(const DrScene* sc, void* out, uint64_t cap_bytes, uint64_
 
 int dr_scene_workspace_bytes(const DrScene* sc, uint64_t* bytes_out) {
   if (!sc || !bytes_out) return fail(DR_ERR_INVALID, "null argument");
-  const Workspace& w = sc->ws;
-  *bytes_out = w.tiles.bytes() + w.scr.bytes() + w.genState.bytes() + w.tail.bytes() + w.tailOff.bytes() + w.activeA.bytes() + w.activeB.bytes() +
-               w.closestQ.bytes() + w.anyQ.bytes() + w.counters.bytes() + w.spill.bytes() + w.envQ.bytes() + w.alive.bytes() + w.roundA.bytes() +
-               w.roundB.bytes() + w.specFrames.bytes() + w.specSp.bytes() + w.pix.bytes() + w.adaptList.bytes() + w.adaptCount.bytes() + w.haltonIdx.bytes() + w.haltonKeyPix.bytes() + w.haltonBlk.bytes() + w.filterTable.bytes() + w.aosSamples.bytes();
+  *bytes_out = sc->ws.bytes();
   return DR_OK;
 }
 
@@ -417,33 +416,47 @@ int dr_intersect(DrScene* sc, const DrRay* rays, int64_t n, DrHit* out, int32_t 
 // ===========================================================================
 namespace {
 
-// What the call asks for, checked, as RenderParams + the flags every later unit reads; which pixels it traces.
+// What the call asks for, checked, as RenderParams + the facts every later unit reads; which pixels it traces.  Callable without a film (the two
+// sample dumps plan this way).  Every check runs where it always ran, so that of two broken rules the same one wins.
 int planRender(RenderPlan& P) {
   DrScene* sc = P.sc;
   const DrRenderDesc* rd = P.rd;
-  P.adaptivePass = rd->sampler_mode == DR_SAMPLER_ADAPTIVE ? 1 : 0;
-  if (P.adaptivePass) {
-    // AdaptiveSampler (adaptive_sampler.dart:53-83) after its own normalisation, which the host does: maxSamples in spp, minSamples in
-    // strat_xsamples.  Powers of two: both passes are LDPixelSample, and the slot -> pixel maps of the batches are shifts.
-    const int mn = rd->strat_xsamples, mx = rd->spp;
-    if (mn < 2 || mx > 4096 || mn >= mx || (mn & (mn - 1)) != 0 || (mx & (mx - 1)) != 0)
-      return fail(DR_ERR_INVALID, "adaptive sampler: minSamples (strat_xsamples) and maxSamples (spp) must be powers of two with 2 <= minSamples < maxSamples <= 4096");
-    P.adMin = mn;
-    P.adMax = mx;
+  // ---- the sampler mode: its kind, its own rules, the samples per pixel of this plan ----
+  static const SamplerKind kinds[] = {SamplerKind::HostBuffer, SamplerKind::LowDiscrepancy, SamplerKind::Stratified, SamplerKind::Stratified, SamplerKind::Adaptive, SamplerKind::Halton};
+  static_assert(DR_SAMPLER_HOST_BUFFER == 0 && DR_SAMPLER_COUNTER == 1 && DR_SAMPLER_STRATIFIED == 2 && DR_SAMPLER_STRATIFIED_NOJITTER == 3 && DR_SAMPLER_ADAPTIVE == 4 && DR_SAMPLER_HALTON == 5, "kinds[] is indexed by sampler_mode");
+  const bool knownMode = rd->sampler_mode >= 0 && rd->sampler_mode <= DR_SAMPLER_HALTON;
+  P.sampler = knownMode ? kinds[rd->sampler_mode] : SamplerKind::LowDiscrepancy;  // (an unknown mode is refused where the pixel source is chosen, as ever)
+  P.traits = &kSamplerTraits[(int)P.sampler];
+  P.spp = rd->spp;
+  switch (P.sampler) {  // (no default: -Wall names a kind this forgets)
+    case SamplerKind::HostBuffer: case SamplerKind::LowDiscrepancy: break;
+    case SamplerKind::Stratified:  // StratifiedSampler (stratified_sampler.dart:39-54): xs * ys samples per pixel; refused under its own name
+      if (P.spp <= 0 || (P.spp & (P.spp - 1)) != 0 || P.spp > 4096)
+        return fail(DR_ERR_UNSUPPORTED, "stratified sampler: xsamples * ysamples must be a power of two, at most 4096 (the slot -> pixel maps of the batches are shifts)");
+      break;
+    case SamplerKind::Adaptive: {
+      // AdaptiveSampler (adaptive_sampler.dart:53-83) after its own normalisation, which the host does: maxSamples in spp, minSamples in
+      // strat_xsamples.  Powers of two: both passes are LDPixelSample, and the slot -> pixel maps of the batches are shifts.
+      const int mn = rd->strat_xsamples, mx = rd->spp;
+      if (mn < 2 || mx > 4096 || mn >= mx || (mn & (mn - 1)) != 0 || (mx & (mx - 1)) != 0)
+        return fail(DR_ERR_INVALID, "adaptive sampler: minSamples (strat_xsamples) and maxSamples (spp) must be powers of two with 2 <= minSamples < maxSamples <= 4096");
+      P.adaptive.pass = 1;
+      P.spp = P.adaptive.min = mn;  // (this plan is the first pass)
+      P.adaptive.max = mx;
+      break;
+    }
+    case SamplerKind::Halton:
+      // HaltonSampler (halton_sampler.dart:31-48): any positive pixelsamples; ONE sequence per task over the task's own window, so the
+      // tile round-robin -- a share of the pixels -- has nothing to deal out
+      if (rd->spp < 1) return fail(DR_ERR_INVALID, "halton sampler: pixelsamples (spp) must be at least 1");
+      if (rd->tile_count > 1) return fail(DR_ERR_UNSUPPORTED, "halton sampler: tile_count > 1 (the tile round-robin deals out pixels; a task's Halton sequence is not bound to pixels: split by task_num / task_count)");
+      P.spp = 1;  // (one slot per accepted sample)
+      break;
   }
-  P.halton = rd->sampler_mode == DR_SAMPLER_HALTON;
-  if (P.halton) {
-    // HaltonSampler (halton_sampler.dart:31-48): any positive pixelsamples; ONE sequence per task over the task's own window, so the
-    // tile round-robin -- a share of the pixels -- has nothing to deal out
-    if (rd->spp < 1) return fail(DR_ERR_INVALID, "halton sampler: pixelsamples (spp) must be at least 1");
-    if (rd->tile_count > 1) return fail(DR_ERR_UNSUPPORTED, "halton sampler: tile_count > 1 (the tile round-robin deals out pixels; a task's Halton sequence is not bound to pixels: split by task_num / task_count)");
-  }
-  const int spp = P.spp = P.adaptivePass ? P.adMin : (P.halton ? 1 : rd->spp);  // (adaptive: this plan is the first pass; halton: one slot per accepted sample)
-  P.strat = rd->sampler_mode == DR_SAMPLER_STRATIFIED || rd->sampler_mode == DR_SAMPLER_STRATIFIED_NOJITTER;
-  if (P.strat && (spp <= 0 || (spp & (spp - 1)) != 0 || spp > 4096))
-    return fail(DR_ERR_UNSUPPORTED, "stratified sampler: xsamples * ysamples must be a power of two, at most 4096 (the slot -> pixel maps of the batches are shifts)");
-  if (spp <= 0 || (spp & (spp - 1)) != 0) return fail(DR_ERR_INVALID, "spp must be a power of two (low_discrepancy_sampler.dart:43-49)");
+  const int spp = P.spp;
+  if (P.traits->pow2Spp && (spp <= 0 || (spp & (spp - 1)) != 0)) return fail(DR_ERR_INVALID, "spp must be a power of two (low_discrepancy_sampler.dart:43-49)");
   if (spp > 4096) return fail(DR_ERR_UNSUPPORTED, "spp > 4096 (one pixel's shuffle table of a 16-pixel sampler group would not fit the LDS)");
+  // ---- the integrator, the camera and the film into rp; the state layout; the stages ----
   if (rd->integrator != DR_INTEGRATOR_PATH && rd->integrator != DR_INTEGRATOR_DIRECT_ALL && rd->integrator != DR_INTEGRATOR_DIRECT_ONE)
     return fail(DR_ERR_INVALID, "unknown integrator");
   if (rd->max_depth < 0 || rd->max_depth > 64) return fail(DR_ERR_INVALID, "max_depth out of range");
@@ -461,7 +474,7 @@ int planRender(RenderPlan& P) {
   // DARTRAY_STATE_LAYOUT=64|4 forces one, dr_scene_set_state_layout stores one; renders too small for a pilot keep round 3's
   // rule (plain-triangle scenes under an environment map: sp4).
   const DrOpt layoutEnv = dr_opt("DARTRAY_STATE_LAYOUT");
-  P.layoutKnown = layoutEnv || sc->stateLayout != 0 || rd->integrator != DR_INTEGRATOR_PATH || P.halton;  // (halton: no pilot of its own)
+  P.layoutKnown = layoutEnv || sc->stateLayout != 0 || rd->integrator != DR_INTEGRATOR_PATH || !P.traits->pixelBound;  // (not pixel bound: no pilot)
   const bool sparseLayout = layoutEnv ? layoutEnv.toInt(0) == 4 : (sc->stateLayout ? sc->stateLayout == 4 : P.envStage);
   P.L = sparseLayout ? &kLayoutSp4 : &kLayout64;
   P.maxStateWords = P.layoutKnown ? P.L->stateWords : std::max(kLayout64.stateWords, kLayoutSp4.stateWords);
@@ -479,9 +492,9 @@ int planRender(RenderPlan& P) {
   rp_film(rp, rd->film);
   rp.integrator = rd->integrator;
   rp.maxDepth = rd->max_depth;
-  rp.spp = spp;
+  rp.spp = P.spp;
   rp.sppShift = 0;
-  while ((1 << rp.sppShift) < spp) ++rp.sppShift;
+  while ((1 << rp.sppShift) < P.spp) ++rp.sppShift;
   rp.nLights = (int)sc->d.nlights;
   rp.nFloats = P.direct && !directOne ? sc->dlNFloats : dr_sample_floats(rd->integrator, sc->d.nlights);
   rp.n1D = directOne ? 5 : (P.direct ? sc->dlN1D : 14);
@@ -493,24 +506,7 @@ int planRender(RenderPlan& P) {
   rp.deferredNee = rd->integrator == DR_INTEGRATOR_PATH ? 1 : 0;
   rp.genMask = 0ull;
   rp.genSlowDraws = dr_opt("DARTRAY_GEN_SLOW_DRAWS").set ? 1 : 0;
-  if (P.strat) {
-    // StratifiedSampler (stratified_sampler.dart:39-54): xs * ys samples per pixel.  The slot -> pixel maps of the batch machinery are
-    // shifts, hence the power of two (checked above); roundSize is the identity (:63-65) while the scene's DirectLighting slot layout is
-    // LowDiscrepancySampler's rounded one, so a light's nsamples must be its own rounding.
-    const int xs = rd->strat_xsamples;
-    if (xs <= 0 || spp % xs != 0)
-      return fail(DR_ERR_INVALID, "stratified sampler: strat_xsamples must be positive and divide spp (spp = xsamples * ysamples)");
-    if (rd->integrator == DR_INTEGRATOR_DIRECT_ALL)
-      for (int n : sc->lightNSamples)
-        if (n > 1 && (n & (n - 1)) != 0)
-          return fail(DR_ERR_UNSUPPORTED, "stratified sampler: a light's nsamples must be a power of two (StratifiedSampler.roundSize is the identity, the scene's sample layout is the rounded one)");
-    P.stratX = xs;
-  }
-  if (P.halton && rd->integrator == DR_INTEGRATOR_DIRECT_ALL)  // HaltonSampler.roundSize is the identity as well (halton_sampler.dart:102-104)
-    for (int n : sc->lightNSamples)
-      if (n > 1 && (n & (n - 1)) != 0)
-        return fail(DR_ERR_UNSUPPORTED, "halton sampler: a light's nsamples must be a power of two (HaltonSampler.roundSize is the identity, the scene's sample layout is the rounded one)");
-  if (!P.strat && !P.halton && rd->integrator == DR_INTEGRATOR_PATH && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
+  if (!(P.traits->deviceGenerated && P.traits->floatForm) && rd->integrator == DR_INTEGRATOR_PATH && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
     // What the path kernels read of a pixel sample (dr_kernels.hip: k_raygen, load_shade_in, k_film): the image sample,
     // the lens sample of a thin-lens camera, and per SAMPLE_DEPTH level b <= maxDepth the light number, the light
     // sample (component + position), the BSDF and path directions; the two uComponent slots only where a material has
@@ -522,19 +518,30 @@ int planRender(RenderPlan& P) {
       if (general) m |= 12ull << (3 + 4 * b);
       m |= 7ull << (3 + rp.n1D + 3 * b);
     }
-    rp.genMask = m;
+    rp.genMask = m;  // (only the LD sampler reads it: a device sampler that writes floats leaves no block out)
   }
-  rp.samplerMode = P.adaptivePass ? DR_SAMPLER_COUNTER : rd->sampler_mode;  // (both adaptive passes are the LD sampler's keyed streams)
-  if (P.adaptivePass && rp.blocks && P.adMax > 1024)
-    return fail(DR_ERR_UNSUPPORTED, "adaptive sampler: maxSamples > 1024 with LD blocks of several entries per sample (DirectLighting with nsamples > 1): the float-form sampler's table exceeds the LDS");
+  rp.samplerMode = P.sampler == SamplerKind::Adaptive ? DR_SAMPLER_COUNTER : rd->sampler_mode;  // (both adaptive passes are the LD sampler's keyed streams)
   rp.seed = (uint64_t)rd->seed;
   const int perNee = rp.nLights > 0 ? 7 : 0;
   P.needTail = rd->integrator == DR_INTEGRATOR_PATH && rd->max_depth >= 3 ? (rd->max_depth - 2) * (perNee + 3) + std::max(0, rd->max_depth - 3) : 0;
   rp.maxTail = rd->max_tail;
-
-  // ---- which pixels does this call trace? ----
-  P.hostBuf = rd->sampler_mode == DR_SAMPLER_HOST_BUFFER;
-  if (P.hostBuf) {
+  P.sgrid = g_numCU;  // the shade launchers size their grid per CU (DR_SHADE_GRID), grid-stride over the active list
+  P.nStages = rd->integrator == DR_INTEGRATOR_PATH ? rd->max_depth + 2 : rp.nDirectStages + 1;
+  // ---- the mode's rules that have always run behind the integrator's, max_depth's and the camera's refusals above (strat_xsamples reads only spp, but a descriptor
+  // that also names an unknown integrator keeps that refusal); which pixels: the caller's list, the task's / tile share's, or -- not pixel bound -- a window ----
+  if (P.sampler == SamplerKind::Stratified) {
+    P.strat.x = rd->strat_xsamples;
+    if (P.strat.x <= 0 || spp % P.strat.x != 0)
+      return fail(DR_ERR_INVALID, "stratified sampler: strat_xsamples must be positive and divide spp (spp = xsamples * ysamples)");
+  }
+  // roundSize is the identity (stratified_sampler.dart:63-65, halton_sampler.dart:102-104) while the scene's DirectLighting slot layout is
+  // LowDiscrepancySampler's rounded one, so a light's nsamples must be its own rounding
+  if (P.traits->identityRoundSize && rd->integrator == DR_INTEGRATOR_DIRECT_ALL)
+    for (int n : sc->lightNSamples)
+      if (n > 1 && (n & (n - 1)) != 0) return fail(DR_ERR_UNSUPPORTED, P.traits->identityRoundSize);
+  if (P.sampler == SamplerKind::Adaptive && rp.blocks && P.adaptive.max > 1024)
+    return fail(DR_ERR_UNSUPPORTED, "adaptive sampler: maxSamples > 1024 with LD blocks of several entries per sample (DirectLighting with nsamples > 1): the float-form sampler's table exceeds the LDS");
+  if (P.sampler == SamplerKind::HostBuffer) {
     if (rd->nsamples <= 0 || rd->nsamples % spp != 0 || !rd->pixel_xy || !rd->sample_vec)
       return fail(DR_ERR_INVALID, "host-buffer sampler: nsamples must be a positive multiple of spp with pixel_xy and sample_vec set");
     if (rd->sample_stride < rp.nFloats) return fail(DR_ERR_INVALID, "sample_stride smaller than the sample vector");
@@ -546,16 +553,17 @@ int planRender(RenderPlan& P) {
     const int64_t np = rd->nsamples / spp;
     P.pixels.resize(np);
     for (int64_t i = 0; i < np; ++i) P.pixels[i] = make_int2(rd->pixel_xy[2 * i], rd->pixel_xy[2 * i + 1]);
-  } else if (rd->sampler_mode == DR_SAMPLER_COUNTER || P.strat || P.adaptivePass) {
+  } else if (P.traits->pixelBound) {
+    if (!knownMode) return fail(DR_ERR_INVALID, "unknown sampler mode");
     enumeratePixels(rp, rd, P.pixels);
-  } else if (P.halton) {
-    // the task's window as the reference hands it to the sampler (GetSubWindow's extents as they are: see enumeratePixels)
+  } else {
+    // Halton: the task's window as the reference hands it to the sampler (GetSubWindow's extents as they are: see enumeratePixels)
     int ext[4];
     getSubWindow(rp.extW, rp.extH, rd->task_num, std::max(1, rd->task_count), ext);
     const int w = ext[1] - ext[0], h = ext[3] - ext[2], delta = std::max(w, h);
     P.pixels.clear();
     const int32_t win[5] = {ext[0], ext[2], ext[0] + w - 1, ext[2] + h - 1, delta};
-    memcpy(P.haltonWin, win, sizeof(win));
+    memcpy(P.halton.win, win, sizeof(win));
     const uint64_t wanted = w > 0 && h > 0 ? (uint64_t)rd->spp * (uint64_t)delta * (uint64_t)delta : 0ull;  // wantedSamples (halton_sampler.dart:35-36)
     if (wanted >= (1ull << 53)) return fail(DR_ERR_UNSUPPORTED, "halton sampler: pixelsamples * max(width, height)^2 must stay below 2^53 (RadicalInverse takes the index through a double)");
     // (the key pixel of index k is (extX0 + k % extW, extY0 + k / extW): k_gen_halton)
@@ -565,17 +573,13 @@ int planRender(RenderPlan& P) {
     // film_samples, as for the other modes: the window's pixels that the film holds x pixelsamples (what the sequence aims at)
     const int64_t fw = std::min(ext[1], rp.left + rp.width) - std::max(ext[0], rp.left), fh = std::min(ext[3], rp.top + rp.height) - std::max(ext[2], rp.top);
     P.filmSamples = fw > 0 && fh > 0 ? (uint64_t)fw * (uint64_t)fh * (uint64_t)rd->spp : 0ull;
-  } else {
-    return fail(DR_ERR_INVALID, "unknown sampler mode");
   }
-  if (!P.halton) {
+  if (P.traits->pixelBound) {
     P.npixTotal = P.pixels.size();
     P.filmSamples = 0;
     for (const int2& p : P.pixels)
       if (p.x >= rp.left && p.x < rp.left + rp.width && p.y >= rp.top && p.y < rp.top + rp.height) P.filmSamples += spp;
   }
-  P.sgrid = g_numCU;  // the shade launchers size their grid per CU (DR_SHADE_GRID), grid-stride over the active list
-  P.nStages = rd->integrator == DR_INTEGRATOR_PATH ? rd->max_depth + 2 : rp.nDirectStages + 1;
   if (P.nStages > CounterLayout::maxStages()) return fail(DR_ERR_UNSUPPORTED, "too many stages");
   return DR_OK;
 }
@@ -589,15 +593,16 @@ int planBatches(RenderPlan& P) {
   // Sample vectors: the on-device LD sampler stores permuted indices + scrambles (compact form) whenever every LD block
   // has one entry per pixel sample; host buffers and multi-entry blocks (DirectLighting with nsamples > 1) use floats.
   SampleForm& sf = P.sf;
-  sf.compact = !P.hostBuf && !P.strat && !P.halton && rp.blocks == nullptr;  // (the stratified and Halton samplers' values are no function of an LD index: floats)
-  if (!sf.compact && !P.hostBuf && !P.strat && spp > 1024)
+  sf.compact = !P.traits->floatForm && rp.blocks == nullptr;  // (the stratified and Halton samplers' values are no function of an LD index: floats)
+  if (!P.traits->floatForm && !sf.compact && spp > 1024)  // (the LD sampler writing floats)
     return fail(DR_ERR_UNSUPPORTED, "spp > 1024 with LD blocks of several entries per sample (DirectLighting with nsamples > 1): the float-form sampler's table exceeds the LDS");
   sf.nFloats = rp.nFloats;
+  // (not sampler_block_count(rp) of dr_sampler_lhs.h, which answers rp.nBlocks under rp.blocks: this counts the field layout's slots whatever rp.blocks says)
   sf.nBlocks = 3 + rp.n1D + (rp.nFloats - 5 - rp.n1D) / 2;
   sf.idxShift = spp > 256 ? 1 : 0;
   // what the workspace's sample region is sized for: this form; adaptive: the second pass's (same blocks, wider indices above 256 spp)
   P.wsSf = sf;
-  if (P.adaptivePass) P.wsSf.idxShift = P.adMax > 256 ? 1 : 0;
+  if (P.sampler == SamplerKind::Adaptive) P.wsSf.idxShift = P.adaptive.max > 256 ? 1 : 0;
   // Camera samples in flight per batch.  The throughput end is one batch per image (2^28 slots: C2's whole sampler window, 64 GB of a
   // 288 GB MI355X); a scene's FIRST big render -- all a one-shot host ever does (Renderer.render once per task, dartray.dart:574) --
   // stays at 2^27 (C2: three batches, 21 GB, whose hipMalloc does not wait for the driver to scrub 64 GB: profiles/r05_alloc_probe.txt)
@@ -609,10 +614,10 @@ int planBatches(RenderPlan& P) {
     // path state per camera sample: 164 B of ray / hit / NEE state, 20 B of queues and the sample vector (24 B of permuted
     // indices in the compact form, 4 B per float otherwise; + the RNG tail in host-buffer mode).  On a device with less free
     // memory the batch shrinks instead of failing (results do not depend on the batch size).
-    const uint64_t tailPerSlot = !(P.hostBuf && P.needTail > 0) ? 0ull
+    const uint64_t tailPerSlot = !(!P.traits->deviceGenerated && P.needTail > 0) ? 0ull
                                  : (P.packedTail ? 16ull + 8ull * ((rd->tail_offsets[rd->nsamples] - rd->tail_offsets[0]) / (uint64_t)rd->nsamples + 1ull)
                                                  : (uint64_t)rd->max_tail * 8);
-    const uint64_t perSlot = (uint64_t)P.maxStateWords * 4 + (uint64_t)(P.wsSf.svWords() + 15) / 16 + 20 + tailPerSlot + (P.hostBuf ? (uint64_t)rd->sample_stride * 4 : 0) +
+    const uint64_t perSlot = (uint64_t)P.maxStateWords * 4 + (uint64_t)(P.wsSf.svWords() + 15) / 16 + 20 + tailPerSlot + (!P.traits->deviceGenerated ? (uint64_t)rd->sample_stride * 4 : 0) +
                              (sf.compact ? (uint64_t)(16 * sf.nBlocks + spp - 1) / spp : 0) +  // scramble words + generator states, per (block, pixel)
                              (P.dlSpec ? (uint64_t)std::max(1, rd->max_depth) * sizeof(SpecFrame) + 12 : 0);
     size_t freeB = 0, totalB = 0;
@@ -627,21 +632,21 @@ int planBatches(RenderPlan& P) {
   // (the sampler window of a 1024 x 1024 film is 1025 x 1025 pixels -- 2^20 + 2049).
   const uint64_t pixCapBatch = std::max<uint64_t>(1, maxSlots / spp);
   P.nBatches = (P.npixTotal + pixCapBatch - 1) / pixCapBatch;
-  if (!P.halton && P.nBatches > 1 && P.npixTotal <= pixCapBatch + pixCapBatch / 4) P.nBatches = 1;  // (halton: a batch's range is its slot capacity at most)
+  if (P.traits->pixelBound && P.nBatches > 1 && P.npixTotal <= pixCapBatch + pixCapBatch / 4) P.nBatches = 1;  // (else: a batch's range is its slot capacity at most)
   P.pixPerBatch = (uint32_t)((P.npixTotal + P.nBatches - 1) / P.nBatches);
   P.cap = P.pixPerBatch * (uint32_t)spp;
   P.wsCap = P.cap;
   P.wsPix = P.pixPerBatch;
-  if (P.adaptivePass) {
+  if (P.sampler == SamplerKind::Adaptive) {
     // The second pass runs in the workspace of the first: how many pixels are flagged is only known once the first pass has run, and
     // a workspace sized for the worst case (every pixel at maxSamples) would be max / min times the first pass's.  Its batches hold
     // as many slots as a first-pass batch -- or 2^22 where those are smaller, so that a small image's flagged pixels still go as a
     // few launches -- and never more than every pixel of the render at maxSamples, nor less than one pixel.
-    const uint64_t worst = (uint64_t)P.npixTotal * (uint64_t)P.adMax;
-    const uint64_t slots2 = std::max<uint64_t>((uint64_t)P.adMax, std::min<uint64_t>(worst, std::max<uint64_t>(P.cap, std::min<uint64_t>(1ull << 22, maxSlots))));
-    P.adPixCap = (uint32_t)(slots2 / (uint64_t)P.adMax);
-    P.wsCap = std::max(P.cap, P.adPixCap * (uint32_t)P.adMax);
-    P.wsPix = std::max(P.pixPerBatch, P.adPixCap);
+    const uint64_t worst = (uint64_t)P.npixTotal * (uint64_t)P.adaptive.max;
+    const uint64_t slots2 = std::max<uint64_t>((uint64_t)P.adaptive.max, std::min<uint64_t>(worst, std::max<uint64_t>(P.cap, std::min<uint64_t>(1ull << 22, maxSlots))));
+    P.adaptive.pixCap = (uint32_t)(slots2 / (uint64_t)P.adaptive.max);
+    P.wsCap = std::max(P.cap, P.adaptive.pixCap * (uint32_t)P.adaptive.max);
+    P.wsPix = std::max(P.pixPerBatch, P.adaptive.pixCap);
   }
   return DR_OK;
 }
@@ -651,22 +656,22 @@ int planBatches(RenderPlan& P) {
 bool lazyGenFor(const RenderPlan& P);
 RenderPlan secondPass(const RenderPlan& P, uint32_t nFlagged) {
   RenderPlan Q = P;
-  Q.adaptivePass = 2;
-  Q.spp = Q.rp.spp = P.adMax;
+  Q.adaptive.pass = 2;
+  Q.spp = Q.rp.spp = P.adaptive.max;
   Q.rp.sppShift = 0;
   while ((1 << Q.rp.sppShift) < Q.spp) ++Q.rp.sppShift;
   Q.sf = P.wsSf;
   Q.lazyGen = lazyGenFor(Q);
   Q.calibrateTrace = Q.measureLayout = false;
   Q.npixTotal = nFlagged;
-  Q.nBatches = ((uint64_t)nFlagged + P.adPixCap - 1) / P.adPixCap;
+  Q.nBatches = ((uint64_t)nFlagged + P.adaptive.pixCap - 1) / P.adaptive.pixCap;
   Q.pixPerBatch = (uint32_t)(((uint64_t)nFlagged + Q.nBatches - 1) / Q.nBatches);
   Q.cap = Q.pixPerBatch * (uint32_t)Q.spp;
   return Q;
 }
 
 bool lazyGenFor(const RenderPlan& P) {
-  return !P.hostBuf && P.sf.compact && P.rp.genMask != 0ull && P.rd->integrator == DR_INTEGRATOR_PATH && P.coherentCamera && !P.sc->d.nquads && P.spp >= 64 &&
+  return P.sf.compact && P.rp.genMask != 0ull && P.rd->integrator == DR_INTEGRATOR_PATH && P.coherentCamera && !P.sc->d.nquads && P.spp >= 64 &&
          !dr_opt("DARTRAY_LAZY_GEN").isZero();
 }
 
@@ -677,7 +682,7 @@ int prepareRender(RenderPlan& P) {
   const int spp = P.spp;
   const auto tAlloc0 = std::chrono::steady_clock::now();
   const uint32_t capBefore = sc->ws.cap;
-  int rc = allocWorkspace(sc, sc->ws, P.wsCap, P.wsSf, P.wsPix, rd->max_tail, P.hostBuf && P.needTail > 0 && !P.packedTail, P.maxStateWords);
+  int rc = allocWorkspace(sc, sc->ws, P.wsCap, P.wsSf, P.wsPix, rd->max_tail, !P.traits->deviceGenerated && P.needTail > 0 && !P.packedTail, P.maxStateWords);
   if (rc) return rc;
   if (dr_opt("DARTRAY_VERBOSE") && sc->ws.cap != capBefore) {
     (void)hipDeviceSynchronize();
@@ -696,7 +701,7 @@ int prepareRender(RenderPlan& P) {
   rc = ensureSpill(sc, sc->ws, P.tgrid);
   if (rc) return rc;
   // the camera rays (a tile = 64 samples of one pixel) through the wave-coherent kernel k_trace_pk (DARTRAY_COHERENT_CAMERA=0: k_trace & co.)
-  P.coherentCamera = !dr_opt("DARTRAY_COHERENT_CAMERA").isZero() && !P.dlSpec && !P.halton;  // (halton: a tile's slots are samples of 64 pixels)
+  P.coherentCamera = !dr_opt("DARTRAY_COHERENT_CAMERA").isZero() && !P.dlSpec && P.traits->pixelBound;  // (else: a tile's slots are samples of 64 pixels)
   // lazy sample generation (DARTRAY_LAZY_GEN=0: every block for every pixel up front): needs the device sampler's compact form, the keyed
   // per-(pixel, block) streams (a block that is left out disturbs no other) and k_trace_pk's marks of the camera rays that hit
   P.lazyGen = lazyGenFor(P);
@@ -712,7 +717,7 @@ int prepareRender(RenderPlan& P) {
   // on the choice; dr_scene_set_trace_kernels / DARTRAY_TRACE_IMPL fix it (an N-rank host measures on rank 0 and hands the choice on).
   const DrOpt pilotOpt = dr_opt("DARTRAY_PILOT");  // 0: never; force: also on renders too small to need one (tests)
   const bool bigJob = (sc->d.nnodes >= (1u << 20) && (uint64_t)P.npixTotal * spp >= (1ull << 25)) || pilotOpt.is("force");
-  const bool pilotOk = !pilotOpt.is("0") && !P.hostBuf && !P.dlSpec && !P.halton && bigJob && P.npixTotal >= 3 * 64 * 4;
+  const bool pilotOk = !pilotOpt.is("0") && P.traits->deviceGenerated && P.traits->pixelBound && !P.dlSpec && bigJob && P.npixTotal >= 3 * 64 * 4;
   P.calibrateTrace = !sc->traceCalibrated && pilotOk && !dr_opt("DARTRAY_TRACE_IMPL") && sc->d.pairs && !sc->d.nquads;
   P.measureLayout = !P.layoutKnown && pilotOk;
   if (P.measureLayout) P.L = &kLayout64;  // the batch whose stage lists are measured runs in the 64-slot layout
@@ -740,22 +745,41 @@ int prepareRender(RenderPlan& P) {
     ordered.insert(ordered.end(), P.pixels.begin() + totalGroups * 64, P.pixels.end());
     P.pixels.swap(ordered);
   }
-  if (P.halton) {  // the pixel array is a batch's: k_gen_halton writes every slot's anchor pixel
+  if (!P.traits->pixelBound) {  // the pixel array is a batch's: k_gen_halton writes every slot's anchor pixel
     HIP_TRY(sc->ws.pix.alloc(P.cap));
-    HIP_TRY(sc->ws.haltonIdx.alloc(P.cap));
-    HIP_TRY(sc->ws.haltonKeyPix.alloc(P.cap));
-    HIP_TRY(sc->ws.haltonBlk.alloc((size_t)(P.cap + 255u) / 256u + 1));
+    HIP_TRY(sc->ws.halton.alloc(P.cap));
   } else {
     HIP_TRY(sc->ws.pix.alloc(P.npixTotal));
     HIP_TRY(hipMemcpyAsync(sc->ws.pix.p, P.pixels.data(), P.npixTotal * sizeof(int2), hipMemcpyHostToDevice, P.s));
   }
-  if (P.adaptivePass) {  // the list of flagged pixels: every pixel of the render at most
+  if (P.sampler == SamplerKind::Adaptive) {  // the list of flagged pixels: every pixel of the render at most
     HIP_TRY(sc->ws.adaptList.alloc(P.npixTotal));
     HIP_TRY(sc->ws.adaptCount.alloc(2));
     HIP_TRY(hipMemsetAsync(sc->ws.adaptCount.p, 0, 2 * sizeof(uint32_t), P.s));
   }
   HIP_TRY(hipMemcpyAsync(sc->ws.filterTable.p, rd->film.filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, P.s));
   HIP_TRY(hipStreamSynchronize(P.s));  // (the copies read host memory the caller and this plan own)
+  return DR_OK;
+}
+
+// What the two sample dumps share.  The plan of a render of these pixels / indices -- the same sample form, batches and launches -- its workspace,
+// and the staging rows of a batch, [P.cap][stride] floats, zeroed (the words of a row behind the vector stay zero).
+int prepareDump(RenderPlan& P, DevBuf<float>& aos, int stride) {
+  int rc = planBatches(P);
+  if (!rc) rc = allocWorkspace(P.sc, P.sc->ws, P.cap, P.sf, P.pixPerBatch, P.rd->max_tail, false, P.maxStateWords);
+  if (rc) return rc;
+  HIP_TRY(aos.alloc((size_t)P.cap * stride));
+  HIP_TRY(hipMemsetAsync(aos.p, 0, (size_t)P.cap * stride * sizeof(float), P.s));
+  return DR_OK;
+}
+
+// One batch's vectors to the caller: the sampler's launches for np entries of pix (nslots slots), the export, the copy to out.  The caller waits for the stream.
+int dumpBatch(const RenderPlan& P, const int2* pix, uint32_t np, uint32_t nslots, float* aos, int stride, float* out) {
+  const BatchState st = makeState(P.sc->ws, P.sf, pix, nslots, false, P.L->stateWords);
+  P.genSamples(P.rp, st, np);
+  P.L->export_samples(P.rp, st, aos, stride, P.s);
+  HIP_TRY(hipGetLastError());  // (a launch that could not start)
+  HIP_TRY(hipMemcpyAsync(out, aos, (size_t)nslots * stride * sizeof(float), hipMemcpyDeviceToHost, P.s));
   return DR_OK;
 }
 
@@ -799,14 +823,14 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
     if (rc) return rc;
   }
   uint64_t cameraSamples = (uint64_t)P.npixTotal * P.spp, nBatches = P.nBatches;
-  if (P.halton) {  // one host wait per batch: how many indices of its range the window accepted
+  if (P.sampler == SamplerKind::Halton) {  // one host wait per batch: how many indices of its range the window accepted
     rc = runHaltonBatches(P, &cameraSamples);
   } else {  // (a calibration set that was skipped left its pixels to the ordinary batches)
     rc = runBatches(P, sc->ws.pix.p, (size_t)pilot.setsRun * P.calibPix);
   }
   if (rc) return rc;
   bool lazy2 = false;
-  if (P.adaptivePass) {
+  if (P.sampler == SamplerKind::Adaptive) {
     // the one host round trip of the mode: how many pixels the first pass flagged (and how many of them the film holds)
     uint32_t counts[2] = {0u, 0u};
     HIP_TRY(hipMemcpyAsync(counts, sc->ws.adaptCount.p, sizeof(counts), hipMemcpyDeviceToHost, P.s));
@@ -880,27 +904,19 @@ int dr_generate_samples(DrScene* sc, const DrRenderDesc* rd, const int32_t* pixe
   if (rc) return rc;
   if (stride < P.rp.nFloats) return fail(DR_ERR_INVALID, "dr_generate_samples: stride smaller than the sample vector");
   if (npix * (uint64_t)P.spp >= (1ull << 31)) return fail(DR_ERR_UNSUPPORTED, "dr_generate_samples: more than 2^31 samples in one call");
-  // the plan of a render of these pixels: the same sample form, batches and launches (launch_gen_samples), every LD block produced
-  P.rp.genMask = 0ull;
+  P.rp.genMask = 0ull;  // (every LD block produced)
   P.pixels.resize(npix);
   for (uint64_t i = 0; i < npix; ++i) P.pixels[i] = make_int2(pixel_xy[2 * i], pixel_xy[2 * i + 1]);
   P.npixTotal = P.pixels.size();
-  rc = planBatches(P);
-  if (rc) return rc;
-  rc = allocWorkspace(sc, sc->ws, P.cap, P.sf, P.pixPerBatch, rd->max_tail, false, P.maxStateWords);
+  DevBuf<float> aos;
+  rc = prepareDump(P, aos, stride);
   if (rc) return rc;
   HIP_TRY(sc->ws.pix.alloc(P.npixTotal));
   HIP_TRY(hipMemcpyAsync(sc->ws.pix.p, P.pixels.data(), P.npixTotal * sizeof(int2), hipMemcpyHostToDevice, P.s));
-  DevBuf<float> aos;
-  HIP_TRY(aos.alloc((size_t)P.cap * stride));
-  HIP_TRY(hipMemsetAsync(aos.p, 0, (size_t)P.cap * stride * sizeof(float), P.s));  // (the words of a row behind the vector)
   for (size_t p0 = 0; p0 < P.npixTotal; p0 += P.pixPerBatch) {
-    const uint32_t np = (uint32_t)std::min<size_t>(P.pixPerBatch, P.npixTotal - p0), nslots = np * (uint32_t)P.spp;
-    const BatchState st = makeState(sc->ws, P.sf, sc->ws.pix.p + p0, nslots, false, P.L->stateWords);
-    P.genSamples(P.rp, st, np);
-    P.L->export_samples(P.rp, st, aos.p, stride, P.s);
-    HIP_TRY(hipGetLastError());  // (a launch that could not start)
-    HIP_TRY(hipMemcpyAsync(out + p0 * P.spp * (size_t)stride, aos.p, (size_t)nslots * stride * sizeof(float), hipMemcpyDeviceToHost, P.s));
+    const uint32_t np = (uint32_t)std::min<size_t>(P.pixPerBatch, P.npixTotal - p0);
+    rc = dumpBatch(P, sc->ws.pix.p + p0, np, np * (uint32_t)P.spp, aos.p, stride, out + p0 * P.spp * (size_t)stride);
+    if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(P.s));
   }
   return DR_OK;
@@ -921,20 +937,13 @@ int dr_generate_halton_samples(DrScene* sc, const DrRenderDesc* rd, uint64_t fir
   if (count == 0) return DR_OK;
   if (!k_out || !pixel_xy_out || !out) return fail(DR_ERR_INVALID, "null argument");
   if (stride < P.rp.nFloats) return fail(DR_ERR_INVALID, "dr_generate_halton_samples: stride smaller than the sample vector");
-  // the plan of a render of these indices: the same sample form, ranges and launches
   P.npixTotal = (size_t)count;
-  rc = planBatches(P);
-  if (rc) return rc;
-  rc = allocWorkspace(sc, sc->ws, P.cap, P.sf, P.pixPerBatch, rd->max_tail, false, P.maxStateWords);
+  DevBuf<float> aos;
+  rc = prepareDump(P, aos, stride);
   if (rc) return rc;
   Workspace& w = sc->ws;
   HIP_TRY(w.pix.alloc(P.cap));
-  HIP_TRY(w.haltonIdx.alloc(P.cap));
-  HIP_TRY(w.haltonKeyPix.alloc(P.cap));
-  HIP_TRY(w.haltonBlk.alloc((size_t)(P.cap + 255u) / 256u + 1));
-  DevBuf<float> aos;
-  HIP_TRY(aos.alloc((size_t)P.cap * stride));
-  HIP_TRY(hipMemsetAsync(aos.p, 0, (size_t)P.cap * stride * sizeof(float), P.s));  // (the words of a row behind the vector)
+  HIP_TRY(w.halton.alloc(P.cap));
   uint64_t done = 0;
   for (uint64_t i0 = 0; i0 < count; i0 += P.pixPerBatch) {
     const uint32_t n = (uint32_t)std::min<uint64_t>(P.pixPerBatch, count - i0);
@@ -943,12 +952,9 @@ int dr_generate_halton_samples(DrScene* sc, const DrRenderDesc* rd, uint64_t fir
     if (rc) return rc;
     if (accepted > n) return fail(DR_ERR_HIP, "halton sampler: the selection accepted more indices than its range holds");
     if (accepted == 0) continue;
-    const BatchState st = makeState(w, P.sf, w.pix.p, accepted, false, P.L->stateWords);
-    P.genSamples(P.rp, st, accepted);
-    P.L->export_samples(P.rp, st, aos.p, stride, P.s);
-    HIP_TRY(hipGetLastError());  // (a launch that could not start)
-    HIP_TRY(hipMemcpyAsync(out + done * (size_t)stride, aos.p, (size_t)accepted * stride * sizeof(float), hipMemcpyDeviceToHost, P.s));
-    HIP_TRY(hipMemcpyAsync(k_out + done, w.haltonIdx.p, (size_t)accepted * sizeof(uint64_t), hipMemcpyDeviceToHost, P.s));
+    rc = dumpBatch(P, w.pix.p, accepted, accepted, aos.p, stride, out + done * (size_t)stride);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(k_out + done, w.halton.idx.p, (size_t)accepted * sizeof(uint64_t), hipMemcpyDeviceToHost, P.s));
     HIP_TRY(hipMemcpyAsync(pixel_xy_out + 2 * done, w.pix.p, (size_t)accepted * sizeof(int2), hipMemcpyDeviceToHost, P.s));
     HIP_TRY(hipStreamSynchronize(P.s));
     done += accepted;

@@ -27,7 +27,7 @@ class BatchRunner {
   BatchRunner(RenderPlan& plan, Workspace& ws, const int2* pixDev, size_t firstPixel, uint32_t npixels, PilotTimes* pilotTimes)
       : P(plan), sc(plan.sc), rd(plan.rd), rp(plan.rp), L(*plan.L), w(ws), s(plan.s), p0(firstPixel), np(npixels), nslots(npixels * (uint32_t)plan.spp),
         pilot(pilotTimes), C(ws.counters.p) {
-    st = makeState(w, P.sf, pixDev, nslots, P.hostBuf && P.needTail > 0, L.stateWords);
+    st = makeState(w, P.sf, pixDev, nslots, !P.traits->deviceGenerated && P.needTail > 0, L.stateWords);
     const DrOpt scOpt = dr_opt("DARTRAY_STAGE_COUNTS");
     stageCounts = scOpt.toInt(0) > 0 ? scOpt.toInt(0) : (scOpt.set ? 1 : 0);
     slog.resize(stageCounts ? (size_t)P.nStages + 1 : 0);  // [0] = the camera rays' traversal, [b + 1] = stage b
@@ -74,7 +74,7 @@ class BatchRunner {
   // of the draws inside Li are keyed by the sample's sequence index, not by the pixel it is anchored in
   BatchState shadeState() const {
     BatchState s2 = st;
-    if (P.halton) s2.pix = w.haltonKeyPix.p;
+    if (P.sampler == SamplerKind::Halton) s2.pix = w.halton.keyPix.p;
     return s2;
   }
   uint32_t nGroups = 0;  // lazy generation: 64-pixel groups of this batch
@@ -149,7 +149,7 @@ int BatchRunner::loadHostSamples() {
 int BatchRunner::loadSamples() {
   hipEvent_t evGen = sc->getEvent();
   (void)hipEventRecord(evGen, s);
-  if (P.hostBuf) {
+  if (!P.traits->deviceGenerated) {
     const int rc = loadHostSamples();
     if (rc) return rc;
   } else if (P.lazyGen) {
@@ -339,7 +339,7 @@ int BatchRunner::finish() {
   (void)hipEventRecord(evF, s);
   // adaptive, first pass: the pixels that need maxSamples go to the list and leave this batch's film step (their entries of the
   // render's pixel array, which no later batch reads, move outside every film window)
-  if (P.adaptivePass == 1) L.adaptive_decide(rp, st, np, w.pix.p + p0, w.adaptList.p, w.adaptCount.p, (uint32_t)P.npixTotal, s);
+  if (P.adaptive.pass == 1) L.adaptive_decide(rp, st, np, w.pix.p + p0, w.adaptList.p, w.adaptCount.p, (uint32_t)P.npixTotal, s);
   L.film(rp, st, sc->ws.filterTable.p, np, P.film, s);
   timed(TimedKind::Film, evF);
   sc->stats.batches++;
@@ -348,7 +348,7 @@ int BatchRunner::finish() {
     if (rc) return rc;
   }
   HIP_TRY(hipGetLastError());
-  if (P.hostBuf) HIP_TRY(hipStreamSynchronize(s));  // host buffers of the next batch reuse the staging area
+  if (!P.traits->deviceGenerated) HIP_TRY(hipStreamSynchronize(s));  // host buffers of the next batch reuse the staging area
   return DR_OK;
 }
 
@@ -445,9 +445,9 @@ int runBatches(RenderPlan& plan, const int2* pixDev, size_t firstPixel) {
 
 int haltonSelect(RenderPlan& P, uint64_t k0, uint32_t n, uint32_t* accepted) {
   Workspace& w = P.sc->ws;
-  P.L->halton_select(P.haltonWin, k0, n, w.haltonBlk.p, w.haltonIdx.p, P.s);
+  P.L->halton_select(P.halton.win, k0, n, w.halton.blk.p, w.halton.idx.p, P.s);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(accepted, w.haltonBlk.p + (n + 255u) / 256u, sizeof(uint32_t), hipMemcpyDeviceToHost, P.s));
+  HIP_TRY(hipMemcpyAsync(accepted, w.halton.blk.p + (n + 255u) / 256u, sizeof(uint32_t), hipMemcpyDeviceToHost, P.s));
   HIP_TRY(hipStreamSynchronize(P.s));
   return DR_OK;
 }

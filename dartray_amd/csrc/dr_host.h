@@ -68,11 +68,24 @@ struct Workspace {
   DevBuf<int2> pix;
   DevBuf<int2> adaptList;       // DR_SAMPLER_ADAPTIVE: the raster pixels the first pass flagged (k_adaptive_decide), the second pass's pixel array
   DevBuf<uint32_t> adaptCount;  //   [0] their number, [1] those inside the film window
-  DevBuf<unsigned long long> haltonIdx;  // DR_SAMPLER_HALTON: the sequence index of every slot of the batch,
-  DevBuf<int2> haltonKeyPix;             //   the pixel whose index in the sampler extent is that index: the shade stages' pixel array (k_gen_halton)
-  DevBuf<uint32_t> haltonBlk;            //   the selection's per-workgroup counts / offsets; the word behind them: the batch's slot count
+  struct Halton {  // DR_SAMPLER_HALTON, sized for a batch (beside `pix`, where k_gen_halton writes the slots' anchor pixels)
+    DevBuf<unsigned long long> idx;  // the sequence index of every slot of the batch,
+    DevBuf<int2> keyPix;             //   the pixel whose index in the sampler extent is that index: the shade stages' pixel array (k_gen_halton)
+    DevBuf<uint32_t> blk;            //   the selection's per-workgroup counts / offsets; the word behind them: the batch's slot count
+    hipError_t alloc(uint32_t cap) {
+      hipError_t e = idx.alloc(cap);
+      if (e == hipSuccess) e = keyPix.alloc(cap);
+      return e != hipSuccess ? e : blk.alloc((size_t)(cap + 255u) / 256u + 1);
+    }
+  } halton;
   DevBuf<float> filterTable, aosSamples;
   int spillGrid = 0;
+  size_t bytes() const {  // device memory held right now (dr_scene_workspace_bytes): every buffer above
+    return tiles.bytes() + scr.bytes() + genState.bytes() + tail.bytes() + tailOff.bytes() + activeA.bytes() + activeB.bytes() + closestQ.bytes() +
+           anyQ.bytes() + counters.bytes() + spill.bytes() + envQ.bytes() + alive.bytes() + roundA.bytes() + roundB.bytes() + specFrames.bytes() +
+           specSp.bytes() + pix.bytes() + adaptList.bytes() + adaptCount.bytes() + halton.idx.bytes() + halton.keyPix.bytes() + halton.blk.bytes() +
+           filterTable.bytes() + aosSamples.bytes();
+  }
 };
 
 // Where things live in Workspace::counters -- the only place that knows:
@@ -234,29 +247,37 @@ struct SampleForm {
 // with -DDR_SUB=4 -DDR_NS=sp4).  Dense stage lists are faster in the first; lists that thin out early -- open scenes under an
 // environment map, where most bounce rays leave -- in the second (C5: shade 711 -> 536 ms, MEASUREMENTS.md round 3).
 // A render picks one (dr_render_device); results do not depend on it.
+// X(member, function) for every launcher a layout has its own copy of: LayoutOps' members and both tables (dr_api.hip) are this list
+#define DR_LAYOUT_LAUNCHERS(X)                                                                                                          \
+  X(trace, launch_trace) X(trace_coherent, launch_trace_coherent) X(trace_kernel_id, trace_kernel_id) X(gen_samples, launch_gen_samples)   \
+  X(gen_strat, launch_gen_strat) X(export_samples, launch_export_samples) X(adaptive_decide, launch_adaptive_decide)                       \
+  X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(mark_alive, launch_mark_alive) X(sum_alive, launch_sum_alive) \
+  X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path) X(env, launch_env)              \
+  X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(film, launch_film)
 struct LayoutOps {
-  decltype(&launch_trace) trace;
-  decltype(&launch_trace_coherent) trace_coherent;
-  decltype(&trace_kernel_id) trace_kernel_id;
-  decltype(&launch_gen_samples) gen_samples;
-  decltype(&launch_gen_strat) gen_strat;
-  decltype(&launch_export_samples) export_samples;
-  decltype(&launch_adaptive_decide) adaptive_decide;
-  decltype(&launch_halton_select) halton_select;
-  decltype(&launch_gen_halton) gen_halton;
-  decltype(&launch_mark_alive) mark_alive;
-  decltype(&launch_sum_alive) sum_alive;
-  decltype(&launch_transpose_samples) transpose_samples;
-  decltype(&launch_raygen) raygen;
-  decltype(&launch_shade_path) shade_path;
-  decltype(&launch_env) env;
-  decltype(&launch_shade_direct) shade_direct;
-  decltype(&launch_shade_spec) shade_spec;
-  decltype(&launch_film) film;
+#define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
+  DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
   int stateWords;  // 4-byte words of fixed path state per slot in this layout (a tile is 64 of them + the sample region):
                    // what the kernels' own translation unit was compiled with (layout_state_words), not a constant repeated here
 };
 extern const LayoutOps kLayout64, kLayoutSp4;  // dr_api.hip
+
+// The sampler modes of the C ABI (DrRenderDesc.sampler_mode) as the planner sees them, and what each one declares: every decision of
+// dr_api.hip / dr_batch.hip that depends on the mode reads one of these facts.  A new mode adds a row, its plan function and its case in genSamples.
+enum class SamplerKind : int { HostBuffer, LowDiscrepancy, Stratified, Adaptive, Halton };
+struct SamplerTraits {
+  bool deviceGenerated;  // the device sampler runs (else the caller's vectors are uploaded per batch)
+  bool floatForm;        // sample vectors are floats; the other kinds use the compact form unless rp.blocks forces floats
+  bool pixelBound;       // samples belong to a pixel list known up front (uploaded once, film_samples, tiles, one-batch slack, coherent camera, pilot); else written per batch
+  bool pow2Spp;          // spp is a power of two (the slot -> pixel maps of the batches are shifts)
+  const char* identityRoundSize;  // where Sampler.roundSize is the identity a light's nsamples must be its own rounding: the refusal's text, else null
+};
+constexpr SamplerTraits kSamplerTraits[] = {
+    {false, true, true, true, nullptr},       // HostBuffer
+    {true, false, true, true, nullptr},       // LowDiscrepancy
+    {true, true, true, true, "stratified sampler: a light's nsamples must be a power of two (StratifiedSampler.roundSize is the identity, the scene's sample layout is the rounded one)"},  // Stratified
+    {true, false, true, true, nullptr},       // Adaptive
+    {true, true, false, false, "halton sampler: a light's nsamples must be a power of two (HaltonSampler.roundSize is the identity, the scene's sample layout is the rounded one)"}};  // Halton
 
 struct RenderPlan {
   DrScene* sc = nullptr;
@@ -267,20 +288,18 @@ struct RenderPlan {
   SampleForm sf;
   const LayoutOps* L = nullptr;  // state layout of the NEXT batch (the layout pilot decides it after the first calibration batch)
   int spp = 0;
-  bool direct = false, dlSpec = false, envStage = false, hostBuf = false, packedTail = false;
-  bool strat = false;     // DR_SAMPLER_STRATIFIED(_NOJITTER): the device sampler writes the float sample form
-  int stratX = 0;         //   xPixelSamples (yPixelSamples = spp / stratX)
-  // DR_SAMPLER_HALTON: a "pixel" of this plan is an INDEX of the task's sequence (npixTotal = wanted, spp = 1: one slot
-  // per accepted sample); a batch is a range of indices, selected on the device before it runs with as many slots as were accepted
-  bool halton = false;
-  int32_t haltonWin[5] = {0, 0, 0, 0, 0};  // the task's window: left, top, right, bottom (inclusive), delta = max(width, height)
-  // the device sampler's launches for one batch (BatchRunner::loadSamples, dr_generate_samples)
+  bool direct = false, dlSpec = false, envStage = false, packedTail = false;
+  SamplerKind sampler = SamplerKind::LowDiscrepancy;
+  const SamplerTraits* traits = &kSamplerTraits[(int)SamplerKind::LowDiscrepancy];
+  struct { int x = 0; } strat;  // Stratified: xPixelSamples (yPixelSamples = spp / x)
+  // Adaptive: two counter-mode passes.  This plan is the first (spp, rp, sf: every pixel at min; its batches end with k_adaptive_decide), secondPass()
+  // derives the flagged pixels' at max.  pass: 0 = another sampler, 1 / 2 = which pass this plan runs; pixCap: pixels of a second-pass batch at most (planBatches)
+  struct { int pass = 0, min = 0, max = 0; uint32_t pixCap = 0; } adaptive;
+  // Halton: a "pixel" of this plan is an INDEX of the task's sequence (npixTotal = wanted, spp = 1: one slot per accepted sample); a
+  // batch is a range of indices, selected on the device before it runs.  win: the task's window: left, top, right, bottom (inclusive), delta = max(width, height)
+  struct { int32_t win[5] = {0, 0, 0, 0, 0}; } halton;
+  // the device sampler's launches for one batch (BatchRunner::loadSamples, the two sample dumps)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
-  // DR_SAMPLER_ADAPTIVE: two counter-mode passes.  This plan is the first (every pixel at adMin samples: spp,
-  // rp and sf are that pass's; its batches end with k_adaptive_decide); secondPass() derives the plan of the flagged pixels at adMax.
-  int adaptivePass = 0;   // 0: another sampler; 1 / 2: which pass of an adaptive render this plan runs
-  int adMin = 0, adMax = 0;
-  uint32_t adPixCap = 0;  // pixels of a second-pass batch at most (planBatches: against the workspace both passes share)
   // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'
   uint32_t wsCap = 0, wsPix = 0;
   SampleForm wsSf;
@@ -314,7 +333,7 @@ struct PilotResult {
 BatchState makeState(Workspace& w, const SampleForm& sf, const int2* pix, uint32_t nslots, bool useTail, int stateWords);  // dr_api.hip
 int runBatches(RenderPlan& plan, const int2* pixDev, size_t firstPixel);                                                    // dr_batch.hip
 int runPilot(RenderPlan& P, PilotResult& R);                                                                                // dr_batch.hip
-// DR_SAMPLER_HALTON: the accepted indices of [k0, k0 + n) into the workspace (haltonIdx), their number read back (the mode's host wait)
+// DR_SAMPLER_HALTON: the accepted indices of [k0, k0 + n) into the workspace (halton.idx), their number read back (the mode's host wait)
 int haltonSelect(RenderPlan& P, uint64_t k0, uint32_t n, uint32_t* accepted);                                               // dr_batch.hip
 int runHaltonBatches(RenderPlan& P, uint64_t* acceptedTotal);                                                               // dr_batch.hip
 

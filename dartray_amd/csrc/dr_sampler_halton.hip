@@ -9,8 +9,7 @@
 // workgroup counts its accepted lanes (wave ballots), one workgroup scans the counts, and the scatter repeats the test and places every
 // index behind the accepted ones before it.  Compiled once per state layout like dr_sampler_strat.hip (k_gen_halton writes the float
 // sample form behind the layout's state words), with -ffp-contract=off: every expression below is the reference's f64 expression.
-#include "dr_kernels.h"
-#include "dr_rng.h"
+#include "dr_sampler_lhs.h"
 #include "dr_wave.h"
 
 #ifdef DR_NS
@@ -110,16 +109,10 @@ __global__ void __launch_bounds__(DR_HALTON_BLOCK) k_halton_scatter(HaltonWindow
   seqIdx[at] = k0 + i;
 }
 
-// min((i + u) * delta, ONE_MINUS_EPSILON) in f64, stored to f32 (montecarlo.dart:311-312)
-DR_DEV float halton_lhs_value(int i, double u, double delta) {
-  return (float)fmin(((double)i + u) * delta, 0.9999999403953552);
-}
-
 // lane = slot = accepted sample.  The image sample leaves as its anchor pixel (floor) and the f32 fraction behind it (which may round
 // to 1.0f; consumers form (double)px + fraction as for every mode); lens and time are the radical inverses of k + 1 (the reference
 // increments currentSample before it draws them, :76-89), time raw.  The integrator's slots: LatinHypercube per 1-D slot, then per
-// 2-D slot, on the stream kind 5 of (k, 0) -- the loop of k_gen_strat_lhs (dr_sampler_strat.hip), slots of several entries through
-// rp.blocks and permuted in place.
+// 2-D slot, on the stream kind 5 of (k, 0) -- LHS_FILL_SLOTS (dr_sampler_lhs.h), the loop k_gen_strat_lhs runs as well.
 // The draws inside Li come from the stream kind 2 of (k, 0).  The shade kernels key that stream by the slot's pixel -- its index in the
 // full sampler extent, (y - extY0) * extW + (x - extX0), and the sample number, 0 at one sample per pixel entry (TailSrc, dr_kernels.hip) --
 // so the slot gets a second, KEY pixel whose index is k; the shade stages of a Halton batch read that array as their pixel array (nothing
@@ -143,37 +136,7 @@ __global__ void __launch_bounds__(256) k_gen_halton(RenderParams rp, BatchState 
   sv[4 * 64] = (float)radical_inverse<11>(k + 1);
   DartRandom rng;
   rng.seed(dr_counter_key(rp.seed, k, 0ull, 5));
-  for (int b = 3; b < nBlocks; ++b) {
-    int dst, n, dims;
-    if (rp.blocks) {
-      const LdBlock lb = rp.blocks[b];
-      dst = lb.dst;
-      n = lb.n;
-      dims = lb.is2D ? 2 : 1;
-    } else if (b < 3 + rp.n1D) {
-      dst = 5 + (b - 3);
-      n = 1;
-      dims = 1;
-    } else {
-      dst = 5 + rp.n1D + 2 * (b - 3 - rp.n1D);
-      n = 1;
-      dims = 2;
-    }
-    const double delta = 1.0 / (double)n;
-    for (int i = 0; i < n; ++i)
-      for (int d = 0; d < dims; ++d) sv[(size_t)(dst + dims * i + d) * 64] = halton_lhs_value(i, rng.randomFloat(), delta);
-    for (int d = 0; d < dims; ++d)
-      for (int j = 0; j < n; ++j) {
-        const int other = j + (int)(rng.randomUint() % (uint32_t)(n - j));
-        if (other != j) {
-          float* a = sv + (size_t)(dst + dims * j + d) * 64;
-          float* c = sv + (size_t)(dst + dims * other + d) * 64;
-          const float t = *a;
-          *a = *c;
-          *c = t;
-        }
-      }
-  }
+  LHS_FILL_SLOTS(rp, sv, rng, nBlocks)
 }
 
 // The accepted indices of [k0, k0 + n), in order, to seqIdx; their number to blk[(n + 255) / 256] (blk: that many entries + 1).
@@ -190,8 +153,7 @@ void launch_gen_halton(const RenderParams& rp, const BatchState& st, const int32
                        hipStream_t s) {
   if (st.nslots == 0) return;
   const HaltonWindow hw = {win[0], win[1], win[2], win[3], win[4]};
-  const int nBlocks = rp.blocks ? rp.nBlocks : 3 + rp.n1D + (rp.nFloats - 5 - rp.n1D) / 2;
-  hipLaunchKernelGGL(k_gen_halton, dim3((st.nslots + 255) / 256), dim3(256), 0, s, rp, st, hw, seqIdx, pix, keyPix, nBlocks);
+  hipLaunchKernelGGL(k_gen_halton, dim3((st.nslots + 255) / 256), dim3(256), 0, s, rp, st, hw, seqIdx, pix, keyPix, sampler_block_count(rp));
 }
 
 #ifdef DR_NS

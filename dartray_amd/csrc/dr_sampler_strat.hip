@@ -7,8 +7,7 @@
 // The sampler writes the float sample form (BatchState, dr_kernels.h): k_raygen, the shade kernels and k_film read it as they
 // read a host buffer's vectors.  Compiled once per state layout like dr_kernels.hip (the sample region starts behind the
 // layout's state words), with -ffp-contract=off.
-#include "dr_kernels.h"
-#include "dr_rng.h"
+#include "dr_sampler_lhs.h"
 
 #ifdef DR_NS
 namespace DR_NS {
@@ -19,10 +18,6 @@ namespace DR_NS {
 // Streams: kind 3 of (pixel, 0) -- the pixel's strata and shuffles, k_gen_strat_pixel; kind 4 of
 // (pixel, sample) -- the LatinHypercube draws of the integrator's slots, k_gen_strat_lhs.
 // ---------------------------------------------------------------------------
-// min((i + u) * delta, ONE_MINUS_EPSILON) in f64, stored to a Float32List (montecarlo.dart:275,288-289,311-312)
-DR_DEV float strat_value(int i, double u, double delta) {
-  return (float)fmin(((double)i + u) * delta, 0.9999999403953552);
-}
 // r % m for the wave-uniform divisor m: mulhi(r, floor(2^32 / m)) is r / m or one less (s_magic as in k_gen_samples)
 DR_DEV int magic_rem(uint32_t r, uint32_t m, const uint32_t* s_magic) {
   uint32_t rem = r - __umulhi(r, s_magic[m]) * m;
@@ -61,7 +56,7 @@ __global__ void __launch_bounds__(64) k_gen_strat_pixel(RenderParams rp, BatchSt
         for (int x = 0; x < xs; ++x, ++i) {
           const double jx = jitter ? rng.randomFloat() : 0.5;
           const double jy = jitter ? rng.randomFloat() : 0.5;
-          float u = strat_value(x, jx, dx), v = strat_value(y, jy, dy);
+          float u = lhs_value(x, jx, dx), v = lhs_value(y, jy, dy);
           if (pass == 0) {
             u = (u + fpx) - fpx;
             v = (v + fpy) - fpy;
@@ -70,7 +65,7 @@ __global__ void __launch_bounds__(64) k_gen_strat_pixel(RenderParams rp, BatchSt
           at(2 * pass + 1, i) = v;
         }
     const double invTot = 1.0 / (double)spp;  // StratifiedSample1D (montecarlo.dart:270-277): time
-    for (int i = 0; i < spp; ++i) at(4, i) = strat_value(i, jitter ? rng.randomFloat() : 0.5, invTot);
+    for (int i = 0; i < spp; ++i) at(4, i) = lhs_value(i, jitter ? rng.randomFloat() : 0.5, invTot);
     for (int i = 0; i < spp; ++i) {  // Shuffle(lensSamples, 0, spp, 2) (montecarlo.dart:294-303)
       const int other = i + magic_rem(rng.randomUint(), (uint32_t)(spp - i), s_magic);
       const float a = at(2, i), b = at(3, i);
@@ -108,9 +103,7 @@ __global__ void __launch_bounds__(64) k_gen_strat_pixel(RenderParams rp, BatchSt
 }
 
 // lane = sample slot: consecutive lanes are consecutive slots of a tile, so every field's store is one 256-byte run per wave.
-// LatinHypercube (montecarlo.dart:305-325) per 1-D slot, then per 2-D slot: n * dims randomFloat along the diagonal, then
-// dims * n randomUint for the permutations (drawn for n == 1 too).  Slots of several entries (DirectLighting, a light
-// with nSamples > 1: rp.blocks) are permuted in place in the sample region -- element (entry j, dim d) at field dst + dims * j + d.
+// The LatinHypercubes of the integrator's slots: LHS_FILL_SLOTS (dr_sampler_lhs.h).
 __global__ void __launch_bounds__(256) k_gen_strat_lhs(RenderParams rp, BatchState st, int nBlocks) {
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= st.nslots) return;
@@ -119,37 +112,7 @@ __global__ void __launch_bounds__(256) k_gen_strat_lhs(RenderParams rp, BatchSta
   DartRandom rng;
   rng.seed(dr_counter_key(rp.seed, pixelIndex, (uint64_t)(slot & (uint32_t)(rp.spp - 1)), 4));
   float* sv = st.sv() + TI64(st.tileStride, slot);
-  for (int k = 3; k < nBlocks; ++k) {
-    int dst, n, dims;
-    if (rp.blocks) {
-      const LdBlock b = rp.blocks[k];
-      dst = b.dst;
-      n = b.n;
-      dims = b.is2D ? 2 : 1;
-    } else if (k < 3 + rp.n1D) {
-      dst = 5 + (k - 3);
-      n = 1;
-      dims = 1;
-    } else {
-      dst = 5 + rp.n1D + 2 * (k - 3 - rp.n1D);
-      n = 1;
-      dims = 2;
-    }
-    const double delta = 1.0 / (double)n;
-    for (int i = 0; i < n; ++i)
-      for (int d = 0; d < dims; ++d) sv[(size_t)(dst + dims * i + d) * 64] = strat_value(i, rng.randomFloat(), delta);
-    for (int d = 0; d < dims; ++d)
-      for (int j = 0; j < n; ++j) {
-        const int other = j + (int)(rng.randomUint() % (uint32_t)(n - j));
-        if (other != j) {
-          float* a = sv + (size_t)(dst + dims * j + d) * 64;
-          float* b = sv + (size_t)(dst + dims * other + d) * 64;
-          const float t = *a;
-          *a = *b;
-          *b = t;
-        }
-      }
-  }
+  LHS_FILL_SLOTS(rp, sv, rng, nBlocks)
 }
 
 // ---------------------------------------------------------------------------
@@ -196,8 +159,7 @@ void launch_gen_strat(const RenderParams& rp, const BatchState& st, uint32_t npi
     attrSet = true;
   }
   hipLaunchKernelGGL(k_gen_strat_pixel, dim3((npix + ln - 1) / ln), dim3(ln), lds, s, rp, st, npix, xsamples);
-  const int nBlocks = rp.blocks ? rp.nBlocks : 3 + rp.n1D + (rp.nFloats - 5 - rp.n1D) / 2;
-  hipLaunchKernelGGL(k_gen_strat_lhs, dim3((st.nslots + 255) / 256), dim3(256), 0, s, rp, st, nBlocks);
+  hipLaunchKernelGGL(k_gen_strat_lhs, dim3((st.nslots + 255) / 256), dim3(256), 0, s, rp, st, sampler_block_count(rp));
 }
 void launch_export_samples(const RenderParams& rp, const BatchState& st, float* out, int stride, hipStream_t s) {
   if (st.nslots == 0) return;

@@ -13,9 +13,8 @@ import numpy as np
 
 from dartray_amd import core
 
+from montecarlo_restatement import ONE_MINUS_EPSILON, LatinHypercube  # noqa: F401  (shared with stratified_restatement.py)
 from stratified_restatement import counter_key, sample_extent
-
-ONE_MINUS_EPSILON = 0.9999999403953552  # montecarlo.dart:23
 
 
 def RadicalInverse(n, base):                                      # montecarlo.dart:327-339
@@ -43,17 +42,6 @@ def radical_inverse_int(n, base):
 
 def Lerp(t, v1, v2):                                               # common.dart:80-81
     return v1 * (1.0 - t) + v2 * t
-
-
-def LatinHypercube(samples, nSamples, nDim, rng):                  # montecarlo.dart:305-325 (samples: a Float32List)
-    delta = 1.0 / nSamples
-    for i in range(nSamples):
-        for j in range(nDim):
-            samples[nDim * i + j] = min((i + rng.randomFloat()) * delta, ONE_MINUS_EPSILON)
-    for i in range(nDim):
-        for j in range(nSamples):
-            other = j + (rng.randomUint() % (nSamples - j))
-            samples[nDim * j + i], samples[nDim * other + i] = samples[nDim * other + i], samples[nDim * j + i]
 
 
 def task_window(film, task_num=0, task_count=1):

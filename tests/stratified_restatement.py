@@ -13,7 +13,9 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-from dart_restatement import ONE_MINUS_EPSILON, RNG, DartRandom, Shuffle  # noqa: E402
+from dart_restatement import RNG, DartRandom, Shuffle  # noqa: E402
+
+from montecarlo_restatement import ONE_MINUS_EPSILON, LatinHypercube  # noqa: E402,F401  (shared with halton_restatement.py)
 
 _M64 = (1 << 64) - 1
 
@@ -35,17 +37,6 @@ def StratifiedSample2D(samples, nx, ny, rng, jitter=True):        # montecarlo.d
             samples[si] = min((x + jx) * dx, ONE_MINUS_EPSILON)
             samples[si + 1] = min((y + jy) * dy, ONE_MINUS_EPSILON)
             si += 2
-
-
-def LatinHypercube(samples, nSamples, nDim, rng):                  # montecarlo.dart:305-325
-    delta = 1.0 / nSamples
-    for i in range(nSamples):
-        for j in range(nDim):
-            samples[nDim * i + j] = min((i + rng.randomFloat()) * delta, ONE_MINUS_EPSILON)
-    for i in range(nDim):
-        for j in range(nSamples):
-            other = j + (rng.randomUint() % (nSamples - j))
-            samples[nDim * j + i], samples[nDim * other + i] = samples[nDim * other + i], samples[nDim * j + i]
 
 
 def get_more_samples(px, py, xs, ys, jitter, n1D, n2D, pixel_rng, sample_rng):
