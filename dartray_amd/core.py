@@ -142,6 +142,63 @@ class Disk(_Quadric):
         return (-self.radius, -self.radius, self.height), (self.radius, self.radius, self.height)
 
 
+def loop_subdivide(indices, P, nlevels, builder=None):
+    """LoopSubdivision's constructor and refine() (loop_subdivision.dart:24-308) through the C ABI: (P, N, indices, builder that ran) of
+    the TriangleMesh it creates, object space.  builder: "device" = dr_loop_subdivide_device (HIP; needs an initialised GPU), "host" =
+    dr_loop_subdivide (serial C++); None = the environment's DARTRAY_BVH_BUILDER, else the device builder whenever a GPU has been
+    selected -- the rule of build_bvh_arrays.  Both write the same bytes (tests/test_gpu_subdiv.py).  A mesh the reference would crash
+    or loop on raises DartRayHipError with the refusal's name."""
+    if builder is None:
+        builder = os.environ.get("DARTRAY_BVH_BUILDER") or ("device" if _abi._initialised is not None else "host")
+    if builder not in ("device", "host"):
+        raise ValueError("builder must be 'device' or 'host'")
+    lib = _abi.lib()
+    fn = lib.dr_loop_subdivide_device if builder == "device" else lib.dr_loop_subdivide
+    idx = np.ascontiguousarray(np.asarray(indices).astype(np.uint32, copy=False).reshape(-1))
+    idx = idx[:3 * (len(idx) // 3)]  # vi.length ~/ 3 faces (:370)
+    P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+    nv, nf = C.c_uint64(0), C.c_uint64(0)
+    args = (idx.ctypes.data, len(idx) // 3, P.ctypes.data, len(P), int(nlevels))
+    _abi.check(fn(*args, None, None, None, 0, 0, C.byref(nv), C.byref(nf)))  # the size query
+    Pout = np.empty((nv.value, 3), np.float32)
+    Nout = np.empty((nv.value, 3), np.float32)
+    iout = np.empty((nf.value, 3), np.uint32)
+    _abi.check(fn(*args, Pout.ctypes.data, Nout.ctypes.data, iout.ctypes.data, nv.value, nf.value, C.byref(nv), C.byref(nf)))
+    return Pout, Nout, iout, builder
+
+
+class LoopSubdivision:
+    """shapes/loop_subdivision.dart:23-93: Shape 'loopsubdiv'.  Not intersectable; refine() gives ONE TriangleMesh with per-vertex normals
+    (:285-307).  indices / P are the control mesh in object space; the constructor's topology (and the refusal of every mesh it cannot
+    handle) happens in refine(), inside the library."""
+
+    def __init__(self, o2w, w2o, reverseOrientation, indices, P, nlevels=1):
+        self.objectToWorld = np.ascontiguousarray(np.asarray(o2w, np.float32).reshape(4, 4))
+        self.worldToObject = np.ascontiguousarray(np.asarray(w2o, np.float32).reshape(4, 4))
+        self.reverseOrientation = bool(reverseOrientation)
+        self.indices = np.asarray(indices).reshape(-1)
+        self.P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 3)
+        self.nLevels = int(nlevels)
+        self.builder = None  # the builder the last refine() ran
+
+    def canIntersect(self):
+        return False  # :95-97
+
+    def objectBound(self):  # :310-316
+        return self.P.min(0), self.P.max(0)
+
+    def worldBound(self):  # :318-324
+        pts = transform_points(self.objectToWorld, self.P)
+        return pts.min(0), pts.max(0)
+
+    def refine(self, builder=None):
+        """TriangleMesh.Create(objectToWorld, worldToObject, reverseOrientation, {indices, P: Plimit, N}) (:301-307): the positions
+        go to world space like any mesh's (triangle_mesh.dart:29-36), the normals stay in object space with the transform."""
+        P, N, idx, self.builder = loop_subdivide(self.indices, self.P, self.nLevels, builder)
+        return TriangleMesh(idx, transform_points(self.objectToWorld, P), self.reverseOrientation, n=N,
+                            objectToWorld=self.objectToWorld, worldToObject=self.worldToObject)
+
+
 class MatteMaterial:
     """materials/matte_material.dart:37-77 with constant textures."""
 

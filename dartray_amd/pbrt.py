@@ -16,7 +16,7 @@ produce, and hands them to core.BVHAccel / core.SamplerRenderer (the C ABI).
 Matrices follow the reference's numerics (Float32List storage, f64
 expressions): matrix4x4.dart:193-343, transform.dart:83-86,110-129,214-331.
 
-Plugins on the path: shapes trianglemesh (with N / S / uv), heightfield, sphere, disk;
+Plugins on the path: shapes trianglemesh (with N / S / uv), heightfield, loopsubdiv, sphere, disk;
 materials matte (Lambertian / Oren-Nayar), plastic, mirror, glass; area lights
 on any of those shapes, infinite lights (constant or .npy lat-long map), point,
 spot and distant lights; perspective / orthographic / environment cameras, image film, box / gaussian / mitchell / triangle / sinc filters,
@@ -755,8 +755,14 @@ class DartRay:
             idx = np.stack([v(x, y), v(x + 1, y), v(x + 1, y + 1), v(x, y), v(x + 1, y + 1), v(x, y + 1)], axis=1).reshape(-1, 3)
             return core.TriangleMesh(idx.astype(np.uint32), self.ctm.transformPoints(P), ro, uvs=uv.reshape(-1),
                                      objectToWorld=self.ctm.m, worldToObject=self.ctm.mInv)
+        if name == "loopsubdiv":              # loop_subdivision.dart:360-372: refines into ONE TriangleMesh with N
+            nlevels = ps.findOneInt("nlevels", 1)
+            vi, P = ps.findInt("indices"), ps.findPoint("P")
+            if vi is None or P is None:
+                return None
+            return core.LoopSubdivision(o2w.m, o2w.mInv, ro, vi, P, nlevels).refine()
         if name != "trianglemesh":
-            raise UnsupportedFeature(f"Shape \"{name}\": only 'trianglemesh', 'heightfield', 'sphere' and 'disk' are on the path "
+            raise UnsupportedFeature(f"Shape \"{name}\": only 'trianglemesh', 'heightfield', 'loopsubdiv', 'sphere' and 'disk' are on the path "
                                      "(SURVEY.md section 8 row f4)")
         vi = ps.findInt("indices")            # triangle_mesh.dart:91-193
         P = ps.findPoint("P")

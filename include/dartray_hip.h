@@ -345,6 +345,28 @@ int dr_bvh_build_device(const float* verts, uint64_t nverts, const uint32_t* tri
                         const float* quadric_bounds, uint64_t nquadrics, int32_t max_prims_in_node,
                         DrBvhNode* nodes_out, uint64_t* nnodes_out, uint32_t* order_out, uint32_t* depth_out);
 
+/* LoopSubdivision (lib/shapes/loop_subdivision.dart:23-308): the constructor and refine() of Shape "loopsubdiv".
+ * indices[nfaces][3] / P[nverts][3]: the control mesh, object space.  Out: the TriangleMesh refine() hands to TriangleMesh.Create -- P_out
+ * (the limit positions, object space), N_out (Cross(S, T), object space, not normalised), indices_out[nfaces * 4^nlevels][3] in final face
+ * order and final vertex numbering -- bit for bit what the reference's text computes (f32 storage, one f64 operation and one rounding per
+ * operator, every sum in one-ring order), with one stated departure: the cos / sin weights of the tangents are the C library's.
+ * Two calls, like dr_enumerate_pixels: with P_out, N_out and indices_out all NULL the call validates the mesh and writes only the sizes
+ * (*nverts_out, *nfaces_out, always written on DR_OK); with all three set, vert_cap / face_cap are the vertices / faces the buffers hold,
+ * too few of either is DR_ERR_INVALID.  nlevels 0 is legal: the limit positions and normals of the control mesh itself.
+ * Refused by name (the reference crashes or loops on each): DR_ERR_INVALID for nlevels < 0, a vertex index out of range, a face that repeats
+ * a vertex, a vertex that no face names, an edge shared by more than two faces, two faces that traverse a shared edge in the same
+ * direction, a vertex whose faces do not form one fan; DR_ERR_UNSUPPORTED for 2^31 or more faces or vertices at the last level.
+ * Face order and the rotation of a face's three indices decide startFace and every ring's order, and so the low bits of the output.
+ * dr_loop_subdivide runs on the host and needs no GPU. */
+int dr_loop_subdivide(const uint32_t* indices, uint64_t nfaces, const float* P, uint64_t nverts, int32_t nlevels, float* P_out,
+                      float* N_out, uint32_t* indices_out, uint64_t vert_cap, uint64_t face_cap, uint64_t* nverts_out, uint64_t* nfaces_out);
+/* The same ON THE GPU (dr_subdiv_device.hip): identical arguments (host pointers) and byte-identical outputs.  Level 0 -- topology and the
+ * refusals -- stays on the host; every level, the limit positions and the normals are kernels over arrays that stay in device memory.
+ * Needs dr_init.  The host builder above stays as the fallback (no GPU) and as this one's checker. */
+int dr_loop_subdivide_device(const uint32_t* indices, uint64_t nfaces, const float* P, uint64_t nverts, int32_t nlevels, float* P_out,
+                             float* N_out, uint32_t* indices_out, uint64_t vert_cap, uint64_t face_cap, uint64_t* nverts_out,
+                             uint64_t* nfaces_out);
+
 /* Scene upload (replaces the construction of lib/core/scene.dart Scene). */
 int dr_scene_create(const DrSceneDesc* desc, DrScene** out);
 void dr_scene_destroy(DrScene* scene);
@@ -510,7 +532,8 @@ const char* dr_version(void);
  * 8: DR_SAMPLER_STRATIFIED, strat_xsamples -- the former padding at offset 1292 -- and dr_generate_samples;
  * 9: DR_SAMPLER_ADAPTIVE -- minSamples travels in strat_xsamples, no layout change -- and dr_scene_get_adaptive_pixels.
  * Still 9: DR_SAMPLER_HALTON and dr_generate_halton_samples are additive -- a new constant and a new entry point, no struct changes, no
- * existing call means anything else; a host built against the earlier version-9 header runs unchanged). */
+ * existing call means anything else; a host built against the earlier version-9 header runs unchanged.  Likewise dr_loop_subdivide and
+ * dr_loop_subdivide_device: two new entry points, no struct). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 

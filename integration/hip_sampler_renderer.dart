@@ -208,6 +208,13 @@ typedef _HaltonSamplesC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Uint64, 
     Pointer<Uint64>);
 typedef _HaltonSamplesD = int Function(Pointer<Void>, Pointer<Uint8>, int, int, Pointer<Uint64>, Pointer<Int32>, Pointer<Float>, int,
     Pointer<Uint64>);
+// dr_loop_subdivide / dr_loop_subdivide_device (LoopSubdivision.refine on the host / on the GPU; DESIGN.md 2.10): indices, nfaces, P, nverts,
+// nlevels, P_out, N_out, indices_out, vert_cap, face_cap, nverts_out, nfaces_out.  All three outputs null: the size query.  (Signatures only --
+// like the rest of this file they have never been compiled: nothing here can compile Dart.)
+typedef _LoopSubdivideC = Int32 Function(Pointer<Uint32>, Uint64, Pointer<Float>, Uint64, Int32, Pointer<Float>, Pointer<Float>, Pointer<Uint32>,
+    Uint64, Uint64, Pointer<Uint64>, Pointer<Uint64>);
+typedef _LoopSubdivideD = int Function(Pointer<Uint32>, int, Pointer<Float>, int, int, Pointer<Float>, Pointer<Float>, Pointer<Uint32>,
+    int, int, Pointer<Uint64>, Pointer<Uint64>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -246,6 +253,9 @@ class _Blob {
 class HipSamplerRenderer extends Renderer {
   static final DynamicLibrary _lib = _open();
   static final _InitD _init = _lib.lookupFunction<_InitC, _InitD>('dr_init');
+  /// LoopSubdivision.refine behind the C ABI: the host builder and, after dr_init, the device builder (same bytes).
+  static final _LoopSubdivideD loopSubdivide = _lib.lookupFunction<_LoopSubdivideC, _LoopSubdivideD>('dr_loop_subdivide');
+  static final _LoopSubdivideD loopSubdivideDevice = _lib.lookupFunction<_LoopSubdivideC, _LoopSubdivideD>('dr_loop_subdivide_device');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
   /// library of another layout version is refused before any struct crosses the boundary.
   static const int ABI_VERSION = 9;
