@@ -1,0 +1,156 @@
+"""lib/renderers/, lib/surface_integrators/ and lib/volume_integrators/."""
+import ctypes as C
+
+import numpy as np
+
+from .. import _abi
+from .samplers import HaltonSampler
+
+
+class PathIntegrator:
+    """surface_integrators/path_integrator.dart:26-27,133-136."""
+
+    def __init__(self, maxDepth=5):
+        self.maxDepth = int(maxDepth)
+
+    kind = _abi.DR_INTEGRATOR_PATH
+
+
+class DirectLightingIntegrator:
+    """surface_integrators/direct_lighting_integrator.dart:23-28: strategy 'all' (UniformSampleAllLights, the default) or 'one'
+    (UniformSampleOneLight with the integrator's own lightNum slot, :51-55,82-87)."""
+    SAMPLE_ALL_UNIFORM = 0
+    SAMPLE_ONE_UNIFORM = 1
+
+    def __init__(self, strategy=0, maxDepth=5):
+        if strategy not in (self.SAMPLE_ALL_UNIFORM, self.SAMPLE_ONE_UNIFORM):
+            raise ValueError("DirectLightingIntegrator strategy must be SAMPLE_ALL_UNIFORM (0) or SAMPLE_ONE_UNIFORM (1)")
+        self.strategy = strategy
+        self.maxDepth = int(maxDepth)
+
+    @property
+    def kind(self):
+        return _abi.DR_INTEGRATOR_DIRECT_ONE if self.strategy == self.SAMPLE_ONE_UNIFORM else _abi.DR_INTEGRATOR_DIRECT_ALL
+
+
+class EmissionIntegrator:
+    """volume_integrators/emission_integrator.dart with no VolumeRegion: T = 1,
+    Lv = 0; its only effect on the path is the two 1-D sample slots it requests."""
+
+    def __init__(self, stepSize=1.0):
+        self.stepSize = stepSize
+
+
+class OutputImage:
+    """core/output_image.dart:35-55."""
+
+    def __init__(self, xOffset, yOffset, width, height, rgb, film=None):
+        self.xOffset, self.yOffset, self.width, self.height = xOffset, yOffset, width, height
+        self.imageWidth, self.imageHeight = width, height
+        self.rgb = rgb
+        self.film = film  # (X, Y, Z, weightSum) per pixel: ImageFilm._Lxyz/_weightSum
+
+
+class SamplerRenderer:
+    """renderers/sampler_renderer.dart:28-31: Renderer.render(Scene) -> OutputImage."""
+
+    def __init__(self, sampler, camera, surfaceIntegrator, volumeIntegrator=None, taskNum=0, taskCount=1,
+                 tileRank=0, tileCount=1, tileSize=32):
+        self.sampler = sampler
+        self.camera = camera
+        self.surfaceIntegrator = surfaceIntegrator
+        self.volumeIntegrator = volumeIntegrator
+        self.taskNum, self.taskCount = int(taskNum), int(taskCount)
+        self.tileRank, self.tileCount, self.tileSize = int(tileRank), int(tileCount), int(tileSize)
+        self.last_stats = None
+
+    def describe(self):
+        """DrRenderDesc for this renderer (plus the arrays it points into)."""
+        d = _abi.DrRenderDesc()
+        self.camera.to_abi(d.camera)
+        self.camera.film.to_abi(d.film)
+        d.integrator = self.surfaceIntegrator.kind
+        d.max_depth = self.surfaceIntegrator.maxDepth
+        d.task_num, d.task_count = self.taskNum, self.taskCount
+        d.tile_rank, d.tile_count, d.tile_size = self.tileRank, self.tileCount, self.tileSize
+        return d, self.sampler.to_abi(d)
+
+    def generate_samples(self, scene, pixels):
+        """dr_generate_samples: the device sampler's vectors for the raster pixels `pixels` ([n, 2]) -> [n * spp, nFloats] f32
+        (AdaptiveSampler: the first pass's, spp = minSamples)."""
+        d, keep = self.describe()
+        dev = scene._device()
+        pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
+        nf = _abi.lib().dr_scene_sample_floats(dev.handle, d.integrator)
+        out = np.zeros((len(pixels) * self.sampler.generatedSamplesPerPixel, nf), dtype=np.float32)
+        _abi.check(_abi.lib().dr_generate_samples(dev.handle, C.byref(d), pixels.ctypes.data, len(pixels), out.ctypes.data, nf))
+        return out
+
+    def generate_halton_samples(self, scene, first=0, count=None):
+        """dr_generate_halton_samples: the device sampler's accepted samples among the indices [first, first + count) of this task's
+        sequence (count None: to its end) -> (k [n] uint64, pixel_xy [n, 2] int32, vectors [n, nFloats] f32), in increasing k."""
+        d, keep = self.describe()
+        dev = scene._device()
+        if count is None:
+            _, _, w, h = HaltonSampler.window(self)
+            count = (d.spp * max(w, h) ** 2 if w > 0 and h > 0 else 0) - first
+        nf = _abi.lib().dr_scene_sample_floats(dev.handle, d.integrator)
+        k = np.zeros(max(1, count), np.uint64)
+        xy = np.zeros((max(1, count), 2), np.int32)
+        out = np.zeros((max(1, count), nf), np.float32)
+        n = C.c_uint64(0)
+        _abi.check(_abi.lib().dr_generate_halton_samples(dev.handle, C.byref(d), first, count, k.ctypes.data, xy.ctypes.data, out.ctypes.data, nf, C.byref(n)))
+        return k[:n.value].copy(), xy[:n.value].copy(), out[:n.value].copy()
+
+    def render(self, scene):
+        film = self.camera.film
+        d, keep = self.describe()
+        out_film = np.zeros((film.height, film.width, 4), dtype=np.float32)
+        out_rgb = np.zeros((film.height, film.width, 3), dtype=np.float32)
+        dev = scene._device()
+        dev.reset_stats()
+        _abi.check(_abi.lib().dr_render(dev.handle, C.byref(d), out_film.ctypes.data, out_rgb.ctypes.data))
+        del keep
+        self.last_stats = dev.stats()
+        return OutputImage(film.left, film.top, film.width, film.height, out_rgb, out_film)
+
+    def supersampled_pixels(self, scene):
+        """The raster pixels the last render of `scene` traced at maxSamples ([n, 2] int32, no particular order; AdaptiveSampler)."""
+        return scene._device().adaptive_pixels()
+
+    def render_sharded(self, scene, root=0):
+        """One rank's part of a sharded render (dr_render_sharded): this renderer's tile / task share, ONE film reduce over
+        the communicator of dr_comm_init, and on the root rank the OutputImage; other ranks return None.  What
+        RenderManager's fan-out and rectangle merge do in the host (render_manager.dart:100-141), as one C call."""
+        film = self.camera.film
+        d, keep = self.describe()
+        lib = _abi.lib()
+        is_root = lib.dr_comm_world() <= 1 or lib.dr_comm_rank() == root
+        out_film = np.zeros((film.height, film.width, 4), dtype=np.float32) if is_root else None
+        out_rgb = np.zeros((film.height, film.width, 3), dtype=np.float32) if is_root else None
+        dev = scene._device()
+        _abi.check(lib.dr_render_sharded(dev.handle, C.byref(d), root, out_film.ctypes.data if is_root else None,
+                                         out_rgb.ctypes.data if is_root else None))
+        del keep
+        return OutputImage(film.left, film.top, film.width, film.height, out_rgb, out_film) if is_root else None
+
+    def pixels(self):
+        """Raster pixels this renderer's task / tile share traces, in trace order (host-only)."""
+        d, keep = self.describe()
+        n = C.c_uint64(0)
+        _abi.check(_abi.lib().dr_enumerate_pixels(C.byref(d), None, 0, C.byref(n)))
+        out = np.zeros((n.value, 2), dtype=np.int32)
+        _abi.check(_abi.lib().dr_enumerate_pixels(C.byref(d), out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def render_device(self, scene, film_ptr, stream=0):
+        """Renderer.render with the film left in HBM: accumulates this renderer's share into the
+        [height, width, 4] f32 device buffer at `film_ptr` on HIP stream `stream` (asynchronous)."""
+        d, keep = self.describe()
+        dev = scene._device()
+        _abi.check(_abi.lib().dr_render_device(dev.handle, C.byref(d), film_ptr, stream))
+        self._keep = keep
+        return dev
+
+    def Li(self, *a, **k):  # a per-ray FFI seam is far too fine grained
+        raise NotImplementedError("SamplerRenderer.Li is evaluated on the device inside render()")
