@@ -20,6 +20,7 @@ DR_SAMPLER_STRATIFIED = 2
 DR_SAMPLER_STRATIFIED_NOJITTER = 3
 DR_SAMPLER_ADAPTIVE = 4  # spp = maxSamples, strat_xsamples = minSamples
 DR_SAMPLER_HALTON = 5  # spp = pixelsamples, any integer >= 1
+DR_SAMPLER_RANDOM = 6  # spp = pixelsamples, a power of two
 DR_LIGHT_DIFFUSE_AREA = 0
 DR_LIGHT_INFINITE = 1
 DR_LIGHT_POINT = 2

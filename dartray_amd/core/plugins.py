@@ -6,8 +6,8 @@ from .film import BoxFilter, GaussianFilter, ImageFilm, LanczosSincFilter, Mitch
 from .lights import DiffuseAreaLight
 from .materials import MatteMaterial
 from .renderer import DirectLightingIntegrator, EmissionIntegrator, PathIntegrator, SamplerRenderer
-from .samplers import (AdaptiveSampler, HaltonSampler, LinearPixelSampler, LowDiscrepancySampler, RandomPixelSampler, StratifiedSampler,
-                       TilePixelSampler)
+from .samplers import (AdaptiveSampler, HaltonSampler, LinearPixelSampler, LowDiscrepancySampler, RandomPixelSampler, RandomSampler,
+                       StratifiedSampler, TilePixelSampler)
 from .shapes import TriangleMesh
 
 
@@ -35,6 +35,7 @@ def RegisterStandardPlugins():
     Plugin.register("sampler", "stratified", StratifiedSampler)
     Plugin.register("sampler", "adaptive", AdaptiveSampler)
     Plugin.register("sampler", "halton", HaltonSampler)
+    Plugin.register("sampler", "random", RandomSampler)
     Plugin.register("film", "image", ImageFilm)
     Plugin.register("pixelSampler", "linear", lambda ps=None: LinearPixelSampler())
     Plugin.register("pixelSampler", "tile", lambda ps=None: TilePixelSampler((ps or {}).get("tilesize", 32), (ps or {}).get("random", True)))

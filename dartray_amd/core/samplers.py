@@ -433,6 +433,78 @@ class HaltonSampler(_Sampler):
         return HostBufferSampler(self.camera, 1, np.array(pixels, np.int32).reshape(-1, 2), np.array(vecs, np.float32).reshape(-1, nf), tail, cnt)
 
 
+class RandomSampler(_Sampler):
+    """samplers/random_sampler.dart:31-107, FULL_SAMPLING: every value of a sample vector is one RNG.randomFloat() -- image x, image y,
+    lens u, lens v, time, then the entries of every 1-D and of every 2-D slot in request order; nothing is stratified or shuffled.  On the
+    device (DR_SAMPLER_RANDOM) every (pixel, sample) owns a keyed stream; serial_samples() walks the reference's ONE serial
+    RNG(taskNum) instead and returns the vectors as a HostBufferSampler.  The device needs pixelsamples to be a power of two, at most 4096:
+    the reference's default of 10 (Create, :94-101) has to be given as one."""
+
+    def __init__(self, camera, pixelsamples=10, seed=5489, pixels=None):
+        self.camera = camera
+        self.samplesPerPixel = int(pixelsamples)
+        if self.samplesPerPixel < 1:
+            raise ValueError("RandomSampler: pixelsamples must be positive")
+        self.seed = int(seed)
+        self.pixelSampler = pixels or LinearPixelSampler()
+
+    sampler_mode = _abi.DR_SAMPLER_RANDOM
+
+    def to_abi(self, d):
+        n = self.samplesPerPixel
+        if n & (n - 1) or n > 4096:
+            raise ValueError("RandomSampler: pixelsamples must be a power of two, at most 4096, on the device (got %d; the slot -> pixel "
+                             "maps of the batches are shifts)" % n)
+        return super().to_abi(d)
+
+    def roundSize(self, size):  # :90-92
+        return size
+
+    def maximumSampleCount(self):  # :43-45
+        return self.samplesPerPixel
+
+    slot_counts = StratifiedSampler.slot_counts
+
+    def pixel_samples(self, px, py, n1D, n2D, sample_rng):
+        """The loop of getMoreSamples (:65-85) for one pixel: [spp, 5 + sum(n1D) + 2 sum(n2D)] f32 in the C ABI's field order, the image
+        sample as the f32 of its fraction inside the pixel (the reference's imageX is the double u + px), time raw (the Lerp over the shutter
+        is the consumer's).  sample_rng(i) is the generator of sample i's draws (the same object everywhere: the reference's serial stream)."""
+        nf = 5 + sum(n1D) + 2 * sum(n2D)
+        vec = np.zeros((self.samplesPerPixel, nf), np.float32)
+        for i in range(self.samplesPerPixel):
+            rng = sample_rng(i)
+            for f in range(nf):  # (the field order is the draw order: image, lens, time, oneD..., twoD...)
+                vec[i, f] = rng.randomFloat()
+        return vec
+
+    def serial_samples(self, renderer, scene, li_draws=None, passes=1):
+        """The reference's own stream: ONE RNG(taskNum) (sampler_renderer.dart:137) threaded through the sampler, pixel after pixel in the
+        pixel sampler's order, and through Li.  Returns a HostBufferSampler.  li_draws(px, py, vector, rng): as for
+        StratifiedSampler.serial_samples.  passes: as written, getMoreSamples walks the pixel list samplesPerPixel times in FULL_SAMPLING
+        (:50-56 count walks, :62 hands out samplesPerPixel samples per call); the device traces the first walk, the default here, and
+        passes = samplesPerPixel continues the same stream through all of them (the pixel list repeats)."""
+        integ = renderer.surfaceIntegrator
+        needs_tail = integ.kind == _abi.DR_INTEGRATOR_PATH and integ.maxDepth >= 3
+        if needs_tail and li_draws is None:
+            raise ValueError("serial_samples: a PathIntegrator with maxDepth >= 3 draws inside Li; pass li_draws")
+        if not 1 <= int(passes) <= self.samplesPerPixel:
+            raise ValueError("serial_samples: passes must be between 1 and samplesPerPixel")
+        n1D, n2D = self.slot_counts(renderer, scene)
+        e = renderer.camera.film.getSampleExtent()
+        x0, x1, y0, y1 = GetSubWindow(e[1] - e[0], e[3] - e[2], renderer.taskNum, max(1, renderer.taskCount))
+        pixels = np.concatenate([self.pixelSampler.setup(x0, y0, x1 - x0, y1 - y0)] * int(passes))
+        rng = DartRandom(renderer.taskNum)
+        vecs, tails = [], []
+        for px, py in pixels:
+            v = self.pixel_samples(int(px), int(py), n1D, n2D, lambda i: rng)
+            vecs.append(v)
+            if needs_tail:
+                tails += [list(li_draws(int(px), int(py), v[i], rng)) for i in range(len(v))]
+        tail, cnt = _pack_tails(tails) if needs_tail else (None, None)
+        nf = 5 + sum(n1D) + 2 * sum(n2D)
+        return HostBufferSampler(self.camera, self.samplesPerPixel, pixels, np.concatenate(vecs) if vecs else np.zeros((0, nf), np.float32), tail, cnt)
+
+
 class HostBufferSampler(_Sampler):
     """Explicit camera samples: pixel_xy [npix,2] int32, sample_vec [npix*spp, nfloats] f32
     (imageU, imageV, lensU, lensV, time, oneD..., twoD...), tail [npix*spp, max_tail] f64 =

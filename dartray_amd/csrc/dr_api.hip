@@ -236,6 +236,7 @@ void RenderPlan::genSamples(const RenderParams& rpB, const BatchState& st, uint3
     case SamplerKind::LowDiscrepancy: case SamplerKind::Adaptive: L->gen_samples(rpB, st, np, s); break;
     case SamplerKind::Stratified: L->gen_strat(rpB, st, np, strat.x, s); break;
     case SamplerKind::Halton: L->gen_halton(rpB, st, halton.win, sc->ws.halton.idx.p, sc->ws.pix.p, sc->ws.halton.keyPix.p, s); break;
+    case SamplerKind::Random: L->gen_random(rpB, st, s); break;
   }
 }
 
@@ -422,9 +423,9 @@ int planRender(RenderPlan& P) {
   DrScene* sc = P.sc;
   const DrRenderDesc* rd = P.rd;
   // ---- the sampler mode: its kind, its own rules, the samples per pixel of this plan ----
-  static const SamplerKind kinds[] = {SamplerKind::HostBuffer, SamplerKind::LowDiscrepancy, SamplerKind::Stratified, SamplerKind::Stratified, SamplerKind::Adaptive, SamplerKind::Halton};
-  static_assert(DR_SAMPLER_HOST_BUFFER == 0 && DR_SAMPLER_COUNTER == 1 && DR_SAMPLER_STRATIFIED == 2 && DR_SAMPLER_STRATIFIED_NOJITTER == 3 && DR_SAMPLER_ADAPTIVE == 4 && DR_SAMPLER_HALTON == 5, "kinds[] is indexed by sampler_mode");
-  const bool knownMode = rd->sampler_mode >= 0 && rd->sampler_mode <= DR_SAMPLER_HALTON;
+  static const SamplerKind kinds[] = {SamplerKind::HostBuffer, SamplerKind::LowDiscrepancy, SamplerKind::Stratified, SamplerKind::Stratified, SamplerKind::Adaptive, SamplerKind::Halton, SamplerKind::Random};
+  static_assert(DR_SAMPLER_HOST_BUFFER == 0 && DR_SAMPLER_COUNTER == 1 && DR_SAMPLER_STRATIFIED == 2 && DR_SAMPLER_STRATIFIED_NOJITTER == 3 && DR_SAMPLER_ADAPTIVE == 4 && DR_SAMPLER_HALTON == 5 && DR_SAMPLER_RANDOM == 6, "kinds[] is indexed by sampler_mode");
+  const bool knownMode = rd->sampler_mode >= 0 && rd->sampler_mode <= DR_SAMPLER_RANDOM;
   P.sampler = knownMode ? kinds[rd->sampler_mode] : SamplerKind::LowDiscrepancy;  // (an unknown mode is refused where the pixel source is chosen, as ever)
   P.traits = &kSamplerTraits[(int)P.sampler];
   P.spp = rd->spp;
@@ -451,6 +452,10 @@ int planRender(RenderPlan& P) {
       if (rd->spp < 1) return fail(DR_ERR_INVALID, "halton sampler: pixelsamples (spp) must be at least 1");
       if (rd->tile_count > 1) return fail(DR_ERR_UNSUPPORTED, "halton sampler: tile_count > 1 (the tile round-robin deals out pixels; a task's Halton sequence is not bound to pixels: split by task_num / task_count)");
       P.spp = 1;  // (one slot per accepted sample)
+      break;
+    case SamplerKind::Random:  // RandomSampler (random_sampler.dart:94-101): pixelsamples as given -- nothing rounds it, so the limit is refused under its own name
+      if (P.spp <= 0 || (P.spp & (P.spp - 1)) != 0 || P.spp > 4096)
+        return fail(DR_ERR_UNSUPPORTED, "random sampler: pixelsamples (spp) must be a power of two, at most 4096 (the slot -> pixel maps of the batches are shifts)");
       break;
   }
   const int spp = P.spp;
@@ -534,7 +539,7 @@ int planRender(RenderPlan& P) {
     if (P.strat.x <= 0 || spp % P.strat.x != 0)
       return fail(DR_ERR_INVALID, "stratified sampler: strat_xsamples must be positive and divide spp (spp = xsamples * ysamples)");
   }
-  // roundSize is the identity (stratified_sampler.dart:63-65, halton_sampler.dart:102-104) while the scene's DirectLighting slot layout is
+  // roundSize is the identity (stratified_sampler.dart:63-65, halton_sampler.dart:102-104, random_sampler.dart:90-92) while the scene's DirectLighting slot layout is
   // LowDiscrepancySampler's rounded one, so a light's nsamples must be its own rounding
   if (P.traits->identityRoundSize && rd->integrator == DR_INTEGRATOR_DIRECT_ALL)
     for (int n : sc->lightNSamples)
@@ -593,7 +598,7 @@ int planBatches(RenderPlan& P) {
   // Sample vectors: the on-device LD sampler stores permuted indices + scrambles (compact form) whenever every LD block
   // has one entry per pixel sample; host buffers and multi-entry blocks (DirectLighting with nsamples > 1) use floats.
   SampleForm& sf = P.sf;
-  sf.compact = !P.traits->floatForm && rp.blocks == nullptr;  // (the stratified and Halton samplers' values are no function of an LD index: floats)
+  sf.compact = !P.traits->floatForm && rp.blocks == nullptr;  // (the stratified, Halton and random samplers' values are no function of an LD index: floats)
   if (!P.traits->floatForm && !sf.compact && spp > 1024)  // (the LD sampler writing floats)
     return fail(DR_ERR_UNSUPPORTED, "spp > 1024 with LD blocks of several entries per sample (DirectLighting with nsamples > 1): the float-form sampler's table exceeds the LDS");
   sf.nFloats = rp.nFloats;

@@ -251,9 +251,9 @@ struct SampleForm {
 #define DR_LAYOUT_LAUNCHERS(X)                                                                                                          \
   X(trace, launch_trace) X(trace_coherent, launch_trace_coherent) X(trace_kernel_id, trace_kernel_id) X(gen_samples, launch_gen_samples)   \
   X(gen_strat, launch_gen_strat) X(export_samples, launch_export_samples) X(adaptive_decide, launch_adaptive_decide)                       \
-  X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(mark_alive, launch_mark_alive) X(sum_alive, launch_sum_alive) \
-  X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path) X(env, launch_env)              \
-  X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(film, launch_film)
+  X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
+  X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
+  X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(film, launch_film)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -264,7 +264,7 @@ extern const LayoutOps kLayout64, kLayoutSp4;  // dr_api.hip
 
 // The sampler modes of the C ABI (DrRenderDesc.sampler_mode) as the planner sees them, and what each one declares: every decision of
 // dr_api.hip / dr_batch.hip that depends on the mode reads one of these facts.  A new mode adds a row, its plan function and its case in genSamples.
-enum class SamplerKind : int { HostBuffer, LowDiscrepancy, Stratified, Adaptive, Halton };
+enum class SamplerKind : int { HostBuffer, LowDiscrepancy, Stratified, Adaptive, Halton, Random };
 struct SamplerTraits {
   bool deviceGenerated;  // the device sampler runs (else the caller's vectors are uploaded per batch)
   bool floatForm;        // sample vectors are floats; the other kinds use the compact form unless rp.blocks forces floats
@@ -277,7 +277,8 @@ constexpr SamplerTraits kSamplerTraits[] = {
     {true, false, true, true, nullptr},       // LowDiscrepancy
     {true, true, true, true, "stratified sampler: a light's nsamples must be a power of two (StratifiedSampler.roundSize is the identity, the scene's sample layout is the rounded one)"},  // Stratified
     {true, false, true, true, nullptr},       // Adaptive
-    {true, true, false, false, "halton sampler: a light's nsamples must be a power of two (HaltonSampler.roundSize is the identity, the scene's sample layout is the rounded one)"}};  // Halton
+    {true, true, false, false, "halton sampler: a light's nsamples must be a power of two (HaltonSampler.roundSize is the identity, the scene's sample layout is the rounded one)"},  // Halton
+    {true, true, true, true, "random sampler: a light's nsamples must be a power of two (RandomSampler.roundSize is the identity, the scene's sample layout is the rounded one)"}};  // Random
 
 struct RenderPlan {
   DrScene* sc = nullptr;

@@ -28,6 +28,8 @@ void launch_adaptive_decide(const RenderParams& rp, const BatchState& st, uint32
 void launch_halton_select(const int32_t win[5], uint64_t k0, uint32_t n, uint32_t* blk, unsigned long long* seqIdx, hipStream_t s);
 void launch_gen_halton(const RenderParams& rp, const BatchState& st, const int32_t win[5], const unsigned long long* seqIdx, int2* pix, int2* keyPix,
                        hipStream_t s);
+// dr_sampler_random.hip (DR_SAMPLER_RANDOM): the st.nslots float-form vectors of the batch, every value one randomFloat() of the slot's own stream
+void launch_gen_random(const RenderParams& rp, const BatchState& st, hipStream_t s);
 void launch_mark_alive(const uint32_t* list, const uint32_t* nList, uint32_t shift, uint8_t* alive, hipStream_t s);
 void launch_sum_alive(const uint8_t* alive, uint32_t nGroups, uint32_t npix, const uint32_t nb[3], TraceCounters* ctr, hipStream_t s);
 void launch_transpose_samples(const float* aos, int stride, const BatchState& st, int nFloats, hipStream_t s);

@@ -1,5 +1,5 @@
 // dr_sampler_lhs.h -- what the stratified and the Halton device sampler share (dr_sampler_strat.hip, dr_sampler_halton.hip):
-// how many LD blocks a sample vector has, and the LatinHypercube of the integrator's slots (core/montecarlo.dart:305-325).
+// how many LD blocks a sample vector has (also dr_sampler_random.hip's), and the LatinHypercube of the integrator's slots (core/montecarlo.dart:305-325).
 #ifndef DR_SAMPLER_LHS_H
 #define DR_SAMPLER_LHS_H
 

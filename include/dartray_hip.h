@@ -253,6 +253,15 @@ typedef struct DrFilm {
  * sample by at most 2^-25 pixel).  One host wait per batch of the call (the number of accepted samples of the batch's index range).
  * DrRenderStats.camera_samples counts the accepted samples, film_samples the window's film pixels x spp. */
 #define DR_SAMPLER_HALTON 5
+/* On-device RandomSampler (random_sampler.dart:47-88, FULL_SAMPLING); DESIGN.md section 2.11.  One keyed stream per (pixel, sample),
+ * (seed, pixelIndex, sample, kind 6) with pixelIndex the pixel's position in the full sampler extent; every value of the sample vector is one
+ * Random.nextDouble() of it, in the reference's order: image x, image y, lens u, lens v, time, then the entries of every 1-D slot and of every
+ * 2-D slot in request order.  Nothing is stratified, shuffled or permuted; the draws inside Li stay on kind 2 as in every mode.
+ * DrRenderDesc.spp = pixelsamples, a power of two <= 4096 (the reference's default of 10 has to be given as a power of two), and under
+ * DR_INTEGRATOR_DIRECT_ALL every light's nsamples must be a power of two (RandomSampler.roundSize is the identity, the scene's slot layout is
+ * the rounded one): DR_ERR_UNSUPPORTED otherwise.  strat_xsamples is ignored.  Departure from the reference, as for DR_SAMPLER_HALTON: image
+ * fraction, lens and time are rounded to f32 once (the image sample by at most 2^-25 pixel); the slots' values are exact. */
+#define DR_SAMPLER_RANDOM 6
 
 /* Everything SamplerRenderer.render needs besides the Scene
  * (lib/renderers/sampler_renderer.dart:29-31,36-65). */
@@ -262,7 +271,7 @@ typedef struct DrRenderDesc {
   int32_t integrator;
   int32_t max_depth; /* PathIntegrator.maxDepth / DirectLightingIntegrator.maxDepth (default 5) */
   int32_t spp;       /* LowDiscrepancySampler.nPixelSamples, StratifiedSampler's xPixelSamples * yPixelSamples or AdaptiveSampler.maxSamples, power of two;
-                      * DR_SAMPLER_HALTON: pixelsamples, any integer >= 1 */
+                      * DR_SAMPLER_HALTON: pixelsamples, any integer >= 1; DR_SAMPLER_RANDOM: pixelsamples, a power of two */
   int32_t sampler_mode;
   int64_t seed; /* DR_SAMPLER_COUNTER */
   /* Work split.  task_*: the reference's GetSubWindow rectangle of the sampler
@@ -458,7 +467,7 @@ int dr_render_device(DrScene* scene, const DrRenderDesc* desc, void* film_dev, v
  * rank's round-robin tiles).  Host-only; out_xy may be NULL to query the count. */
 int dr_enumerate_pixels(const DrRenderDesc* desc, int32_t* out_xy, uint64_t cap, uint64_t* n_out);
 
-/* Diagnostics and tests: runs ONLY the device sampler of `desc` (DR_SAMPLER_COUNTER or DR_SAMPLER_STRATIFIED*) for the npix raster
+/* Diagnostics and tests: runs ONLY the device sampler of `desc` (DR_SAMPLER_COUNTER, DR_SAMPLER_STRATIFIED* or DR_SAMPLER_RANDOM) for the npix raster
  * pixels pixel_xy[npix][2] -- the launches a render of those pixels makes, into the render's own workspace -- and copies the camera-sample
  * vectors back: out[npix * spp][stride] in reference field order (imageU, imageV, lensU, lensV, time, oneD..., twoD...; the image
  * sample as its fraction inside the pixel), stride >= dr_scene_sample_floats.  Every LD block is produced (a render may skip blocks no
@@ -533,7 +542,8 @@ const char* dr_version(void);
  * 9: DR_SAMPLER_ADAPTIVE -- minSamples travels in strat_xsamples, no layout change -- and dr_scene_get_adaptive_pixels.
  * Still 9: DR_SAMPLER_HALTON and dr_generate_halton_samples are additive -- a new constant and a new entry point, no struct changes, no
  * existing call means anything else; a host built against the earlier version-9 header runs unchanged.  Likewise dr_loop_subdivide and
- * dr_loop_subdivide_device: two new entry points, no struct). */
+ * dr_loop_subdivide_device: two new entry points, no struct; and DR_SAMPLER_RANDOM: a new constant that dr_render*, dr_generate_samples and
+ * dr_scene_last_render_info serve like the other pixel-bound modes, no struct, no entry point). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 

@@ -173,6 +173,7 @@ const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed str
 const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
 const int DR_SAMPLER_ADAPTIVE = 4;             // AdaptiveSampler (contrast) on the LD sampler's keyed streams; spp = maxSamples
 const int DR_SAMPLER_HALTON = 5;               // HaltonSampler: one sequence per task, samples not bound to pixels; spp = samplesPerPixel, any count
+const int DR_SAMPLER_RANDOM = 6;               // RandomSampler: every value one nextDouble() of the (pixel, sample) stream; spp = samplesPerPixel, a power of two
 
 typedef _InitC = Int32 Function(Int32);
 typedef _InitD = int Function(int);
@@ -834,7 +835,8 @@ class HipSamplerRenderer extends Renderer {
       final bool stratified = '${sampler.runtimeType}' == 'StratifiedSampler';
       final bool adaptive = '${sampler.runtimeType}' == 'AdaptiveSampler';
       final bool halton = '${sampler.runtimeType}' == 'HaltonSampler';
-      if (!stratified && !adaptive && !halton && sampler is! LowDiscrepancySampler) {
+      final bool random = '${sampler.runtimeType}' == 'RandomSampler';
+      if (!stratified && !adaptive && !halton && !random && sampler is! LowDiscrepancySampler) {
         _unsupported('sampler ${sampler.runtimeType}');
       }
       // The device runs the same LD / stratified sampler with one keyed RNG stream per (pixel, LD block) / pixel / (pixel, sample)
@@ -862,6 +864,11 @@ class HipSamplerRenderer extends Renderer {
         // over the task's own window; the library refuses the tile split for this sampler (tileCount > 1: DR_ERR_UNSUPPORTED).
         rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
         rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_HALTON);
+      } else if (random) {
+        // pixelsamples as given (samplers/random_sampler.dart:94-101): it must be a power of two (the library answers DR_ERR_UNSUPPORTED
+        // otherwise, so the default of 10 has to be given as 8 or 16)
+        rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
+        rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_RANDOM);
       } else {
         rd.i32(OFF_DrRenderDesc_spp, sampler.samplesPerPixel);
         rd.i32(OFF_DrRenderDesc_sampler_mode, DR_SAMPLER_COUNTER);

@@ -7,7 +7,7 @@ out="${1:-/dev/stdout}"
 cd "$root/dartray_amd/csrc"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function -x hip -c --cuda-device-only -Rpass-analysis=kernel-resource-usage -o /dev/null"
 {
-for src in dr_trace.hip dr_kernels.hip dr_sampler_strat.hip dr_sampler_adaptive.hip dr_sampler_halton.hip; do
+for src in dr_trace.hip dr_kernels.hip dr_sampler_strat.hip dr_sampler_adaptive.hip dr_sampler_halton.hip dr_sampler_random.hip; do
   for lay in "" "-DDR_SUB=4 -DDR_NS=sp4 -DDR_STATE_WORDS_K=48 -DDR_GROUPED=1"; do
     /opt/rocm/bin/hipcc $F $lay $src 2>&1 | python3 -c '
 import re, sys
