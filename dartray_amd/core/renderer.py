@@ -33,6 +33,21 @@ class DirectLightingIntegrator:
         return _abi.DR_INTEGRATOR_DIRECT_ONE if self.strategy == self.SAMPLE_ONE_UNIFORM else _abi.DR_INTEGRATOR_DIRECT_ALL
 
 
+class WhittedIntegrator:
+    """surface_integrators/whitted_integrator.dart:23-80: Le, one light sample per light, SpecularReflect / SpecularTransmit while
+    ray.depth + 1 < maxDepth.  On the device DR_INTEGRATOR_WHITTED (k_shade_whitted)."""
+
+    def __init__(self, maxDepth=5):
+        self.maxDepth = int(maxDepth)
+
+    kind = _abi.DR_INTEGRATOR_WHITTED
+
+    @staticmethod
+    def Create(params=None):
+        """WhittedIntegrator.Create (whitted_integrator.dart:74-77): `maxdepth`, default 5."""
+        return WhittedIntegrator((params or {}).get("maxdepth", 5))
+
+
 class EmissionIntegrator:
     """volume_integrators/emission_integrator.dart with no VolumeRegion: T = 1,
     Lv = 0; its only effect on the path is the two 1-D sample slots it requests."""
@@ -70,6 +85,10 @@ class SamplerRenderer:
         self.camera.to_abi(d.camera)
         self.camera.film.to_abi(d.film)
         d.integrator = self.surfaceIntegrator.kind
+        if d.integrator == _abi.DR_INTEGRATOR_WHITTED and getattr(self.sampler, "sampler_mode", None) == _abi.DR_SAMPLER_HOST_BUFFER \
+                and self.sampler.li_seed is None:
+            raise ValueError("a WhittedIntegrator draws from the keyed (pixel, sample) streams in every sampler mode: give the "
+                             "HostBufferSampler the seed of the render it replays (seed=...)")
         d.max_depth = self.surfaceIntegrator.maxDepth
         d.task_num, d.task_count = self.taskNum, self.taskCount
         d.tile_rank, d.tile_count, d.tile_size = self.tileRank, self.tileCount, self.tileSize

@@ -258,6 +258,8 @@ class StratifiedSampler(_Sampler):
             return [1] * 14, [1] * 9
         if kind == _abi.DR_INTEGRATOR_DIRECT_ONE:
             return [1] * 5, [1] * 2
+        if kind == _abi.DR_INTEGRATOR_WHITTED:  # no requestSamples: the volume integrator's tau + scatter slots only
+            return [1] * 2, []
         ns = [self.roundSize(L.nSamples) for L in scene.lights]
         return [n for k in ns for n in (k, k)] + [1, 1], [n for k in ns for n in (k, k)]
 
@@ -510,11 +512,13 @@ class HostBufferSampler(_Sampler):
     (imageU, imageV, lensU, lensV, time, oneD..., twoD...), tail [npix*spp, max_tail] f64 =
     the RNG.randomFloat() values PathIntegrator.Li draws for bounces >= 3.  tail_count [npix*spp] (how many of its
     max_tail slots each sample actually drew: the oracle's recording has it) selects the PACKED form of the C ABI
-    (DrRenderDesc.tail_offsets): only the drawn values cross the host link."""
+    (DrRenderDesc.tail_offsets): only the drawn values cross the host link.  `seed`: read by a WhittedIntegrator render alone, whose
+    LightSample.random draws are keyed streams, not a recorded tail."""
 
-    def __init__(self, camera, spp, pixel_xy, sample_vec, tail=None, tail_count=None):
+    def __init__(self, camera, spp, pixel_xy, sample_vec, tail=None, tail_count=None, seed=None):
         self.camera = camera
         self.samplesPerPixel = int(spp)
+        self.li_seed = None if seed is None else int(seed)  # WhittedIntegrator only (required there: SamplerRenderer.describe): its draws inside Li are the keyed (pixel, sample) streams in every mode (DESIGN.md 2.12)
         self.pixel_xy = np.ascontiguousarray(pixel_xy, dtype=np.int32).reshape(-1, 2)
         self.sample_vec = np.ascontiguousarray(sample_vec, dtype=np.float32)
         self.tail = None if tail is None else np.ascontiguousarray(tail, dtype=np.float64)
@@ -540,6 +544,8 @@ class HostBufferSampler(_Sampler):
         d.pixel_xy = self.pixel_xy.ctypes.data
         d.sample_vec = self.sample_vec.ctypes.data
         d.sample_stride = self.sample_vec.shape[1]
+        if self.li_seed is not None:
+            d.seed = self.li_seed
         if self.tail is not None:
             d.tail = self.tail.ctypes.data
             if self.tail_offsets is not None:

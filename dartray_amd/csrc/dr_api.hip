@@ -293,6 +293,7 @@ int32_t dr_sample_floats(int32_t integrator, uint32_t nlights) {
   if (integrator == DR_INTEGRATOR_PATH) return 5 + 14 + 18;
   // strategy "one" (direct_lighting_integrator.dart:82-87): light component, lightNum, BSDF component + tau + scatter; light position, BSDF direction
   if (integrator == DR_INTEGRATOR_DIRECT_ONE) return 5 + 5 + 4;
+  if (integrator == DR_INTEGRATOR_WHITTED) return 5 + 2;  // WhittedIntegrator has no requestSamples: tau + scatter only
   return 5 + (2 * (int)nlights + 2) + 4 * (int)nlights;
 }
 
@@ -462,14 +463,20 @@ int planRender(RenderPlan& P) {
   if (P.traits->pow2Spp && (spp <= 0 || (spp & (spp - 1)) != 0)) return fail(DR_ERR_INVALID, "spp must be a power of two (low_discrepancy_sampler.dart:43-49)");
   if (spp > 4096) return fail(DR_ERR_UNSUPPORTED, "spp > 4096 (one pixel's shuffle table of a 16-pixel sampler group would not fit the LDS)");
   // ---- the integrator, the camera and the film into rp; the state layout; the stages ----
-  if (rd->integrator != DR_INTEGRATOR_PATH && rd->integrator != DR_INTEGRATOR_DIRECT_ALL && rd->integrator != DR_INTEGRATOR_DIRECT_ONE)
+  if (rd->integrator != DR_INTEGRATOR_PATH && rd->integrator != DR_INTEGRATOR_DIRECT_ALL && rd->integrator != DR_INTEGRATOR_DIRECT_ONE &&
+      rd->integrator != DR_INTEGRATOR_WHITTED)
     return fail(DR_ERR_INVALID, "unknown integrator");
+  // WhittedIntegrator (whitted_integrator.dart:26-72): no sample slots of its own, one stage per light, the specular recursion below
+  P.whitted = rd->integrator == DR_INTEGRATOR_WHITTED;
+  if (P.whitted && rd->max_depth < 1) return fail(DR_ERR_INVALID, "whitted integrator: max_depth must be at least 1 (maxdepth counts the camera vertex: ray.depth + 1 < maxDepth)");
   if (rd->max_depth < 0 || rd->max_depth > 64) return fail(DR_ERR_INVALID, "max_depth out of range");
-  P.direct = rd->integrator != DR_INTEGRATOR_PATH;
+  if (P.whitted && P.sampler == SamplerKind::Adaptive)
+    return fail(DR_ERR_UNSUPPORTED, "whitted integrator: the adaptive sampler is not supported (its second pass over the rounds of the specular recursion has no test; every other sampler mode is)");
+  P.direct = rd->integrator != DR_INTEGRATOR_PATH && !P.whitted;
   const bool directOne = rd->integrator == DR_INTEGRATOR_DIRECT_ONE;  // strategy "one": the last entry of the scene's stage table, an arithmetic slot layout
   // DirectLighting over mirror / glass recurses through SpecularReflect / SpecularTransmit (integrator.dart:187-290):
-  // an explicit per-slot stack and one round of the stage loop per vertex of the ray tree (k_shade_spec)
-  P.dlSpec = P.direct && sc->hasSpecular;
+  // an explicit per-slot stack and one round of the stage loop per vertex of the ray tree (k_shade_spec); so does Whitted
+  P.dlSpec = (P.direct || P.whitted) && sc->hasSpecular;
   // k_env (dr_kernels.hip): the environment-map work of a plain-triangle scene's path stages runs in its own kernel
   P.envStage = rd->integrator == DR_INTEGRATOR_PATH && sc->d.hasEnv && !(sc->d.nquads || sc->d.hasSpec || sc->d.srec);
   // State layout (see LayoutOps): the four-slot sub-tiles for the renders whose lists thin out early.  Which one is MEASURED on
@@ -502,7 +509,7 @@ int planRender(RenderPlan& P) {
   while ((1 << rp.sppShift) < P.spp) ++rp.sppShift;
   rp.nLights = (int)sc->d.nlights;
   rp.nFloats = P.direct && !directOne ? sc->dlNFloats : dr_sample_floats(rd->integrator, sc->d.nlights);
-  rp.n1D = directOne ? 5 : (P.direct ? sc->dlN1D : 14);
+  rp.n1D = directOne ? 5 : (P.direct ? sc->dlN1D : (P.whitted ? 2 : 14));  // (Whitted: only the volume integrator's tau + scatter slots)
   rp.blocks = P.direct && !directOne && sc->dlMulti ? sc->dlBlocks.p : nullptr;
   rp.nBlocks = sc->dlNBlocks;
   rp.dstages = directOne ? sc->dlStages.p + sc->dlNStages : sc->dlStages.p;
@@ -531,7 +538,7 @@ int planRender(RenderPlan& P) {
   P.needTail = rd->integrator == DR_INTEGRATOR_PATH && rd->max_depth >= 3 ? (rd->max_depth - 2) * (perNee + 3) + std::max(0, rd->max_depth - 3) : 0;
   rp.maxTail = rd->max_tail;
   P.sgrid = g_numCU;  // the shade launchers size their grid per CU (DR_SHADE_GRID), grid-stride over the active list
-  P.nStages = rd->integrator == DR_INTEGRATOR_PATH ? rd->max_depth + 2 : rp.nDirectStages + 1;
+  P.nStages = rd->integrator == DR_INTEGRATOR_PATH ? rd->max_depth + 2 : (P.whitted ? rp.nLights + 1 : rp.nDirectStages + 1);
   // ---- the mode's rules that have always run behind the integrator's, max_depth's and the camera's refusals above (strat_xsamples reads only spp, but a descriptor
   // that also names an unknown integrator keeps that refusal); which pixels: the caller's list, the task's / tile share's, or -- not pixel bound -- a window ----
   if (P.sampler == SamplerKind::Stratified) {
@@ -860,7 +867,8 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
   sc->lastInfo[0] = P.L == &kLayoutSp4 ? 4 : 64;
   sc->lastInfo[1] = P.L->trace_kernel_id(sc->d, 0);
   sc->lastInfo[2] = P.L->trace_kernel_id(sc->d, 1);
-  sc->lastInfo[3] = -1;  // (reserved: rounds 4-5 reported the treelet-parked traversal's parking rounds here)
+  // (rounds 4-5 reported the treelet-parked traversal's parking rounds here; -1 since)  A Whitted render: the integrator and its shading kernels
+  sc->lastInfo[3] = !P.whitted ? -1 : DR_INTEGRATOR_WHITTED | 0x100 | (P.dlSpec ? 0x200 : 0);  // bit 8: k_shade_whitted, bit 9: k_shade_spec
   sc->lastInfo[4] = pilot.setsRun;
   sc->lastInfo[5] = (int32_t)std::min<uint64_t>(0x7fffffff, nBatches);
   sc->lastInfo[6] = P.tgrid / std::max(1, g_numCU);

@@ -230,6 +230,7 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
   (void)hipEventRecord(evS, s);
   const BatchState stS = shadeState();
   if (rd->integrator == DR_INTEGRATOR_PATH) L.shade_path(sc->d, rp, stS, q, b, P.sgrid, s);
+  else if (P.whitted) L.shade_whitted(sc->d, rp, stS, q, b, P.sgrid, s);
   else L.shade_direct(sc->d, rp, stS, q, b, P.sgrid, s);
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {
@@ -248,7 +249,10 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
     slog[b + 1].s1 = evS1;
   }
   if (b + 1 >= P.nStages) return DR_OK;
-  if (sideBySide) {
+  if (P.whitted) {  // a Whitted stage queues one shadow ray per slot and nothing else (no MIS ray, no continuation: the child rays are the rounds')
+    trace(q.anyQ, q.nAny, 1, s, w.spill.p);
+    if (log) logTrace(slog[b + 1], 1);
+  } else if (sideBySide) {
     hipEvent_t eS = sc->getEvent(), eA = sc->getEvent();
     (void)hipEventRecord(eS, s);
     (void)hipStreamWaitEvent(sc->s3, eS, 0);

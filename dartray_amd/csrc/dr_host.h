@@ -253,7 +253,8 @@ struct SampleForm {
   X(gen_strat, launch_gen_strat) X(export_samples, launch_export_samples) X(adaptive_decide, launch_adaptive_decide)                       \
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
-  X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(film, launch_film)
+  X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
+  X(film, launch_film)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -290,6 +291,7 @@ struct RenderPlan {
   const LayoutOps* L = nullptr;  // state layout of the NEXT batch (the layout pilot decides it after the first calibration batch)
   int spp = 0;
   bool direct = false, dlSpec = false, envStage = false, packedTail = false;
+  bool whitted = false;  // DR_INTEGRATOR_WHITTED: k_shade_whitted's stages (one per light, any-hit rays only); dlSpec: k_shade_spec's rounds behind them
   SamplerKind sampler = SamplerKind::LowDiscrepancy;
   const SamplerTraits* traits = &kSamplerTraits[(int)SamplerKind::LowDiscrepancy];
   struct { int x = 0; } strat;  // Stratified: xPixelSamples (yPixelSamples = spp / x)

@@ -40,6 +40,8 @@ void launch_env(const DScene& sc, const RenderParams& rp, const BatchState& st, 
 void launch_shade_direct(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int stage,
                          int grid, hipStream_t s);
 void launch_shade_spec(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int grid, hipStream_t s);
+// dr_shade_whitted.hip: stage `stage` of a WhittedIntegrator vertex (light stage - 1 folded in, light `stage` set up)
+void launch_shade_whitted(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int stage, int grid, hipStream_t s);
 void launch_film(const RenderParams& rp, const BatchState& st, const float* filterTable, uint32_t npix, float* film,
                  hipStream_t s);
 void launch_film_resolve(const float* film, int64_t npix, float* rgb, hipStream_t s);

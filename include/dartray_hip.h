@@ -219,6 +219,13 @@ typedef struct DrFilm {
 #define DR_INTEGRATOR_PATH 1       /* PathIntegrator (path_integrator.dart) */
 #define DR_INTEGRATOR_DIRECT_ONE 2 /* DirectLightingIntegrator, strategy "one" (direct_lighting_integrator.dart:51-55,82-87): ONE light per
                                     * vertex, picked by its own 1-D sample slot (lightNumOffset), the estimate scaled by the light count */
+/* WhittedIntegrator (whitted_integrator.dart:26-72): at every hit Le, ONE light sample per light -- the light half only, no
+ * BSDF-sampling half, no MIS weight, no nsamples -- and SpecularReflect / SpecularTransmit while ray.depth + 1 < max_depth.  It requests no sample
+ * slots: the vector is image, lens, time and the volume integrator's two 1-D slots (dr_sample_floats: 7), and every LightSample.random(rng) is
+ * three draws of the sample's keyed in-Li stream (kind 2) in EVERY sampler mode, DR_SAMPLER_HOST_BUFFER included (tail / max_tail are not read:
+ * a ray tree's draws have no useful bound).  max_depth < 1 is DR_ERR_INVALID, DR_SAMPLER_ADAPTIVE with it DR_ERR_UNSUPPORTED; every other sampler
+ * mode is served.  One count is read back per round of the specular recursion, as for DirectLighting over mirror / glass. */
+#define DR_INTEGRATOR_WHITTED 3
 
 #define DR_SAMPLER_HOST_BUFFER 0 /* caller supplies sample vectors (+ the in-Li RNG draws) */
 #define DR_SAMPLER_COUNTER 1     /* on-device LD sampler, keyed per (pixel, block) / (pixel, sample) */
@@ -269,11 +276,11 @@ typedef struct DrRenderDesc {
   DrCamera camera;
   DrFilm film;
   int32_t integrator;
-  int32_t max_depth; /* PathIntegrator.maxDepth / DirectLightingIntegrator.maxDepth (default 5) */
+  int32_t max_depth; /* PathIntegrator.maxDepth / DirectLightingIntegrator.maxDepth / WhittedIntegrator.maxDepth (default 5) */
   int32_t spp;       /* LowDiscrepancySampler.nPixelSamples, StratifiedSampler's xPixelSamples * yPixelSamples or AdaptiveSampler.maxSamples, power of two;
                       * DR_SAMPLER_HALTON: pixelsamples, any integer >= 1; DR_SAMPLER_RANDOM: pixelsamples, a power of two */
   int32_t sampler_mode;
-  int64_t seed; /* DR_SAMPLER_COUNTER */
+  int64_t seed; /* the device samplers' keyed streams; DR_INTEGRATOR_WHITTED: its in-Li streams in every sampler mode, DR_SAMPLER_HOST_BUFFER too */
   /* Work split.  task_*: the reference's GetSubWindow rectangle of the sampler
    * window (lib/core/common.dart:52-73, dartray.dart:1009-1023).  tile_*: 32x32
    * tiles (TilePixelSampler.tileSize, tile_pixel_sampler.dart:37) dealt
@@ -395,7 +402,8 @@ int dr_scene_set_trace_kernels(DrScene* scene, const uint32_t kernels[2]);
 int dr_scene_get_pilot(const DrScene* scene, float ms_per_gb_out[6]);
 /* Diagnostics: what the scene's LAST dr_render_device call actually ran with, switches (dr_set_option / environment)
  * included -- out[0] path-state layout (64 / 4), out[1] / out[2] the traversal kernel of its closest-hit / any-hit launches
- * (2, 3, 5 as above), out[3] reserved (-1), out[4] the
+ * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED render the integrator and its shading kernels: bits 0-7 the DR_INTEGRATOR_*
+ * constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass); out[4] the
  * calibration batches it ran (0: no pilot), out[5] its batches, out[6] workgroups per CU of a persistent traversal
  * launch, out[7] bit 0: a stage's any-hit launch ran beside its closest-hit launch, bit 1: the camera rays went through the
  * wave-coherent kernel (k_trace_pk), bit 3: the device sampler generated bounce b's blocks only for the pixel
@@ -543,7 +551,9 @@ const char* dr_version(void);
  * Still 9: DR_SAMPLER_HALTON and dr_generate_halton_samples are additive -- a new constant and a new entry point, no struct changes, no
  * existing call means anything else; a host built against the earlier version-9 header runs unchanged.  Likewise dr_loop_subdivide and
  * dr_loop_subdivide_device: two new entry points, no struct; and DR_SAMPLER_RANDOM: a new constant that dr_render*, dr_generate_samples and
- * dr_scene_last_render_info serve like the other pixel-bound modes, no struct, no entry point). */
+ * dr_scene_last_render_info serve like the other pixel-bound modes, no struct, no entry point; and DR_INTEGRATOR_WHITTED: a new constant for
+ * DrRenderDesc.integrator, whose max_depth carries maxdepth -- no struct, no field, no entry point; dr_scene_last_render_info names it in the
+ * word that was reserved, which stays -1 after every other integrator's render). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 

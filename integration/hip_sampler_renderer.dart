@@ -167,7 +167,7 @@ const int DR_SHADING_N = 1, DR_SHADING_S = 2, DR_SHADING_UV = 4;
 const int DR_COMM_ID_BYTES = 128;
 const int DR_PRIM_QUADRIC = 0xFFFFFFFF, DR_QUADRIC_SPHERE = 1, DR_QUADRIC_DISK = 2;
 const int DR_CAMERA_PERSPECTIVE = 0, DR_CAMERA_ORTHOGRAPHIC = 1, DR_CAMERA_ENVIRONMENT = 2;
-const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2;
+const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2, DR_INTEGRATOR_WHITTED = 3;
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
 const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
@@ -827,6 +827,10 @@ class HipSamplerRenderer extends Renderer {
         rd.i32(OFF_DrRenderDesc_integrator,
                di.strategy == DirectLightingIntegrator.SAMPLE_ONE_UNIFORM ? DR_INTEGRATOR_DIRECT_ONE : DR_INTEGRATOR_DIRECT_ALL);
         rd.i32(OFF_DrRenderDesc_max_depth, di.maxDepth);
+      } else if ('${surfaceIntegrator.runtimeType}' == 'WhittedIntegrator') {  // (told by its name, like the samplers below)
+        final dynamic wi = surfaceIntegrator;
+        rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_WHITTED);
+        rd.i32(OFF_DrRenderDesc_max_depth, wi.maxDepth);
       } else {
         _unsupported('surface integrator ${surfaceIntegrator.runtimeType}');
       }
