@@ -15,6 +15,16 @@ class PathIntegrator:
 
     kind = _abi.DR_INTEGRATOR_PATH
 
+    def requestSamples(self, sampler, scene):
+        """(n1D, n2D): entries of the 1-D and 2-D slots requestSamples asks of the sampler, in request order (:124-131):
+        SAMPLE_DEPTH = 3 x (light 1D+2D, lightNum 1D, bsdf 1D+2D, path 1D+2D)."""
+        return [1] * 12, [1] * 9
+
+    @property
+    def li_draws_recorded(self):
+        """Li draws from the renderer's serial RNG (beyond its third vertex): a replay of that stream has to record those draws."""
+        return self.maxDepth >= 3
+
 
 class DirectLightingIntegrator:
     """surface_integrators/direct_lighting_integrator.dart:23-28: strategy 'all' (UniformSampleAllLights, the default) or 'one'
@@ -32,6 +42,16 @@ class DirectLightingIntegrator:
     def kind(self):
         return _abi.DR_INTEGRATOR_DIRECT_ONE if self.strategy == self.SAMPLE_ONE_UNIFORM else _abi.DR_INTEGRATOR_DIRECT_ALL
 
+    li_draws_recorded = False
+
+    def requestSamples(self, sampler, scene):
+        """(n1D, n2D) as for PathIntegrator (:70-87).  "one": light component, lightNum, BSDF component; light position, BSDF direction.
+        "all": per light a light and a BSDF slot pair of sampler.roundSize(nSamples) entries."""
+        if self.strategy == self.SAMPLE_ONE_UNIFORM:
+            return [1] * 3, [1] * 2
+        ns = [sampler.roundSize(L.nSamples) for L in scene.lights]
+        return [n for k in ns for n in (k, k)], [n for k in ns for n in (k, k)]
+
 
 class WhittedIntegrator:
     """surface_integrators/whitted_integrator.dart:23-80: Le, one light sample per light, SpecularReflect / SpecularTransmit while
@@ -41,6 +61,17 @@ class WhittedIntegrator:
         self.maxDepth = int(maxDepth)
 
     kind = _abi.DR_INTEGRATOR_WHITTED
+    li_draws_recorded = False  # (LightSample.random draws are keyed (pixel, sample) streams in every sampler mode)
+
+    def requestSamples(self, sampler, scene):
+        """No requestSamples in the reference: no slots of its own."""
+        return [], []
+
+    def check_sampler(self, sampler):
+        """SamplerRenderer.describe: what this integrator asks of the renderer's sampler."""
+        if getattr(sampler, "sampler_mode", None) == _abi.DR_SAMPLER_HOST_BUFFER and sampler.li_seed is None:
+            raise ValueError("a WhittedIntegrator draws from the keyed (pixel, sample) streams in every sampler mode: give the "
+                             "HostBufferSampler the seed of the render it replays (seed=...)")
 
     @staticmethod
     def Create(params=None):
@@ -79,16 +110,21 @@ class SamplerRenderer:
         self.tileRank, self.tileCount, self.tileSize = int(tileRank), int(tileCount), int(tileSize)
         self.last_stats = None
 
+    def requestSamples(self, sampler, scene):
+        """(n1D, n2D): the surface integrator's slots, then the volume integrator's two 1-D ones -- tau and scatter, which the device's
+        sample vector always carries (emission_integrator.dart:26-29)."""
+        n1D, n2D = self.surfaceIntegrator.requestSamples(sampler, scene)
+        return n1D + [1, 1], n2D
+
     def describe(self):
         """DrRenderDesc for this renderer (plus the arrays it points into)."""
         d = _abi.DrRenderDesc()
         self.camera.to_abi(d.camera)
         self.camera.film.to_abi(d.film)
         d.integrator = self.surfaceIntegrator.kind
-        if d.integrator == _abi.DR_INTEGRATOR_WHITTED and getattr(self.sampler, "sampler_mode", None) == _abi.DR_SAMPLER_HOST_BUFFER \
-                and self.sampler.li_seed is None:
-            raise ValueError("a WhittedIntegrator draws from the keyed (pixel, sample) streams in every sampler mode: give the "
-                             "HostBufferSampler the seed of the render it replays (seed=...)")
+        check = getattr(self.surfaceIntegrator, "check_sampler", None)
+        if check:
+            check(self.sampler)
         d.max_depth = self.surfaceIntegrator.maxDepth
         d.task_num, d.task_count = self.taskNum, self.taskCount
         d.tile_rank, d.tile_count, d.tile_size = self.tileRank, self.tileCount, self.tileSize

@@ -132,6 +132,10 @@ class _Sampler:
         """Vectors per pixel SamplerRenderer.generate_samples returns."""
         return self.samplesPerPixel
 
+    def slot_counts(self, renderer, scene):
+        """(n1D, n2D): entries of the 1-D and 2-D sample slots the integrators request of this sampler, in request order."""
+        return renderer.requestSamples(self, scene)
+
 
 class LowDiscrepancySampler(_Sampler):
     """samplers/low_discrepancy_sampler.dart:32-88.  The reference threads ONE
@@ -180,6 +184,29 @@ def _pack_tails(tails):
     for i, t in enumerate(tails):
         tail[i, :len(t)] = t
     return tail, cnt
+
+
+def _serial_host_buffer(sampler, renderer, scene, li_draws, spp, walk):
+    """What the samplers' serial_samples share: the reference's ONE RNG(taskNum) (sampler_renderer.dart:137) threaded through the sampler and
+    through Li.  walk(n1D, n2D, rng) is the sampler's own loop: it yields one pixel_xy row at a time, (px, py, vectors [spp, nFloats]), in the stream's order,
+    drawing from rng; behind every yield li_draws(px, py, vector, rng) -> the randomFloat() values Li draws for each of its vectors, taken from the same rng
+    (the host has no integrator of its own to count them): required where the integrator's Li draws from that stream, unused otherwise.
+    Returns the HostBufferSampler of the vectors and the recorded draws, at spp vectors per pixel_xy row."""
+    recorded = renderer.surfaceIntegrator.li_draws_recorded
+    if recorded and li_draws is None:
+        raise ValueError("serial_samples: a PathIntegrator with maxDepth >= 3 draws inside Li; pass li_draws")
+    n1D, n2D = sampler.slot_counts(renderer, scene)
+    rng = DartRandom(renderer.taskNum)
+    pixels, vecs, tails = [], [], []
+    for px, py, v in walk(n1D, n2D, rng):
+        pixels.append((px, py))
+        vecs.append(v)
+        if recorded:
+            tails += [list(li_draws(px, py, row, rng)) for row in v]
+    tail, cnt = _pack_tails(tails) if recorded else (None, None)
+    nf = 5 + sum(n1D) + 2 * sum(n2D)
+    return HostBufferSampler(sampler.camera, spp, np.array(pixels, np.int32).reshape(-1, 2),
+                             np.concatenate(vecs) if vecs else np.zeros((0, nf), np.float32), tail, cnt)
 
 
 class StratifiedSampler(_Sampler):
@@ -251,40 +278,15 @@ class StratifiedSampler(_Sampler):
             vec[i, 5:] = _latin_hypercube_slots(n1D, n2D, sample_rng(i))
         return vec
 
-    def slot_counts(self, renderer, scene):
-        """(n1D, n2D): entries of the 1-D and 2-D sample slots the integrators request, in request order."""
-        kind = renderer.surfaceIntegrator.kind
-        if kind == _abi.DR_INTEGRATOR_PATH:
-            return [1] * 14, [1] * 9
-        if kind == _abi.DR_INTEGRATOR_DIRECT_ONE:
-            return [1] * 5, [1] * 2
-        if kind == _abi.DR_INTEGRATOR_WHITTED:  # no requestSamples: the volume integrator's tau + scatter slots only
-            return [1] * 2, []
-        ns = [self.roundSize(L.nSamples) for L in scene.lights]
-        return [n for k in ns for n in (k, k)] + [1, 1], [n for k in ns for n in (k, k)]
-
     def serial_samples(self, renderer, scene, li_draws=None):
-        """The reference's own stream: ONE RNG(taskNum) (sampler_renderer.dart:137) threaded through the sampler, pixel after pixel in
-        the pixel sampler's order, and through Li.  Returns a HostBufferSampler.  li_draws(px, py, vector, rng) -> the
-        randomFloat() values Li draws for that sample, taken from rng (PathIntegrator beyond its third vertex; the host has
-        no integrator of its own to count them): required for a PathIntegrator with maxDepth >= 3, unused otherwise."""
-        integ = renderer.surfaceIntegrator
-        needs_tail = integ.kind == _abi.DR_INTEGRATOR_PATH and integ.maxDepth >= 3
-        if needs_tail and li_draws is None:
-            raise ValueError("serial_samples: a PathIntegrator with maxDepth >= 3 draws inside Li; pass li_draws")
-        n1D, n2D = self.slot_counts(renderer, scene)
-        e = renderer.camera.film.getSampleExtent()
-        x0, x1, y0, y1 = GetSubWindow(e[1] - e[0], e[3] - e[2], renderer.taskNum, max(1, renderer.taskCount))
-        pixels = self.pixelSampler.setup(x0, y0, x1 - x0, y1 - y0)
-        rng = DartRandom(renderer.taskNum)
-        vecs, tails = [], []
-        for px, py in pixels:
-            v = self.pixel_samples(int(px), int(py), n1D, n2D, rng, lambda i: rng)
-            vecs.append(v)
-            if needs_tail:
-                tails += [list(li_draws(int(px), int(py), v[i], rng)) for i in range(len(v))]
-        tail, cnt = _pack_tails(tails) if needs_tail else (None, None)
-        return HostBufferSampler(self.camera, self.samplesPerPixel, pixels, np.concatenate(vecs), tail, cnt)
+        """The reference's own stream (_serial_host_buffer), pixel after pixel in the pixel sampler's order.  Returns a HostBufferSampler.
+        li_draws(px, py, vector, rng): required for a PathIntegrator with maxDepth >= 3 (beyond its third vertex), unused otherwise."""
+        def walk(n1D, n2D, rng):
+            e = renderer.camera.film.getSampleExtent()
+            x0, x1, y0, y1 = GetSubWindow(e[1] - e[0], e[3] - e[2], renderer.taskNum, max(1, renderer.taskCount))
+            for px, py in self.pixelSampler.setup(x0, y0, x1 - x0, y1 - y0):
+                yield int(px), int(py), self.pixel_samples(int(px), int(py), n1D, n2D, rng, lambda i: rng)
+        return _serial_host_buffer(self, renderer, scene, li_draws, self.samplesPerPixel, walk)
 
 
 class AdaptiveSampler(_Sampler):
@@ -380,8 +382,6 @@ class HaltonSampler(_Sampler):
     def maximumSampleCount(self):  # :50-52
         return 1
 
-    slot_counts = StratifiedSampler.slot_counts
-
     @staticmethod
     def window(renderer):
         """(left, top, width, height) of the renderer's task: GetSubWindow's extents of the sampler extent, as the reference hands them on."""
@@ -417,22 +417,11 @@ class HaltonSampler(_Sampler):
         """The reference's own stream: ONE RNG(taskNum) (sampler_renderer.dart:137) through the accepted samples' LatinHypercube draws and
         through Li, in index order.  Returns a HostBufferSampler at one sample per pixel_xy row (samples are not grouped by pixel).
         li_draws(px, py, vector, rng): as for StratifiedSampler.serial_samples."""
-        integ = renderer.surfaceIntegrator
-        needs_tail = integ.kind == _abi.DR_INTEGRATOR_PATH and integ.maxDepth >= 3
-        if needs_tail and li_draws is None:
-            raise ValueError("serial_samples: a PathIntegrator with maxDepth >= 3 draws inside Li; pass li_draws")
-        n1D, n2D = self.slot_counts(renderer, scene)
-        rng = DartRandom(renderer.taskNum)
-        pixels, vecs, tails = [], [], []
-        for k, imageX, imageY in self.accepted(*self.window(renderer)):
-            xy, v = self.sample_vector(k, imageX, imageY, n1D, n2D, rng)
-            pixels.append(xy)
-            vecs.append(v)
-            if needs_tail:
-                tails.append(list(li_draws(xy[0], xy[1], v, rng)))
-        tail, cnt = _pack_tails(tails) if needs_tail else (None, None)
-        nf = 5 + sum(n1D) + 2 * sum(n2D)
-        return HostBufferSampler(self.camera, 1, np.array(pixels, np.int32).reshape(-1, 2), np.array(vecs, np.float32).reshape(-1, nf), tail, cnt)
+        def walk(n1D, n2D, rng):
+            for k, imageX, imageY in self.accepted(*self.window(renderer)):
+                xy, v = self.sample_vector(k, imageX, imageY, n1D, n2D, rng)
+                yield xy[0], xy[1], v[None, :]
+        return _serial_host_buffer(self, renderer, scene, li_draws, 1, walk)
 
 
 class RandomSampler(_Sampler):
@@ -465,8 +454,6 @@ class RandomSampler(_Sampler):
     def maximumSampleCount(self):  # :43-45
         return self.samplesPerPixel
 
-    slot_counts = StratifiedSampler.slot_counts
-
     def pixel_samples(self, px, py, n1D, n2D, sample_rng):
         """The loop of getMoreSamples (:65-85) for one pixel: [spp, 5 + sum(n1D) + 2 sum(n2D)] f32 in the C ABI's field order, the image
         sample as the f32 of its fraction inside the pixel (the reference's imageX is the double u + px), time raw (the Lerp over the shutter
@@ -485,26 +472,14 @@ class RandomSampler(_Sampler):
         StratifiedSampler.serial_samples.  passes: as written, getMoreSamples walks the pixel list samplesPerPixel times in FULL_SAMPLING
         (:50-56 count walks, :62 hands out samplesPerPixel samples per call); the device traces the first walk, the default here, and
         passes = samplesPerPixel continues the same stream through all of them (the pixel list repeats)."""
-        integ = renderer.surfaceIntegrator
-        needs_tail = integ.kind == _abi.DR_INTEGRATOR_PATH and integ.maxDepth >= 3
-        if needs_tail and li_draws is None:
-            raise ValueError("serial_samples: a PathIntegrator with maxDepth >= 3 draws inside Li; pass li_draws")
-        if not 1 <= int(passes) <= self.samplesPerPixel:
-            raise ValueError("serial_samples: passes must be between 1 and samplesPerPixel")
-        n1D, n2D = self.slot_counts(renderer, scene)
-        e = renderer.camera.film.getSampleExtent()
-        x0, x1, y0, y1 = GetSubWindow(e[1] - e[0], e[3] - e[2], renderer.taskNum, max(1, renderer.taskCount))
-        pixels = np.concatenate([self.pixelSampler.setup(x0, y0, x1 - x0, y1 - y0)] * int(passes))
-        rng = DartRandom(renderer.taskNum)
-        vecs, tails = [], []
-        for px, py in pixels:
-            v = self.pixel_samples(int(px), int(py), n1D, n2D, lambda i: rng)
-            vecs.append(v)
-            if needs_tail:
-                tails += [list(li_draws(int(px), int(py), v[i], rng)) for i in range(len(v))]
-        tail, cnt = _pack_tails(tails) if needs_tail else (None, None)
-        nf = 5 + sum(n1D) + 2 * sum(n2D)
-        return HostBufferSampler(self.camera, self.samplesPerPixel, pixels, np.concatenate(vecs) if vecs else np.zeros((0, nf), np.float32), tail, cnt)
+        def walk(n1D, n2D, rng):
+            if not 1 <= int(passes) <= self.samplesPerPixel:  # (behind the shared helper's own refusal, where it always ran)
+                raise ValueError("serial_samples: passes must be between 1 and samplesPerPixel")
+            e = renderer.camera.film.getSampleExtent()
+            x0, x1, y0, y1 = GetSubWindow(e[1] - e[0], e[3] - e[2], renderer.taskNum, max(1, renderer.taskCount))
+            for px, py in np.concatenate([self.pixelSampler.setup(x0, y0, x1 - x0, y1 - y0)] * int(passes)):
+                yield int(px), int(py), self.pixel_samples(int(px), int(py), n1D, n2D, lambda i: rng)
+        return _serial_host_buffer(self, renderer, scene, li_draws, self.samplesPerPixel, walk)
 
 
 class HostBufferSampler(_Sampler):

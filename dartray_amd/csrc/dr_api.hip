@@ -289,17 +289,14 @@ int dr_init(int device) {
 }
 
 int32_t dr_sample_floats(int32_t integrator, uint32_t nlights) {
-  // SURVEY.md Appendix B.  Path: 3 x (light 1D+2D, lightNum 1D, bsdf 1D+2D, path 1D+2D) + tau + scatter.
-  if (integrator == DR_INTEGRATOR_PATH) return 5 + 14 + 18;
-  // strategy "one" (direct_lighting_integrator.dart:82-87): light component, lightNum, BSDF component + tau + scatter; light position, BSDF direction
-  if (integrator == DR_INTEGRATOR_DIRECT_ONE) return 5 + 5 + 4;
-  if (integrator == DR_INTEGRATOR_WHITTED) return 5 + 2;  // WhittedIntegrator has no requestSamples: tau + scatter only
-  return 5 + (2 * (int)nlights + 2) + 4 * (int)nlights;
+  // kIntegratorTraits' slots (dr_host.h); a value that names no integrator counts as DirectLighting "all", as ever
+  return integratorSlots(knownIntegrator(integrator) ? (IntegratorKind)integrator : IntegratorKind::DirectAll, nullptr, nlights).nFloats();
 }
 
 int32_t dr_scene_sample_floats(const DrScene* scene, int32_t integrator) {
   if (!scene) return -1;
-  return integrator == DR_INTEGRATOR_DIRECT_ALL ? scene->dlNFloats : dr_sample_floats(integrator, scene->d.nlights);  // ("all": the lights' nsamples decide)
+  if (!knownIntegrator(integrator)) return dr_sample_floats(integrator, scene->d.nlights);
+  return integratorSlots((IntegratorKind)integrator, scene, scene->d.nlights).nFloats();  // ("all": the lights' nsamples decide)
 }
 
 int dr_scene_get_trace_kernels(const DrScene* sc, uint32_t out[2]) {
@@ -463,22 +460,17 @@ int planRender(RenderPlan& P) {
   if (P.traits->pow2Spp && (spp <= 0 || (spp & (spp - 1)) != 0)) return fail(DR_ERR_INVALID, "spp must be a power of two (low_discrepancy_sampler.dart:43-49)");
   if (spp > 4096) return fail(DR_ERR_UNSUPPORTED, "spp > 4096 (one pixel's shuffle table of a 16-pixel sampler group would not fit the LDS)");
   // ---- the integrator, the camera and the film into rp; the state layout; the stages ----
-  if (rd->integrator != DR_INTEGRATOR_PATH && rd->integrator != DR_INTEGRATOR_DIRECT_ALL && rd->integrator != DR_INTEGRATOR_DIRECT_ONE &&
-      rd->integrator != DR_INTEGRATOR_WHITTED)
-    return fail(DR_ERR_INVALID, "unknown integrator");
-  // WhittedIntegrator (whitted_integrator.dart:26-72): no sample slots of its own, one stage per light, the specular recursion below
-  P.whitted = rd->integrator == DR_INTEGRATOR_WHITTED;
-  if (P.whitted && rd->max_depth < 1) return fail(DR_ERR_INVALID, "whitted integrator: max_depth must be at least 1 (maxdepth counts the camera vertex: ray.depth + 1 < maxDepth)");
+  if (!knownIntegrator(rd->integrator)) return fail(DR_ERR_INVALID, "unknown integrator");
+  P.integrator = (IntegratorKind)rd->integrator;  // (kIntegratorTraits' static_assert: the kinds are the ABI's values)
+  P.integ = &kIntegratorTraits[rd->integrator];
+  if (P.integ->depthBelowOne && rd->max_depth < 1) return fail(DR_ERR_INVALID, P.integ->depthBelowOne);
   if (rd->max_depth < 0 || rd->max_depth > 64) return fail(DR_ERR_INVALID, "max_depth out of range");
-  if (P.whitted && P.sampler == SamplerKind::Adaptive)
-    return fail(DR_ERR_UNSUPPORTED, "whitted integrator: the adaptive sampler is not supported (its second pass over the rounds of the specular recursion has no test; every other sampler mode is)");
-  P.direct = rd->integrator != DR_INTEGRATOR_PATH && !P.whitted;
-  const bool directOne = rd->integrator == DR_INTEGRATOR_DIRECT_ONE;  // strategy "one": the last entry of the scene's stage table, an arithmetic slot layout
+  if (P.integ->adaptive && P.sampler == SamplerKind::Adaptive) return fail(DR_ERR_UNSUPPORTED, P.integ->adaptive);
   // DirectLighting over mirror / glass recurses through SpecularReflect / SpecularTransmit (integrator.dart:187-290):
   // an explicit per-slot stack and one round of the stage loop per vertex of the ray tree (k_shade_spec); so does Whitted
-  P.dlSpec = (P.direct || P.whitted) && sc->hasSpecular;
+  P.dlSpec = P.integ->specularRounds && sc->hasSpecular;
   // k_env (dr_kernels.hip): the environment-map work of a plain-triangle scene's path stages runs in its own kernel
-  P.envStage = rd->integrator == DR_INTEGRATOR_PATH && sc->d.hasEnv && !(sc->d.nquads || sc->d.hasSpec || sc->d.srec);
+  P.envStage = P.integ->pathStages && sc->d.hasEnv && !(sc->d.nquads || sc->d.hasSpec || sc->d.srec);
   // State layout (see LayoutOps): the four-slot sub-tiles for the renders whose lists thin out early.  Which one is MEASURED on
   // the render's own work: the first calibration batch -- rendered into the film like any other -- runs in the 64-slot layout
   // and its stage lists say how fast the paths die; when less than half of the slots are still alive at the second bounce the
@@ -486,7 +478,7 @@ int planRender(RenderPlan& P) {
   // DARTRAY_STATE_LAYOUT=64|4 forces one, dr_scene_set_state_layout stores one; renders too small for a pilot keep round 3's
   // rule (plain-triangle scenes under an environment map: sp4).
   const DrOpt layoutEnv = dr_opt("DARTRAY_STATE_LAYOUT");
-  P.layoutKnown = layoutEnv || sc->stateLayout != 0 || rd->integrator != DR_INTEGRATOR_PATH || !P.traits->pixelBound;  // (not pixel bound: no pilot)
+  P.layoutKnown = layoutEnv || sc->stateLayout != 0 || !P.integ->pathStages || !P.traits->pixelBound;  // (not pixel bound: no pilot)
   const bool sparseLayout = layoutEnv ? layoutEnv.toInt(0) == 4 : (sc->stateLayout ? sc->stateLayout == 4 : P.envStage);
   P.L = sparseLayout ? &kLayoutSp4 : &kLayout64;
   P.maxStateWords = P.layoutKnown ? P.L->stateWords : std::max(kLayout64.stateWords, kLayoutSp4.stateWords);
@@ -508,17 +500,29 @@ int planRender(RenderPlan& P) {
   rp.sppShift = 0;
   while ((1 << rp.sppShift) < P.spp) ++rp.sppShift;
   rp.nLights = (int)sc->d.nlights;
-  rp.nFloats = P.direct && !directOne ? sc->dlNFloats : dr_sample_floats(rd->integrator, sc->d.nlights);
-  rp.n1D = directOne ? 5 : (P.direct ? sc->dlN1D : (P.whitted ? 2 : 14));  // (Whitted: only the volume integrator's tau + scatter slots)
-  rp.blocks = P.direct && !directOne && sc->dlMulti ? sc->dlBlocks.p : nullptr;
+  const SlotCounts slots = integratorSlots(P.integrator, sc, sc->d.nlights);
+  rp.nFloats = slots.nFloats();
+  rp.n1D = slots.n1D;
+  rp.blocks = P.integ->sceneSlots && sc->dlMulti ? sc->dlBlocks.p : nullptr;
   rp.nBlocks = sc->dlNBlocks;
-  rp.dstages = directOne ? sc->dlStages.p + sc->dlNStages : sc->dlStages.p;
-  rp.nDirectStages = directOne ? (sc->d.nlights ? 1 : 0) : (P.direct ? sc->dlNStages : 0);
+  // the stages: where a stage's DirectStage entry comes from, and how many stages a round of the stage loop runs
+  rp.dstages = sc->dlStages.p;
+  rp.nDirectStages = 0;
+  switch (P.integrator) {  // (no default: -Wall names a kind this forgets)
+    case IntegratorKind::DirectAll: rp.nDirectStages = sc->dlNStages; P.nStages = rp.nDirectStages + 1; break;  // the scene's table from its start
+    case IntegratorKind::DirectOne:  // strategy "one": the last entry of the scene's stage table, an arithmetic slot layout
+      rp.dstages += sc->dlNStages;
+      rp.nDirectStages = sc->d.nlights ? 1 : 0;
+      P.nStages = rp.nDirectStages + 1;
+      break;
+    case IntegratorKind::Path: P.nStages = rd->max_depth + 2; break;
+    case IntegratorKind::Whitted: P.nStages = rp.nLights + 1; break;  // one per light
+  }
   rp.dlSpecular = P.dlSpec ? 1 : 0;
-  rp.deferredNee = rd->integrator == DR_INTEGRATOR_PATH ? 1 : 0;
+  rp.deferredNee = P.integ->pathStages ? 1 : 0;
   rp.genMask = 0ull;
   rp.genSlowDraws = dr_opt("DARTRAY_GEN_SLOW_DRAWS").set ? 1 : 0;
-  if (!(P.traits->deviceGenerated && P.traits->floatForm) && rd->integrator == DR_INTEGRATOR_PATH && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
+  if (!(P.traits->deviceGenerated && P.traits->floatForm) && P.integ->pathStages && !rp.blocks && !dr_opt("DARTRAY_GEN_ALL_BLOCKS").set) {
     // What the path kernels read of a pixel sample (dr_kernels.hip: k_raygen, load_shade_in, k_film): the image sample,
     // the lens sample of a thin-lens camera, and per SAMPLE_DEPTH level b <= maxDepth the light number, the light
     // sample (component + position), the BSDF and path directions; the two uComponent slots only where a material has
@@ -535,10 +539,9 @@ int planRender(RenderPlan& P) {
   rp.samplerMode = P.sampler == SamplerKind::Adaptive ? DR_SAMPLER_COUNTER : rd->sampler_mode;  // (both adaptive passes are the LD sampler's keyed streams)
   rp.seed = (uint64_t)rd->seed;
   const int perNee = rp.nLights > 0 ? 7 : 0;
-  P.needTail = rd->integrator == DR_INTEGRATOR_PATH && rd->max_depth >= 3 ? (rd->max_depth - 2) * (perNee + 3) + std::max(0, rd->max_depth - 3) : 0;
+  P.needTail = P.integ->pathStages && rd->max_depth >= 3 ? (rd->max_depth - 2) * (perNee + 3) + std::max(0, rd->max_depth - 3) : 0;
   rp.maxTail = rd->max_tail;
   P.sgrid = g_numCU;  // the shade launchers size their grid per CU (DR_SHADE_GRID), grid-stride over the active list
-  P.nStages = rd->integrator == DR_INTEGRATOR_PATH ? rd->max_depth + 2 : (P.whitted ? rp.nLights + 1 : rp.nDirectStages + 1);
   // ---- the mode's rules that have always run behind the integrator's, max_depth's and the camera's refusals above (strat_xsamples reads only spp, but a descriptor
   // that also names an unknown integrator keeps that refusal); which pixels: the caller's list, the task's / tile share's, or -- not pixel bound -- a window ----
   if (P.sampler == SamplerKind::Stratified) {
@@ -548,7 +551,7 @@ int planRender(RenderPlan& P) {
   }
   // roundSize is the identity (stratified_sampler.dart:63-65, halton_sampler.dart:102-104, random_sampler.dart:90-92) while the scene's DirectLighting slot layout is
   // LowDiscrepancySampler's rounded one, so a light's nsamples must be its own rounding
-  if (P.traits->identityRoundSize && rd->integrator == DR_INTEGRATOR_DIRECT_ALL)
+  if (P.traits->identityRoundSize && P.integ->sceneSlots)
     for (int n : sc->lightNSamples)
       if (n > 1 && (n & (n - 1)) != 0) return fail(DR_ERR_UNSUPPORTED, P.traits->identityRoundSize);
   if (P.sampler == SamplerKind::Adaptive && rp.blocks && P.adaptive.max > 1024)
@@ -683,7 +686,7 @@ RenderPlan secondPass(const RenderPlan& P, uint32_t nFlagged) {
 }
 
 bool lazyGenFor(const RenderPlan& P) {
-  return P.sf.compact && P.rp.genMask != 0ull && P.rd->integrator == DR_INTEGRATOR_PATH && P.coherentCamera && !P.sc->d.nquads && P.spp >= 64 &&
+  return P.sf.compact && P.rp.genMask != 0ull && P.integ->pathStages && P.coherentCamera && !P.sc->d.nquads && P.spp >= 64 &&
          !dr_opt("DARTRAY_LAZY_GEN").isZero();
 }
 
@@ -795,6 +798,16 @@ int dumpBatch(const RenderPlan& P, const int2* pix, uint32_t np, uint32_t nslots
   return DR_OK;
 }
 
+// dr_scene_last_render_info's word 3: -1 (rounds 4-5 reported the treelet-parked traversal's parking rounds here), or the integrator and
+// the shading kernels of its own that ran -- bit 8: k_shade_whitted, bit 9: k_shade_spec
+int32_t lastInfoWord(const RenderPlan& P) {
+  switch (P.integrator) {  // (no default: -Wall names a kind this forgets)
+    case IntegratorKind::DirectAll: case IntegratorKind::Path: case IntegratorKind::DirectOne: break;
+    case IntegratorKind::Whitted: return DR_INTEGRATOR_WHITTED | 0x100 | (P.dlSpec ? 0x200 : 0);
+  }
+  return -1;
+}
+
 }  // namespace
 
 extern "C" {
@@ -867,8 +880,7 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
   sc->lastInfo[0] = P.L == &kLayoutSp4 ? 4 : 64;
   sc->lastInfo[1] = P.L->trace_kernel_id(sc->d, 0);
   sc->lastInfo[2] = P.L->trace_kernel_id(sc->d, 1);
-  // (rounds 4-5 reported the treelet-parked traversal's parking rounds here; -1 since)  A Whitted render: the integrator and its shading kernels
-  sc->lastInfo[3] = !P.whitted ? -1 : DR_INTEGRATOR_WHITTED | 0x100 | (P.dlSpec ? 0x200 : 0);  // bit 8: k_shade_whitted, bit 9: k_shade_spec
+  sc->lastInfo[3] = lastInfoWord(P);
   sc->lastInfo[4] = pilot.setsRun;
   sc->lastInfo[5] = (int32_t)std::min<uint64_t>(0x7fffffff, nBatches);
   sc->lastInfo[6] = P.tgrid / std::max(1, g_numCU);

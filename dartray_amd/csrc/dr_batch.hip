@@ -229,9 +229,14 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
   hipEvent_t evS = sc->getEvent();
   (void)hipEventRecord(evS, s);
   const BatchState stS = shadeState();
-  if (rd->integrator == DR_INTEGRATOR_PATH) L.shade_path(sc->d, rp, stS, q, b, P.sgrid, s);
-  else if (P.whitted) L.shade_whitted(sc->d, rp, stS, q, b, P.sgrid, s);
-  else L.shade_direct(sc->d, rp, stS, q, b, P.sgrid, s);
+  // the integrator's shading launcher, and the rays it queues: closest-hit (continuation / MIS) and any-hit (shadow) rays, or -- a Whitted stage --
+  // one shadow ray per slot and nothing else (no MIS ray, no continuation: the child rays are the rounds')
+  bool shadowRaysOnly = false;
+  switch (P.integrator) {  // (no default: -Wall names a kind this forgets)
+    case IntegratorKind::Path: L.shade_path(sc->d, rp, stS, q, b, P.sgrid, s); break;
+    case IntegratorKind::DirectAll: case IntegratorKind::DirectOne: L.shade_direct(sc->d, rp, stS, q, b, P.sgrid, s); break;
+    case IntegratorKind::Whitted: L.shade_whitted(sc->d, rp, stS, q, b, P.sgrid, s); shadowRaysOnly = true; break;
+  }
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {
     evMid = sc->getEvent();
@@ -249,7 +254,7 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
     slog[b + 1].s1 = evS1;
   }
   if (b + 1 >= P.nStages) return DR_OK;
-  if (P.whitted) {  // a Whitted stage queues one shadow ray per slot and nothing else (no MIS ray, no continuation: the child rays are the rounds')
+  if (shadowRaysOnly) {
     trace(q.anyQ, q.nAny, 1, s, w.spill.p);
     if (log) logTrace(slog[b + 1], 1);
   } else if (sideBySide) {

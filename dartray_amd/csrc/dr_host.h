@@ -281,6 +281,44 @@ constexpr SamplerTraits kSamplerTraits[] = {
     {true, true, false, false, "halton sampler: a light's nsamples must be a power of two (HaltonSampler.roundSize is the identity, the scene's sample layout is the rounded one)"},  // Halton
     {true, true, true, true, "random sampler: a light's nsamples must be a power of two (RandomSampler.roundSize is the identity, the scene's sample layout is the rounded one)"}};  // Random
 
+// The surface integrators of the C ABI (DrRenderDesc.integrator) as the planner sees them, and what each one declares: every decision of
+// dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
+// source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
+enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted };
+struct IntegratorTraits {
+  bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
+  int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
+  bool pathStages;       // k_shade_path's stages, max_depth + 2 of them: deferred NEE, RNG draws beyond the sample vector, the blocks the path reads
+                         //   (genMask, lazy generation), k_env, the layout pilot and the sparse default layout
+  bool specularRounds;   // mirror / glass recurse through k_shade_spec: one round of the stage loop per vertex of a slot's ray tree
+  const char* depthBelowOne;  // max_depth counts the camera vertex, so it is at least 1: the refusal's text, else null
+  const char* adaptive;       // the adaptive sampler is not supported: the refusal's text, else null
+};
+constexpr IntegratorTraits kIntegratorTraits[] = {
+    {true, 0, 0, false, true, nullptr, nullptr},    // DirectAll: per light a light and a BSDF slot pair of roundSize(nsamples) entries (2n + 2 and 2n slots at nsamples 1)
+    {false, 14, 9, true, false, nullptr, nullptr},  // Path: 3 x (light 1D+2D, lightNum 1D, bsdf 1D+2D, path 1D+2D) + tau + scatter
+    // DirectOne (direct_lighting_integrator.dart:82-87): light component, lightNum, BSDF component + tau + scatter; light position, BSDF direction
+    {false, 5, 2, false, true, nullptr, nullptr},
+    // Whitted (whitted_integrator.dart:26-72): no requestSamples -- tau + scatter only; one stage per light, any-hit rays only
+    {false, 2, 0, false, true, "whitted integrator: max_depth must be at least 1 (maxdepth counts the camera vertex: ray.depth + 1 < maxDepth)",
+     "whitted integrator: the adaptive sampler is not supported (its second pass over the rounds of the specular recursion has no test; every other sampler mode is)"}};
+static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
+                  (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
+                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 4, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
+inline bool knownIntegrator(int32_t v) { return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])); }
+
+// An integrator's sample slots; the floats of a sample vector are computed here and nowhere else.
+struct SlotCounts {
+  int n1D, n2D;
+  int nFloats() const { return 5 + n1D + 2 * n2D; }
+};
+// sc null: DirectAll as of nlights lights of nsamples 1
+inline SlotCounts integratorSlots(IntegratorKind k, const DrScene* sc, uint32_t nlights) {
+  const IntegratorTraits& t = kIntegratorTraits[(int)k];
+  if (!t.sceneSlots) return {t.n1D, t.n2D};
+  return sc ? SlotCounts{sc->dlN1D, (sc->dlNFloats - 5 - sc->dlN1D) / 2} : SlotCounts{2 * (int)nlights + 2, 2 * (int)nlights};
+}
+
 struct RenderPlan {
   DrScene* sc = nullptr;
   const DrRenderDesc* rd = nullptr;
@@ -290,8 +328,9 @@ struct RenderPlan {
   SampleForm sf;
   const LayoutOps* L = nullptr;  // state layout of the NEXT batch (the layout pilot decides it after the first calibration batch)
   int spp = 0;
-  bool direct = false, dlSpec = false, envStage = false, packedTail = false;
-  bool whitted = false;  // DR_INTEGRATOR_WHITTED: k_shade_whitted's stages (one per light, any-hit rays only); dlSpec: k_shade_spec's rounds behind them
+  IntegratorKind integrator = IntegratorKind::Path;
+  const IntegratorTraits* integ = &kIntegratorTraits[(int)IntegratorKind::Path];
+  bool dlSpec = false, envStage = false, packedTail = false;  // dlSpec: k_shade_spec's rounds run (integ->specularRounds over a scene with mirror / glass)
   SamplerKind sampler = SamplerKind::LowDiscrepancy;
   const SamplerTraits* traits = &kSamplerTraits[(int)SamplerKind::LowDiscrepancy];
   struct { int x = 0; } strat;  // Stratified: xPixelSamples (yPixelSamples = spp / x)
