@@ -15,6 +15,7 @@ DR_INTEGRATOR_DIRECT_ALL = 0
 DR_INTEGRATOR_PATH = 1
 DR_INTEGRATOR_DIRECT_ONE = 2
 DR_INTEGRATOR_WHITTED = 3
+DR_INTEGRATOR_AO = 4  # ao_nsamples / ao_mindist / ao_maxdist; max_depth is not read
 DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
 DR_SAMPLER_STRATIFIED = 2
@@ -109,6 +110,20 @@ class DrFilm(C.Structure):
                 ("filter_xw", C.c_double), ("filter_yw", C.c_double), ("filter_table", C.c_float * 256)]
 
 
+class _Overlay:
+    """A value that shares storage with other fields of a ctypes struct (a C union member, or padding the C header names): read and written
+    in place at its byte offset, and no entry of _fields_, whose list stays the struct's own fields."""
+
+    def __init__(self, offset, ctype):
+        self.offset, self.ctype = offset, ctype
+
+    def __get__(self, obj, cls=None):
+        return self if obj is None else self.ctype.from_buffer(obj, self.offset).value
+
+    def __set__(self, obj, value):
+        self.ctype.from_buffer(obj, self.offset).value = value
+
+
 class DrRenderDesc(C.Structure):
     _fields_ = [("camera", DrCamera), ("film", DrFilm),
                 ("integrator", C.c_int32), ("max_depth", C.c_int32), ("spp", C.c_int32), ("sampler_mode", C.c_int32),
@@ -119,6 +134,11 @@ class DrRenderDesc(C.Structure):
                 ("nsamples", C.c_int64),
                 ("pixel_xy", C.c_void_p), ("sample_vec", C.c_void_p), ("sample_stride", C.c_int32),
                 ("tail", C.c_void_p), ("max_tail", C.c_int32), ("tail_offsets", C.c_void_p)]
+    # DR_INTEGRATOR_AO's three parameters (include/dartray_hip.h): the padding behind sample_stride, and unions with the two tail pointers,
+    # which that integrator does not read
+    ao_nsamples = _Overlay(1324, C.c_int32)
+    ao_mindist = _Overlay(1328, C.c_double)
+    ao_maxdist = _Overlay(1344, C.c_double)
 
 
 class DrRenderStats(C.Structure):

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _abi
-from .samplers import HaltonSampler
+from .samplers import AdaptiveSampler, HaltonSampler, RoundUpPow2
 
 
 class PathIntegrator:
@@ -79,6 +79,53 @@ class WhittedIntegrator:
         return WhittedIntegrator((params or {}).get("maxdepth", 5))
 
 
+class AmbientOcclusionIntegrator:
+    """surface_integrators/ambient_occlusion_integrator.dart:23-65: nSamples = RoundUpPow2(ns) occlusion rays Ray(p, w, minDist, maxDist) over the
+    hemisphere of the camera hit's geometric normal, Li = nClear / nSamples.  On the device DR_INTEGRATOR_AO (k_shade_ao)."""
+
+    def __init__(self, nSamples=2048, minDist=1.0e-4, maxDist=float("inf")):
+        if int(nSamples) < 1:
+            raise ValueError("ambient occlusion integrator: nsamples must be at least 1")
+        self.nSamples = RoundUpPow2(int(nSamples))                 # :24-26
+        if self.nSamples > 4096:
+            raise ValueError("ambient occlusion integrator: nsamples above 4096 after rounding up to a power of two (the samplers' cap)")
+        self.minDist, self.maxDist = float(minDist), float(maxDist)
+        if not self.minDist >= 0.0:
+            raise ValueError("ambient occlusion integrator: mindist must not be negative")
+        if not self.maxDist > self.minDist:
+            raise ValueError("ambient occlusion integrator: maxdist must be greater than mindist")
+
+    kind = _abi.DR_INTEGRATOR_AO
+    maxDepth = 1  # (not read by the device under this integrator; SamplerRenderer.describe marshals every integrator's)
+    li_draws_recorded = False  # (the scramble's two randomUint() are keyed (pixel, sample) draws in every sampler mode, DESIGN.md 2.13)
+
+    def requestSamples(self, sampler, scene):
+        """No requestSamples in the reference: no slots of its own."""
+        return [], []
+
+    def check_sampler(self, sampler):
+        """SamplerRenderer.describe: what this integrator asks of the renderer's sampler."""
+        if isinstance(sampler, AdaptiveSampler):
+            raise ValueError("ambient occlusion integrator: the adaptive sampler is not supported (its second pass over the rounds of "
+                             "occlusion rays has no test; every other sampler mode is)")
+        if getattr(sampler, "sampler_mode", None) == _abi.DR_SAMPLER_HOST_BUFFER and sampler.li_seed is None:
+            raise ValueError("an AmbientOcclusionIntegrator draws its scramble from the keyed (pixel, sample) streams in every sampler mode: "
+                             "give the HostBufferSampler the seed of the render it replays (seed=...)")
+
+    def to_abi(self, d):
+        """SamplerRenderer.describe, behind the sampler's own fields: the three parameters (they share storage with the tail pointers, which
+        this integrator does not read: include/dartray_hip.h)."""
+        d.ao_nsamples = self.nSamples
+        d.ao_mindist = self.minDist
+        d.ao_maxdist = self.maxDist
+
+    @staticmethod
+    def Create(params=None):
+        """AmbientOcclusionIntegrator.Create (:55-60): `nsamples` 2048, `maxdist` infinity, `mindist` 1e-4."""
+        ps = params or {}
+        return AmbientOcclusionIntegrator(ps.get("nsamples", 2048), ps.get("mindist", 1.0e-4), ps.get("maxdist", float("inf")))
+
+
 class EmissionIntegrator:
     """volume_integrators/emission_integrator.dart with no VolumeRegion: T = 1,
     Lv = 0; its only effect on the path is the two 1-D sample slots it requests."""
@@ -128,7 +175,11 @@ class SamplerRenderer:
         d.max_depth = self.surfaceIntegrator.maxDepth
         d.task_num, d.task_count = self.taskNum, self.taskCount
         d.tile_rank, d.tile_count, d.tile_size = self.tileRank, self.tileCount, self.tileSize
-        return d, self.sampler.to_abi(d)
+        keep = self.sampler.to_abi(d)
+        fields = getattr(self.surfaceIntegrator, "to_abi", None)  # an integrator with parameters beyond maxDepth, behind the sampler's fields
+        if fields:
+            fields(d)
+        return d, keep
 
     def generate_samples(self, scene, pixels):
         """dr_generate_samples: the device sampler's vectors for the raster pixels `pixels` ([n, 2]) -> [n * spp, nFloats] f32

@@ -517,6 +517,25 @@ int planRender(RenderPlan& P) {
       break;
     case IntegratorKind::Path: P.nStages = rd->max_depth + 2; break;
     case IntegratorKind::Whitted: P.nStages = rp.nLights + 1; break;  // one per light
+    case IntegratorKind::AmbientOcclusion: {
+      // AmbientOcclusionIntegrator (ambient_occlusion_integrator.dart:24-26,55-60): nSamples = RoundUpPow2(ns) occlusion rays per camera
+      // hit, one per stage.  A render holds at most CounterLayout::maxStages() stages, so the rays go in rounds of the stage loop, 128 to a round
+      // (a power of two: it divides every larger nSamples); a round is one stage more than its rays, since the last ray is folded in by a stage
+      // that queues nothing.
+      if (rd->ao_nsamples < 1) return fail(DR_ERR_INVALID, "ambient occlusion integrator: nsamples must be at least 1");
+      uint32_t ns = 1;
+      while (ns < (uint32_t)rd->ao_nsamples) ns <<= 1;  // RoundUpPow2 (common.dart:117-125)
+      if (ns > 4096) return fail(DR_ERR_INVALID, "ambient occlusion integrator: nsamples above 4096 after rounding up to a power of two (the samplers' cap)");
+      if (!(rd->ao_mindist >= 0.0)) return fail(DR_ERR_INVALID, "ambient occlusion integrator: mindist must not be negative");
+      if (!(rd->ao_maxdist > rd->ao_mindist)) return fail(DR_ERR_INVALID, "ambient occlusion integrator: maxdist must be greater than mindist");
+      P.ao.nSamples = (int)ns;
+      P.ao.perRound = std::min(P.ao.nSamples, 128);
+      P.ao.rounds = P.ao.nSamples / P.ao.perRound;
+      P.ao.minDist = rd->ao_mindist;
+      P.ao.maxDist = rd->ao_maxdist;
+      P.nStages = P.ao.perRound + 1;
+      break;
+    }
   }
   rp.dlSpecular = P.dlSpec ? 1 : 0;
   rp.deferredNee = P.integ->pathStages ? 1 : 0;
@@ -711,6 +730,10 @@ int prepareRender(RenderPlan& P) {
     HIP_TRY(sc->ws.roundA.alloc(sc->ws.cap));
     HIP_TRY(sc->ws.roundB.alloc(sc->ws.cap));
   }
+  if (P.ao.rounds > 1) {  // ambient occlusion in rounds: the slots that hit, handed from a round's last stage to the next round's first
+    HIP_TRY(sc->ws.roundA.alloc(sc->ws.cap));
+    HIP_TRY(sc->ws.roundB.alloc(sc->ws.cap));
+  }
   if (P.envStage) HIP_TRY(sc->ws.envQ.alloc(sc->ws.cap));
   P.tgrid = traceGrid();
   rc = ensureSpill(sc, sc->ws, P.tgrid);
@@ -804,6 +827,7 @@ int32_t lastInfoWord(const RenderPlan& P) {
   switch (P.integrator) {  // (no default: -Wall names a kind this forgets)
     case IntegratorKind::DirectAll: case IntegratorKind::Path: case IntegratorKind::DirectOne: break;
     case IntegratorKind::Whitted: return DR_INTEGRATOR_WHITTED | 0x100 | (P.dlSpec ? 0x200 : 0);
+    case IntegratorKind::AmbientOcclusion: return DR_INTEGRATOR_AO | 0x400;  // bit 10: k_shade_ao
   }
   return -1;
 }

@@ -224,8 +224,15 @@ StageQueues BatchRunner::stageQueues(int b, const uint32_t* roundQ, const uint32
 // Stage b: shade the active list (+ the environment-map kernel), generate the next bounce's sample blocks where paths are alive,
 // trace the continuation / MIS rays and the shadow rays the stage queued.
 int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t* nRound) {
-  const StageQueues q = stageQueues(b, roundQ, nRound);
+  StageQueues q = stageQueues(b, roundQ, nRound);
   const bool log = stageCounts && round == 0;
+  // ambient occlusion, the last stage of a round that another one follows: its output list -- the slots that hit, every one with rays still
+  // to send -- is the next round's input and must outlive the reset of the stage counters: it goes to a round list and a round word
+  if (P.integrator == IntegratorKind::AmbientOcclusion && b + 1 == P.nStages && round + 1 < P.ao.rounds) {
+    q.activeOut = (round & 1) ? w.roundB.p : w.roundA.p;
+    q.nActiveOut = C + CounterLayout::roundNext(round);
+    HIP_TRY(hipMemsetAsync(q.nActiveOut, 0, sizeof(uint32_t), s));
+  }
   hipEvent_t evS = sc->getEvent();
   (void)hipEventRecord(evS, s);
   const BatchState stS = shadeState();
@@ -236,6 +243,12 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
     case IntegratorKind::Path: L.shade_path(sc->d, rp, stS, q, b, P.sgrid, s); break;
     case IntegratorKind::DirectAll: case IntegratorKind::DirectOne: L.shade_direct(sc->d, rp, stS, q, b, P.sgrid, s); break;
     case IntegratorKind::Whitted: L.shade_whitted(sc->d, rp, stS, q, b, P.sgrid, s); shadowRaysOnly = true; break;
+    case IntegratorKind::AmbientOcclusion: {  // stage b of round `round`: ray b - 1 of the round folded in, ray b queued (the last stage only folds)
+      const int first = round * P.ao.perRound;
+      L.shade_ao(sc->d, rp, stS, q, P.ao.nSamples, b > 0 ? first + b - 1 : -1, b < P.ao.perRound ? first + b : -1, P.ao.minDist, P.ao.maxDist, P.sgrid, s);
+      shadowRaysOnly = true;
+      break;
+    }
   }
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {
@@ -376,7 +389,8 @@ int BatchRunner::run() {
       wc = 0;
     }
     if (stageCounts && round == 0) readCtrNow(&ctrBase);
-    trace(roundQ, nRound, 0, s, w.spill.p, nullptr, P.coherentCamera && roundQ == nullptr);  // camera rays (or this round's child rays)
+    // camera rays (or this round's child rays; a later round of ambient occlusion has none: its slots go on with their occlusion rays)
+    if (round == 0 || P.dlSpec) trace(roundQ, nRound, 0, s, w.spill.p, nullptr, P.coherentCamera && roundQ == nullptr);
     if (stageCounts && round == 0) {  // (before genBounce pushes its own event)
       logTrace(slog[0], 0);
       readCtrNow(&slog[0].ctr);
@@ -388,6 +402,11 @@ int BatchRunner::run() {
     for (int b = 0; b < P.nStages; ++b) {
       rc = stage(b, round, roundQ, nRound);
       if (rc) return rc;
+    }
+    if (round + 1 < P.ao.rounds) {  // ambient occlusion: the next 128 rays of every slot that hit (no count read back: the rounds are known)
+      roundQ = (round & 1) ? w.roundB.p : w.roundA.p;
+      nRound = C + CounterLayout::roundNext(round);
+      continue;
     }
     if (!P.dlSpec) break;
     bool done = false;

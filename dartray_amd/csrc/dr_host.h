@@ -62,7 +62,7 @@ struct Workspace {
   DevBuf<uint32_t> envQ;  // plain-triangle scenes under an environment map: k_env's list of a stage (cap entries)
   DevBuf<uint8_t> alive;  // lazy sample generation: [3][groups of 64 batch pixels] = a path of the group is alive at bounce 0 / 1 / 2
   size_t spillHalf = 0;
-  DevBuf<uint32_t> roundA, roundB;  // DirectLighting over mirror / glass: the slots whose child ray is traced next round
+  DevBuf<uint32_t> roundA, roundB;  // DirectLighting over mirror / glass: the slots whose child ray is traced next round; ambient occlusion: the slots that hit
   DevBuf<float> specFrames;         //   [maxDepth][cap] SpecFrame
   DevBuf<int32_t> specSp;           //   [cap]
   DevBuf<int2> pix;
@@ -254,7 +254,7 @@ struct SampleForm {
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
   X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
-  X(film, launch_film)
+  X(shade_ao, launch_shade_ao) X(film, launch_film)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -284,7 +284,7 @@ constexpr SamplerTraits kSamplerTraits[] = {
 // The surface integrators of the C ABI (DrRenderDesc.integrator) as the planner sees them, and what each one declares: every decision of
 // dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
 // source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
-enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted };
+enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion };
 struct IntegratorTraits {
   bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
   int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
@@ -301,10 +301,14 @@ constexpr IntegratorTraits kIntegratorTraits[] = {
     {false, 5, 2, false, true, nullptr, nullptr},
     // Whitted (whitted_integrator.dart:26-72): no requestSamples -- tau + scatter only; one stage per light, any-hit rays only
     {false, 2, 0, false, true, "whitted integrator: max_depth must be at least 1 (maxdepth counts the camera vertex: ray.depth + 1 < maxDepth)",
-     "whitted integrator: the adaptive sampler is not supported (its second pass over the rounds of the specular recursion has no test; every other sampler mode is)"}};
+     "whitted integrator: the adaptive sampler is not supported (its second pass over the rounds of the specular recursion has no test; every other sampler mode is)"},
+    // AmbientOcclusion (ambient_occlusion_integrator.dart:28-53): no requestSamples -- tau + scatter only; one any-hit ray per stage,
+    // nsamples of them per camera hit in rounds of the stage loop; max_depth is not read
+    {false, 2, 0, false, false, nullptr,
+     "ambient occlusion integrator: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"}};
 static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
                   (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
-                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 4, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
+                  (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 5, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
 inline bool knownIntegrator(int32_t v) { return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])); }
 
 // An integrator's sample slots; the floats of a sample vector are computed here and nowhere else.
@@ -340,6 +344,9 @@ struct RenderPlan {
   // Halton: a "pixel" of this plan is an INDEX of the task's sequence (npixTotal = wanted, spp = 1: one slot per accepted sample); a
   // batch is a range of indices, selected on the device before it runs.  win: the task's window: left, top, right, bottom (inclusive), delta = max(width, height)
   struct { int32_t win[5] = {0, 0, 0, 0, 0}; } halton;
+  // AmbientOcclusion: nSamples occlusion rays per camera hit, perRound of them in each of `rounds` rounds of the stage loop
+  // (a round is perRound + 1 stages: CounterLayout::maxStages() bounds it); the rays' extent
+  struct { int nSamples = 0, perRound = 0, rounds = 0; double minDist = 0.0, maxDist = 0.0; } ao;
   // the device sampler's launches for one batch (BatchRunner::loadSamples, the two sample dumps)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
   // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'

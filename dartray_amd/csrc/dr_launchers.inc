@@ -42,6 +42,10 @@ void launch_shade_direct(const DScene& sc, const RenderParams& rp, const BatchSt
 void launch_shade_spec(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int grid, hipStream_t s);
 // dr_shade_whitted.hip: stage `stage` of a WhittedIntegrator vertex (light stage - 1 folded in, light `stage` set up)
 void launch_shade_whitted(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int stage, int grid, hipStream_t s);
+// dr_shade_ao.hip: one stage of AmbientOcclusionIntegrator.Li -- occlusion ray `fold` of every slot folded into its count (< 0: none), ray `emit` queued
+// (< 0: none; 0: the camera hit set up first); the last ray folded: the slot's radiance nClear / nSamples
+void launch_shade_ao(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int nSamples, int fold, int emit,
+                     double minDist, double maxDist, int grid, hipStream_t s);
 void launch_film(const RenderParams& rp, const BatchState& st, const float* filterTable, uint32_t npix, float* film,
                  hipStream_t s);
 void launch_film_resolve(const float* film, int64_t npix, float* rgb, hipStream_t s);

@@ -13,6 +13,8 @@
 namespace DR_NS {
 #endif
 
+#include "dr_li_sampling.h"
+
 // ---------------------------------------------------------------------------
 // Stratified sampler (samplers/stratified_sampler.dart:67-124), DR_SAMPLER_STRATIFIED(_NOJITTER): float sample form.
 // Streams: kind 3 of (pixel, 0) -- the pixel's strata and shuffles, k_gen_strat_pixel; kind 4 of
@@ -120,12 +122,7 @@ __global__ void __launch_bounds__(256) k_gen_strat_lhs(RenderParams rp, BatchSta
 // compact form (the LD sampler's permuted index per (LD block, slot) + two scramble words per (LD block, pixel)) is evaluated as
 // its consumers evaluate it (sv_one / sv_pair in dr_kernels.hip): VanDerCorput for a 1-D value and the x of a pair, Sobol2 for the y.
 // ---------------------------------------------------------------------------
-DR_DEV float export_radical(uint32_t n, uint32_t scramble, bool sobol) {  // montecarlo.dart:486-504
-  if (!sobol) return (float)((__brev(n) ^ scramble) >> 8) * 5.9604644775390625e-8f;
-  for (uint32_t v = 1u << 31; n != 0; n >>= 1, v ^= v >> 1)
-    if (n & 1u) scramble ^= v;
-  return (float)(scramble >> 8) * 5.9604644775390625e-8f;
-}
+// (scrambled_radical: dr_li_sampling.h)
 __global__ void __launch_bounds__(256) k_export_samples(RenderParams rp, BatchState st, float* out, int stride) {
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (slot >= st.nslots) return;
@@ -143,7 +140,7 @@ __global__ void __launch_bounds__(256) k_export_samples(RenderParams rp, BatchSt
     const uint8_t* q = st.svIdx() + (size_t)(slot >> 6) * st.tileStride * 4 + (((size_t)k * 64 + (slot & 63u)) << st.idxShift);
     const uint32_t idx = st.idxShift ? (uint32_t)*(const uint16_t*)q : (uint32_t)*q;
     const uint32_t scr = st.svScr[(size_t)(2 * k + (second ? 1 : 0)) * st.pixCap + (slot >> rp.sppShift)];
-    o[f] = export_radical(idx, scr, second);
+    o[f] = scrambled_radical(idx, scr, second);
   }
 }
 

@@ -32,20 +32,11 @@ namespace DR_NS {
 #endif
 
 #include "dr_shade_common.h"
+#include "dr_li_sampling.h"  // li_stream
 
 // per-slot words of the draw numbering: the stream's generator state behind the last draw made (u32 lo, hi), the vertices shaded so far
 // with ray.depth + 1 < maxDepth, and the Specular* calls that had been made when the previous vertex started (i32)
 enum { W_LO = F_MISD, W_HI = F_MISD + 1, W_NR = F_MISPRIM, W_CALLS = F_MISLIGHT };
-
-// The sample's keyed in-Li stream (kind 2 of (pixel, sample): DESIGN.md 2.7) at its first draw.  In every sampler mode: the host-buffer
-// mode's recorded tail is not read (a ray tree's draws have no useful bound), its pixels and seed key the stream.
-DR_DEV DartRandom li_stream(const RenderParams& rp, const BatchState& st, uint32_t slot) {
-  const int2 xy = st.pix[slot >> rp.sppShift];
-  const uint64_t pixelIndex = (uint64_t)(xy.y - rp.extY0) * (uint64_t)rp.extW + (uint64_t)(xy.x - rp.extX0);
-  DartRandom rng;
-  rng.seed(dr_counter_key(rp.seed, pixelIndex, (uint64_t)(slot & (uint32_t)(rp.spp - 1)), 2));
-  return rng;
-}
 
 template <bool LLDS>
 __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true)) k_shade_whitted(DScene sc, RenderParams rp, BatchState st, StageQueues q, int stage) {

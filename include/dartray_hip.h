@@ -226,6 +226,16 @@ typedef struct DrFilm {
  * a ray tree's draws have no useful bound).  max_depth < 1 is DR_ERR_INVALID, DR_SAMPLER_ADAPTIVE with it DR_ERR_UNSUPPORTED; every other sampler
  * mode is served.  One count is read back per round of the specular recursion, as for DirectLighting over mirror / glass. */
 #define DR_INTEGRATOR_WHITTED 3
+/* AmbientOcclusionIntegrator (ambient_occlusion_integrator.dart:28-53): at the camera hit nsamples occlusion rays
+ * Ray(p, w, mindist, maxdist) over the hemisphere of the geometric normal facing the camera ray -- w = UniformSampleSphere(Sample02(i, scramble)),
+ * negated where Dot(w, n) < 0 -- and the radiance Spectrum(nClear / nsamples), nClear the rays scene.intersectP does not stop.  Its three
+ * parameters travel in DrRenderDesc.ao_nsamples / ao_mindist / ao_maxdist; max_depth is not read.  It requests no sample slots
+ * (dr_sample_floats: 7) and the two rng.randomUint() of the scramble are draws 0 and 1 of the sample's keyed in-Li stream (kind 2) in EVERY
+ * sampler mode, DR_SAMPLER_HOST_BUFFER included (seed keys them; there is no recorded tail).  ao_nsamples is rounded up to a power of two as the
+ * constructor does; below 1 or above 4096 after rounding, ao_mindist < 0 (or NaN) and ao_maxdist <= ao_mindist (or NaN) are DR_ERR_INVALID,
+ * DR_SAMPLER_ADAPTIVE with it DR_ERR_UNSUPPORTED; every other sampler mode is served.  The scene needs no light.  No host wait: the number of rounds
+ * of the stage loop (128 rays each) is known up front. */
+#define DR_INTEGRATOR_AO 4
 
 #define DR_SAMPLER_HOST_BUFFER 0 /* caller supplies sample vectors (+ the in-Li RNG draws) */
 #define DR_SAMPLER_COUNTER 1     /* on-device LD sampler, keyed per (pixel, block) / (pixel, sample) */
@@ -295,7 +305,14 @@ typedef struct DrRenderDesc {
   const int32_t* pixel_xy;  /* [nsamples/spp][2] raster pixel of each group of spp samples */
   const float* sample_vec;  /* [nsamples][sample_stride]: imageU, imageV, lensU, lensV, time, oneD..., twoD... */
   int32_t sample_stride;
-  const double* tail;       /* [nsamples][max_tail] RNG.randomFloat() values drawn inside Li, or NULL */
+  int32_t ao_nsamples;      /* DR_INTEGRATOR_AO: AmbientOcclusionIntegrator's ns (the former padding at offset 1324: read under that integrator only) */
+  /* DR_INTEGRATOR_AO draws from keyed streams in every sampler mode and reads no tail: under it, and only under it, the storage of the two tail
+   * pointers carries AmbientOcclusionIntegrator.minDist / maxDist (Dart doubles).  Under every other integrator the unions are `tail` and
+   * `tail_offsets` as they always were: same names, same offsets, same meaning. */
+  union {
+    const double* tail;     /* [nsamples][max_tail] RNG.randomFloat() values drawn inside Li, or NULL */
+    double ao_mindist;      /* DR_INTEGRATOR_AO: minDist (reference default 1e-4) */
+  };
   int32_t max_tail;
   /* Optional packed form of `tail` (round 5): tail_offsets[nsamples + 1], non-decreasing; sample s owns
    * tail[tail_offsets[s] .. tail_offsets[s + 1]) -- the values it actually drew, in draw order (position p of the fixed
@@ -303,7 +320,10 @@ typedef struct DrRenderDesc {
    * bound on a run's length.  NULL: the fixed [nsamples][max_tail] form.  A path draws nothing before its fourth vertex
    * and most paths end early, so a recorded C2 stream holds ~5 of its 40 slots per sample: the replay moves 0.4 x the
    * bytes over PCIe. */
-  const uint64_t* tail_offsets;
+  union {
+    const uint64_t* tail_offsets;
+    double ao_maxdist;      /* DR_INTEGRATOR_AO: maxDist (reference default: infinity) */
+  };
 } DrRenderDesc;
 
 /* Counters and timings accumulated over the dr_render* calls on a scene since
@@ -402,8 +422,8 @@ int dr_scene_set_trace_kernels(DrScene* scene, const uint32_t kernels[2]);
 int dr_scene_get_pilot(const DrScene* scene, float ms_per_gb_out[6]);
 /* Diagnostics: what the scene's LAST dr_render_device call actually ran with, switches (dr_set_option / environment)
  * included -- out[0] path-state layout (64 / 4), out[1] / out[2] the traversal kernel of its closest-hit / any-hit launches
- * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED render the integrator and its shading kernels: bits 0-7 the DR_INTEGRATOR_*
- * constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass); out[4] the
+ * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED or DR_INTEGRATOR_AO render the integrator and its shading kernels: bits 0-7 the
+ * DR_INTEGRATOR_* constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass), bit 10 k_shade_ao ran; out[4] the
  * calibration batches it ran (0: no pilot), out[5] its batches, out[6] workgroups per CU of a persistent traversal
  * launch, out[7] bit 0: a stage's any-hit launch ran beside its closest-hit launch, bit 1: the camera rays went through the
  * wave-coherent kernel (k_trace_pk), bit 3: the device sampler generated bounce b's blocks only for the pixel
@@ -553,7 +573,10 @@ const char* dr_version(void);
  * dr_loop_subdivide_device: two new entry points, no struct; and DR_SAMPLER_RANDOM: a new constant that dr_render*, dr_generate_samples and
  * dr_scene_last_render_info serve like the other pixel-bound modes, no struct, no entry point; and DR_INTEGRATOR_WHITTED: a new constant for
  * DrRenderDesc.integrator, whose max_depth carries maxdepth -- no struct, no field, no entry point; dr_scene_last_render_info names it in the
- * word that was reserved, which stays -1 after every other integrator's render). */
+ * word that was reserved, which stays -1 after every other integrator's render; and DR_INTEGRATOR_AO: a new constant whose three parameters
+ * travel in storage no render read under the constants a version-9 host can pass -- ao_nsamples in the padding behind sample_stride, ao_mindist /
+ * ao_maxdist in unions with tail / tail_offsets, which that integrator does not read -- so no field moved, the struct keeps its 1352 bytes, and a
+ * host built against the earlier version-9 header, which never names the constant, runs unchanged). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -654,9 +677,12 @@ DR_ABI_OFFSET(DrRenderDesc, nsamples, 1296);
 DR_ABI_OFFSET(DrRenderDesc, pixel_xy, 1304);
 DR_ABI_OFFSET(DrRenderDesc, sample_vec, 1312);
 DR_ABI_OFFSET(DrRenderDesc, sample_stride, 1320);
+DR_ABI_OFFSET(DrRenderDesc, ao_nsamples, 1324);
 DR_ABI_OFFSET(DrRenderDesc, tail, 1328);
+DR_ABI_OFFSET(DrRenderDesc, ao_mindist, 1328);
 DR_ABI_OFFSET(DrRenderDesc, max_tail, 1336);
 DR_ABI_OFFSET(DrRenderDesc, tail_offsets, 1344);
+DR_ABI_OFFSET(DrRenderDesc, ao_maxdist, 1344);
 DR_ABI_SIZE(DrRenderStats, 200);
 DR_ABI_OFFSET(DrRenderStats, trace_ms, 72);
 DR_ABI_OFFSET(DrRenderStats, film_ms, 144);

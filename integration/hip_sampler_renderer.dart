@@ -155,8 +155,11 @@ const int OFF_DrRenderDesc_nsamples = 1296;
 const int OFF_DrRenderDesc_pixel_xy = 1304;
 const int OFF_DrRenderDesc_sample_vec = 1312;
 const int OFF_DrRenderDesc_sample_stride = 1320;
+const int OFF_DrRenderDesc_ao_nsamples = 1324;  // DR_INTEGRATOR_AO only (the former padding)
 const int OFF_DrRenderDesc_tail = 1328;
+const int OFF_DrRenderDesc_ao_mindist = 1328;  // DR_INTEGRATOR_AO only: a double in the tail pointer's storage (that integrator reads no tail)
 const int OFF_DrRenderDesc_max_tail = 1336;
+const int OFF_DrRenderDesc_ao_maxdist = 1344;  // likewise, in the storage of tail_offsets
 const int OFF_DrRenderDesc_tail_offsets = 1344;  // host-buffer sampler only: stays NULL here (calloc'd descriptor)
 
 // enums of the header
@@ -167,7 +170,7 @@ const int DR_SHADING_N = 1, DR_SHADING_S = 2, DR_SHADING_UV = 4;
 const int DR_COMM_ID_BYTES = 128;
 const int DR_PRIM_QUADRIC = 0xFFFFFFFF, DR_QUADRIC_SPHERE = 1, DR_QUADRIC_DISK = 2;
 const int DR_CAMERA_PERSPECTIVE = 0, DR_CAMERA_ORTHOGRAPHIC = 1, DR_CAMERA_ENVIRONMENT = 2;
-const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2, DR_INTEGRATOR_WHITTED = 3;
+const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2, DR_INTEGRATOR_WHITTED = 3, DR_INTEGRATOR_AO = 4;
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
 const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
@@ -831,6 +834,16 @@ class HipSamplerRenderer extends Renderer {
         final dynamic wi = surfaceIntegrator;
         rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_WHITTED);
         rd.i32(OFF_DrRenderDesc_max_depth, wi.maxDepth);
+      } else if ('${surfaceIntegrator.runtimeType}' == 'AmbientOcclusionIntegrator') {
+        // nSamples (already RoundUpPow2'd by the constructor), minDist, maxDist: ambient_occlusion_integrator.dart:62-64; max_depth is not read
+        final dynamic ao = surfaceIntegrator;
+        rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_AO);
+        rd.i32(OFF_DrRenderDesc_max_depth, 1);
+        final double minDist = ao.minDist;
+        final double maxDist = ao.maxDist;
+        rd.i32(OFF_DrRenderDesc_ao_nsamples, ao.nSamples);
+        rd.f64(OFF_DrRenderDesc_ao_mindist, minDist);
+        rd.f64(OFF_DrRenderDesc_ao_maxdist, maxDist);
       } else {
         _unsupported('surface integrator ${surfaceIntegrator.runtimeType}');
       }
