@@ -6,15 +6,17 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from dartray_amd import core, scenes
+from dartray_amd import _abi, core, scenes
 from test_oracle_bvh import SCENES, soup_prims
 from util import aggregate_test_rays
 
 pytestmark = pytest.mark.gpu
 
 
-def _compare(ob, prims, n, seed):
+def _compare(ob, prims, n, seed, kernels=None):
     scene = scenes.make_scene(prims)
+    if kernels is not None:  # (closest, any-hit) kernel ids of this scene instead of the default k_intersect<0/1>
+        assert scene._device().trace_kernels(kernels) == kernels
     osc = ob.OracleScene(prims)
     nodes, tri, _, _ = osc.bvh()
     surf = osc.verts()[tri].astype(np.float64).mean(axis=1)
@@ -61,9 +63,19 @@ def test_golden_hit_records(gpu):
     assert np.array_equal(scene.intersectP(rays), g["occluded"])
 
 
-def test_deep_tree_uses_the_spill_stack(ob, gpu):
+@pytest.mark.parametrize("kernels", [(2, 2), (3, 3), (3, 7)], ids=["k2-2", "k3-3", "k3-7"])
+def test_deep_tree_uses_the_spill_stack(ob, gpu, kernels):
     """A geometric progression of triangles makes the SAH tree a long chain: deeper than the 32 LDS stack
-    entries per lane, exercising the global-memory spill (the reference's todo stack holds 64)."""
+    entries per lane, exercising the global-memory spill (the reference's todo stack holds 64).  The sibling-pair
+    kernels (3, 7) keep 15 (reference, E) entries per lane in LDS and spill the rest into two half-buffers."""
+    _abi.check(_abi.lib().dr_set_option(b"TRACE_IMPL", b""))  # the scene's own kernel ids decide, not an inherited DARTRAY_TRACE_IMPL
+    try:
+        _deep_tree(ob, kernels)
+    finally:
+        _abi.check(_abi.lib().dr_set_option(b"TRACE_IMPL", None))
+
+
+def _deep_tree(ob, kernels):
     n = 60
     s = 4.0 ** np.arange(n)
     P = np.zeros((n, 3, 3), np.float32)
@@ -74,6 +86,7 @@ def test_deep_tree_uses_the_spill_stack(ob, gpu):
                                      core.MatteMaterial((0.5, 0.5, 0.5)))]
     scene = scenes.make_scene(prims)
     assert scene.aggregate.depth > 32
+    assert scene._device().trace_kernels(kernels) == kernels
     osc = ob.OracleScene(prims)
     rng = np.random.Generator(np.random.PCG64(5))
     m = 20000
