@@ -16,6 +16,8 @@ DR_INTEGRATOR_PATH = 1
 DR_INTEGRATOR_DIRECT_ONE = 2
 DR_INTEGRATOR_WHITTED = 3
 DR_INTEGRATOR_AO = 4  # ao_nsamples / ao_mindist / ao_maxdist; max_depth is not read
+DR_INTEGRATOR_FEATURE = 5  # feature_channel; max_depth is not read
+DR_FEATURE_NG, DR_FEATURE_NS, DR_FEATURE_DEPTH, DR_FEATURE_UV, DR_FEATURE_ID = 0, 1, 2, 3, 4
 DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
 DR_SAMPLER_STRATIFIED = 2
@@ -139,6 +141,8 @@ class DrRenderDesc(C.Structure):
     ao_nsamples = _Overlay(1324, C.c_int32)
     ao_mindist = _Overlay(1328, C.c_double)
     ao_maxdist = _Overlay(1344, C.c_double)
+    # DR_INTEGRATOR_FEATURE's channel: the padding behind max_tail
+    feature_channel = _Overlay(1340, C.c_int32)
 
 
 class DrRenderStats(C.Structure):
@@ -183,6 +187,7 @@ EXPORTS = {
     "dr_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
     "dr_sample_floats": (C.c_int32, [C.c_int32, C.c_uint32]),
     "dr_scene_sample_floats": (C.c_int32, [C.c_void_p, C.c_int32]),
+    "dr_feature_check": (C.c_int, [C.c_int32, C.c_uint64]),
     "dr_render": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_device": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_sharded": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_int32, C.c_void_p, C.c_void_p]),

@@ -5,7 +5,8 @@ from .cameras import EnvironmentCamera, OrthographicCamera, PerspectiveCamera
 from .film import BoxFilter, GaussianFilter, ImageFilm, LanczosSincFilter, MitchellFilter, TriangleFilter
 from .lights import DiffuseAreaLight
 from .materials import MatteMaterial
-from .renderer import AmbientOcclusionIntegrator, DirectLightingIntegrator, EmissionIntegrator, PathIntegrator, SamplerRenderer, WhittedIntegrator
+from .renderer import (AmbientOcclusionIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, PathIntegrator, SamplerRenderer,
+                       WhittedIntegrator)
 from .samplers import (AdaptiveSampler, HaltonSampler, LinearPixelSampler, LowDiscrepancySampler, RandomPixelSampler, RandomSampler,
                        StratifiedSampler, TilePixelSampler)
 from .shapes import TriangleMesh
@@ -31,6 +32,7 @@ def RegisterStandardPlugins():
                     lambda ps=None: DirectLightingIntegrator(1 if (ps or {}).get("strategy", "all") == "one" else 0, (ps or {}).get("maxdepth", 5)))
     Plugin.register("surfaceIntegrator", "whitted", WhittedIntegrator.Create)
     Plugin.register("surfaceIntegrator", "ambientocclusion", AmbientOcclusionIntegrator.Create)
+    Plugin.register("surfaceIntegrator", "feature", FeatureIntegrator.Create)
     Plugin.register("volumeIntegrator", "emission", lambda ps=None: EmissionIntegrator((ps or {}).get("stepsize", 1.0)))
     Plugin.register("renderer", "sampler", SamplerRenderer)
     Plugin.register("sampler", "lowdiscrepancy", LowDiscrepancySampler)

@@ -126,6 +126,42 @@ class AmbientOcclusionIntegrator:
         return AmbientOcclusionIntegrator(ps.get("nsamples", 2048), ps.get("mindist", 1.0e-4), ps.get("maxdist", float("inf")))
 
 
+class FeatureIntegrator:
+    """The first-hit feature integrator (DR_INTEGRATOR_FEATURE, k_shade_feature; the reference has no such class): Li is one
+    quantity of the camera ray's Intersection -- `channel` "ng" / "ns" (0.5 * (normal + 1), geometric / shading), "depth" (t, t, t), "uv"
+    (u, v, 0) or "id" (primitive + 1, material + 1, 1) -- and 0 where the ray hits nothing.  No light is read."""
+
+    CHANNELS = {"ng": _abi.DR_FEATURE_NG, "ns": _abi.DR_FEATURE_NS, "depth": _abi.DR_FEATURE_DEPTH, "uv": _abi.DR_FEATURE_UV,
+                "id": _abi.DR_FEATURE_ID}
+
+    def __init__(self, channel="ng"):
+        if channel not in self.CHANNELS:
+            raise ValueError("feature integrator: channel must be one of ng, ns, depth, uv, id (got %r)" % (channel,))
+        self.channel = channel
+
+    kind = _abi.DR_INTEGRATOR_FEATURE
+    maxDepth = 0  # (not read by the device under this integrator; SamplerRenderer.describe marshals every integrator's)
+    li_draws_recorded = False  # (Li draws nothing: a host-buffer replay needs neither tail nor seed)
+
+    def requestSamples(self, sampler, scene):
+        """No slots of its own."""
+        return [], []
+
+    def check_sampler(self, sampler):
+        """SamplerRenderer.describe: what this integrator asks of the renderer's sampler."""
+        if isinstance(sampler, AdaptiveSampler):
+            raise ValueError("feature integrator: the adaptive sampler is not supported")
+
+    def to_abi(self, d):
+        """SamplerRenderer.describe, behind the sampler's own fields: the channel (the padding behind max_tail: include/dartray_hip.h)."""
+        d.feature_channel = self.CHANNELS[self.channel]
+
+    @staticmethod
+    def Create(params=None):
+        """`string channel`: ng (the default), ns, depth, uv or id."""
+        return FeatureIntegrator((params or {}).get("channel", "ng"))
+
+
 class EmissionIntegrator:
     """volume_integrators/emission_integrator.dart with no VolumeRegion: T = 1,
     Lv = 0; its only effect on the path is the two 1-D sample slots it requests."""

@@ -293,6 +293,12 @@ int32_t dr_sample_floats(int32_t integrator, uint32_t nlights) {
   return integratorSlots(knownIntegrator(integrator) ? (IntegratorKind)integrator : IntegratorKind::DirectAll, nullptr, nlights).nFloats();
 }
 
+int dr_feature_check(int32_t channel, uint64_t nprimitives) {
+  int code = DR_OK;
+  if (const char* why = featureRefusal(channel, nprimitives, &code)) return fail(code, why);
+  return DR_OK;
+}
+
 int32_t dr_scene_sample_floats(const DrScene* scene, int32_t integrator) {
   if (!scene) return -1;
   if (!knownIntegrator(integrator)) return dr_sample_floats(integrator, scene->d.nlights);
@@ -534,6 +540,13 @@ int planRender(RenderPlan& P) {
       P.ao.minDist = rd->ao_mindist;
       P.ao.maxDist = rd->ao_maxdist;
       P.nStages = P.ao.perRound + 1;
+      break;
+    }
+    case IntegratorKind::Feature: {  // the camera hit itself, one stage, nothing traced behind it
+      int code = DR_OK;
+      if (const char* why = featureRefusal(rd->feature_channel, sc->d.ntris, &code)) return fail(code, why);
+      P.feature.channel = rd->feature_channel;
+      P.nStages = 1;
       break;
     }
   }
@@ -828,6 +841,7 @@ int32_t lastInfoWord(const RenderPlan& P) {
     case IntegratorKind::DirectAll: case IntegratorKind::Path: case IntegratorKind::DirectOne: break;
     case IntegratorKind::Whitted: return DR_INTEGRATOR_WHITTED | 0x100 | (P.dlSpec ? 0x200 : 0);
     case IntegratorKind::AmbientOcclusion: return DR_INTEGRATOR_AO | 0x400;  // bit 10: k_shade_ao
+    case IntegratorKind::Feature: return DR_INTEGRATOR_FEATURE | 0x800 | (P.feature.channel << 12);  // bit 11: k_shade_feature; bits 12-14: its channel
   }
   return -1;
 }

@@ -249,6 +249,7 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
       shadowRaysOnly = true;
       break;
     }
+    case IntegratorKind::Feature: L.shade_feature(sc->d, stS, q, P.feature.channel, P.sgrid, s); break;  // (the only stage: nothing is traced behind it)
   }
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {

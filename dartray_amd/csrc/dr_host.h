@@ -254,7 +254,7 @@ struct SampleForm {
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
   X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
-  X(shade_ao, launch_shade_ao) X(film, launch_film)
+  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(film, launch_film)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -284,7 +284,7 @@ constexpr SamplerTraits kSamplerTraits[] = {
 // The surface integrators of the C ABI (DrRenderDesc.integrator) as the planner sees them, and what each one declares: every decision of
 // dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
 // source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
-enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion };
+enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature };
 struct IntegratorTraits {
   bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
   int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
@@ -305,11 +305,28 @@ constexpr IntegratorTraits kIntegratorTraits[] = {
     // AmbientOcclusion (ambient_occlusion_integrator.dart:28-53): no requestSamples -- tau + scatter only; one any-hit ray per stage,
     // nsamples of them per camera hit in rounds of the stage loop; max_depth is not read
     {false, 2, 0, false, false, nullptr,
-     "ambient occlusion integrator: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"}};
+     "ambient occlusion integrator: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"},
+    // Feature (no reference class): no requestSamples -- tau + scatter only; one stage, no ray beyond the camera's; max_depth and
+    // the lights are not read
+    {false, 2, 0, false, false, nullptr, "feature integrator: the adaptive sampler is not supported"}};
 static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
                   (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
-                  (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 5, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
+                  (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && (int)IntegratorKind::Feature == DR_INTEGRATOR_FEATURE &&
+                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 6, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
 inline bool knownIntegrator(int32_t v) { return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])); }
+
+// The feature integrator's refusals (dr_feature_check, planRender): null, or the text and its code
+inline const char* featureRefusal(int32_t channel, uint64_t nprims, int* code) {
+  if (channel < DR_FEATURE_NG || channel > DR_FEATURE_ID) {
+    *code = DR_ERR_INVALID;
+    return "feature integrator: unknown channel (DR_FEATURE_NG, _NS, _DEPTH, _UV or _ID)";
+  }
+  if (channel == DR_FEATURE_ID && nprims >= (1ull << 24)) {
+    *code = DR_ERR_UNSUPPORTED;
+    return "feature integrator: the id channel needs a scene of fewer than 2^24 primitives (an index + 1 must be exact in the film's f32)";
+  }
+  return nullptr;
+}
 
 // An integrator's sample slots; the floats of a sample vector are computed here and nowhere else.
 struct SlotCounts {
@@ -347,6 +364,7 @@ struct RenderPlan {
   // AmbientOcclusion: nSamples occlusion rays per camera hit, perRound of them in each of `rounds` rounds of the stage loop
   // (a round is perRound + 1 stages: CounterLayout::maxStages() bounds it); the rays' extent
   struct { int nSamples = 0, perRound = 0, rounds = 0; double minDist = 0.0, maxDist = 0.0; } ao;
+  struct { int channel = 0; } feature;  // Feature: DR_FEATURE_*
   // the device sampler's launches for one batch (BatchRunner::loadSamples, the two sample dumps)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
   // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'

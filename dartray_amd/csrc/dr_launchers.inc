@@ -46,6 +46,8 @@ void launch_shade_whitted(const DScene& sc, const RenderParams& rp, const BatchS
 // (< 0: none; 0: the camera hit set up first); the last ray folded: the slot's radiance nClear / nSamples
 void launch_shade_ao(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int nSamples, int fold, int emit,
                      double minDist, double maxDist, int grid, hipStream_t s);
+// dr_shade_feature.hip: the one stage of the feature integrator -- channel DR_FEATURE_* of every slot's camera hit as its radiance (a miss: 0)
+void launch_shade_feature(const DScene& sc, const BatchState& st, const StageQueues& q, int channel, int grid, hipStream_t s);
 void launch_film(const RenderParams& rp, const BatchState& st, const float* filterTable, uint32_t npix, float* film,
                  hipStream_t s);
 void launch_film_resolve(const float* film, int64_t npix, float* rgb, hipStream_t s);

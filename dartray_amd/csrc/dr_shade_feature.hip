@@ -1,0 +1,127 @@
+// dr_shade_feature.hip -- k_shade_feature: the first-hit feature integrator (DR_INTEGRATOR_FEATURE): one quantity of the camera
+// ray's Intersection / DifferentialGeometry (core/intersection.dart, differential_geometry.dart; shapes/triangle.dart, sphere.dart, disk.dart)
+// as the sample's radiance, so that it reaches the film through the same sampler, filter, tiles and shards as a beauty image.
+//
+//   DR_FEATURE_NG     0.5 * (isect.dg.nn + 1)            the geometric normal as Intersection leaves it (reverseOrientation applied)
+//   DR_FEATURE_NS     0.5 * (bsdf.dgShading.nn + 1)      Triangle.getShadingGeometry (per-vertex N / S); the geometric one elsewhere
+//   DR_FEATURE_DEPTH  t, t, t                            ray.maxDistance after scene.intersect
+//   DR_FEATURE_UV     dg.u, dg.v, 0                      mesh uvs, the default uvs (0,0) (1,0) (1,1), the quadrics' parameterisation
+//   DR_FEATURE_ID     primitive + 1, material + 1, 1     indices of the scene's arrays; the blue 1 is the coverage mask
+// A camera ray that hit nothing stores 0, 0, 0: no light is read.  Every value is >= 0: the renderer's guard blacks out a sample whose
+// luminance is below -1e-5.
+//
+// One lane per slot, slots in order (the camera stage has no list), so a wave's reads of the hit record and the camera ray and its store of
+// the radiance are each one run of the tile the state layout was designed around.  The channel is a template parameter: no wave branches on
+// it.  Nothing is queued: the render has one stage and traces nothing but the camera rays.  The geometry comes from dr_device.h's own
+// helpers, as in k_shade_ao's camera-hit part; only (u, v) of a quadric, which quadric_dg does not keep, is restated here (feature_quadric_uv).
+// f64 arithmetic, one rounding to the f32 radiance; compiled with -ffp-contract=off, like every unit.
+#include "dr_kernels.h"
+
+#ifdef DR_NS  // the second state layout (-DDR_SUB=4 -DDR_NS=sp4): every symbol in its own namespace
+namespace DR_NS {
+#endif
+
+#define DR_FEATURE_BLOCK 256
+
+// (u, v) of a quadric hit (sphere.dart:117-120, disk.dart:69-75) at the object-space point quadric_dg_at rebuilds (pointAt(t), the pole fix-up)
+DR_DEV void feature_quadric_uv(const DQuadric& q, F3 o, F3 d, double t, double* u, double* v) {
+  const F3 oo = q_point(q.w2o, o), od = q_vector(q.w2o, d);
+  F3 phit = vadd(oo, vmul(od, t));
+  if (q.kind == DR_QUADRIC_SPHERE && phit.x == 0.0f && phit.y == 0.0f) phit.x = (float)(1.0e-5 * q.radius);
+  const double phi = q_phi(phit);
+  *u = phi / q.phiMax;
+  if (q.kind == DR_QUADRIC_SPHERE) {
+    double r = (double)phit.z / q.radius;
+    r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
+    const double theta = acos(r);
+    *v = (theta - q.thetaMin) / (q.thetaMax - q.thetaMin);
+  } else {
+    const double dist2 = (double)phit.x * (double)phit.x + (double)phit.y * (double)phit.y;
+    const double oneMinusV = (sqrt(dist2) - q.innerRadius) / (q.radius - q.innerRadius);
+    *v = 1.0 - oneMinusV;
+  }
+}
+
+DR_DEV C3 feature_normal(F3 nn) {  // 0.5 * (n + 1), per component
+  return C3{(float)(0.5 * ((double)nn.x + 1.0)), (float)(0.5 * ((double)nn.y + 1.0)), (float)(0.5 * ((double)nn.z + 1.0))};
+}
+
+template <int CHANNEL>
+__global__ void __launch_bounds__(DR_FEATURE_BLOCK) k_shade_feature(DScene sc, BatchState st, TraceCounters* ctr) {
+  __shared__ uint32_t s_hits;
+  if (threadIdx.x == 0) s_hits = 0u;
+  __syncthreads();
+  const uint32_t stride = gridDim.x * blockDim.x;
+  uint32_t hits = 0u;
+  for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < st.nslots; slot += stride) {
+    const SlotRef sr = SlotRef::of(st, slot);
+    const int prim = sr.i32<F_HPRIM>();
+    C3 L = C3{0.f, 0.f, 0.f};
+    if (prim >= 0) {
+      ++hits;
+      const double t = sr.f64<F_HT>();
+      if (CHANNEL == DR_FEATURE_DEPTH) {
+        L = C3{(float)t, (float)t, (float)t};
+      } else {
+        const Tri tr = load_tri(sc, (uint32_t)prim);
+        if (CHANNEL == DR_FEATURE_ID) {
+          L = C3{(float)((double)prim + 1.0), (float)((double)tr.mat + 1.0), 1.0f};
+        } else {
+          const F3 o = ld3f<F_RO>(sr), d = ld3f<F_RD>(sr);
+          DGeo dg = {}, dgs = {};
+          if (tr.kind != 0) {
+            const DQuadric q = sc.quads[tr.quad];
+            if (CHANNEL == DR_FEATURE_UV) feature_quadric_uv(q, o, d, t, &dg.u, &dg.v);
+            else quadric_dg_at(q, o, d, t, &dg);
+            dgs = dg;  // Shape.getShadingGeometry: a copy
+          } else if (sc.srec && __float_as_uint(sc.srec[7 * (size_t)prim + 6].x) != 0u) {
+            const ShadeRec srec = load_srec(sc, (uint32_t)prim);
+            tri_dg_srec(tr, srec, o, d, t, &dg);
+            if (CHANNEL == DR_FEATURE_NS && (srec.flags & (DR_SHADING_N | DR_SHADING_S))) shading_geometry(sc, srec, tr.reverse, dg, &dgs);
+            else dgs = dg;
+          } else if (CHANNEL == DR_FEATURE_UV) {
+            // Triangle.getUVs without a uv array (triangle.dart:255-262) and the interpolation of :134-137, on the accepting test's barycentrics
+            double tt, b1 = 0.0, b2 = 0.0;
+            (void)tri_hit(tr.p1, tr.p2, tr.p3, o, d, -DR_INF, DR_INF, &tt, &b1, &b2);
+            const double b0 = 1.0 - b1 - b2;
+            dg.u = b0 * 0.0 + b1 * 1.0 + b2 * 1.0;
+            dg.v = b0 * 0.0 + b1 * 0.0 + b2 * 1.0;
+            dgs = dg;
+          } else {
+            tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
+            dgs = dg;
+          }
+          if (CHANNEL == DR_FEATURE_NG) L = feature_normal(dg.nn);
+          else if (CHANNEL == DR_FEATURE_NS) L = feature_normal(dgs.nn);
+          else L = C3{(float)dg.u, (float)dg.v, 0.f};
+        }
+      }
+    }
+    stcf<F_L>(sr, L);
+    sr.u32<F_FLAGS>() = 0u;
+  }
+  // DrRenderStats.shade_items / shade_vertices, as shade_count keeps them: one atomic per workgroup
+  if (hits) atomicAdd(&s_hits, hits);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_hits) atomicAdd(&ctr->shade_vertices, (unsigned long long)s_hits);
+    if (blockIdx.x == 0) atomicAdd(&ctr->shade_items, (unsigned long long)st.nslots);
+  }
+}
+
+void launch_shade_feature(const DScene& sc, const BatchState& st, const StageQueues& q, int channel, int grid, hipStream_t s) {
+  if (st.nslots == 0) return;
+  const unsigned need = (st.nslots + DR_FEATURE_BLOCK - 1) / DR_FEATURE_BLOCK, most = (unsigned)grid * 8u;  // (grid: the CUs; 8 workgroups of 256 each)
+  const dim3 g(need < most ? need : most), b(DR_FEATURE_BLOCK);
+  switch (channel) {  // (planRender refused every other value)
+    case DR_FEATURE_NG: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_NG>, g, b, 0, s, sc, st, q.ctr); break;
+    case DR_FEATURE_NS: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_NS>, g, b, 0, s, sc, st, q.ctr); break;
+    case DR_FEATURE_DEPTH: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_DEPTH>, g, b, 0, s, sc, st, q.ctr); break;
+    case DR_FEATURE_UV: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_UV>, g, b, 0, s, sc, st, q.ctr); break;
+    case DR_FEATURE_ID: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_ID>, g, b, 0, s, sc, st, q.ctr); break;
+  }
+}
+
+#ifdef DR_NS
+}  // namespace DR_NS
+#endif

@@ -236,6 +236,21 @@ typedef struct DrFilm {
  * DR_SAMPLER_ADAPTIVE with it DR_ERR_UNSUPPORTED; every other sampler mode is served.  The scene needs no light.  No host wait: the number of rounds
  * of the stage loop (128 rays each) is known up front. */
 #define DR_INTEGRATOR_AO 4
+/* The first-hit feature integrator (the reference has none): the radiance of a sample is one quantity of the camera
+ * ray's Intersection, chosen by DrRenderDesc.feature_channel -- a guide image (normal, depth, uv, ids) that goes through the same sampler,
+ * filter, tiles and shards as the beauty image and is aligned with it sample for sample.  A camera ray that hits nothing gives 0, 0, 0; no
+ * light is read (a scene without lights renders), max_depth is not read, no sample slots are requested (dr_sample_floats: 7) and nothing is
+ * drawn inside Li (a host-buffer replay needs neither tail nor seed).  One stage, no ray beyond the camera's.  An unknown channel is
+ * DR_ERR_INVALID, DR_SAMPLER_ADAPTIVE with it DR_ERR_UNSUPPORTED, DR_FEATURE_ID over a scene of 2^24 primitives or more DR_ERR_UNSUPPORTED
+ * (dr_feature_check says so without a scene); every other sampler mode is served. */
+#define DR_INTEGRATOR_FEATURE 5
+/* DrRenderDesc.feature_channel: R, G, B at a hit.  Every value is >= 0 (the renderer blacks out a sample of negative luminance). */
+#define DR_FEATURE_NG 0    /* 0.5 * (isect.dg.nn + 1): the geometric normal, world space, reverseOrientation applied */
+#define DR_FEATURE_NS 1    /* 0.5 * (bsdf.dgShading.nn + 1): Triangle.getShadingGeometry (per-vertex N / S); else the geometric one */
+#define DR_FEATURE_DEPTH 2 /* t, t, t: the camera ray's parameter at the hit (ray.maxDistance after scene.intersect) */
+#define DR_FEATURE_UV 3    /* dg.u, dg.v, 0 */
+#define DR_FEATURE_ID 4    /* primitive index + 1, material index + 1, 1 (indices of dr_scene_create's arrays); B is the coverage mask.
+                            * Meaningful per sample, or with a box filter of width 0.5 at 1 spp: any other film averages ids */
 
 #define DR_SAMPLER_HOST_BUFFER 0 /* caller supplies sample vectors (+ the in-Li RNG draws) */
 #define DR_SAMPLER_COUNTER 1     /* on-device LD sampler, keyed per (pixel, block) / (pixel, sample) */
@@ -314,6 +329,7 @@ typedef struct DrRenderDesc {
     double ao_mindist;      /* DR_INTEGRATOR_AO: minDist (reference default 1e-4) */
   };
   int32_t max_tail;
+  int32_t feature_channel;  /* DR_INTEGRATOR_FEATURE: DR_FEATURE_* (the former padding at offset 1340: read under that integrator only) */
   /* Optional packed form of `tail` (round 5): tail_offsets[nsamples + 1], non-decreasing; sample s owns
    * tail[tail_offsets[s] .. tail_offsets[s + 1]) -- the values it actually drew, in draw order (position p of the fixed
    * form = element p of the run; a read past the run yields 0.0 like the zero fill of the fixed form); max_tail stays the
@@ -422,8 +438,9 @@ int dr_scene_set_trace_kernels(DrScene* scene, const uint32_t kernels[2]);
 int dr_scene_get_pilot(const DrScene* scene, float ms_per_gb_out[6]);
 /* Diagnostics: what the scene's LAST dr_render_device call actually ran with, switches (dr_set_option / environment)
  * included -- out[0] path-state layout (64 / 4), out[1] / out[2] the traversal kernel of its closest-hit / any-hit launches
- * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED or DR_INTEGRATOR_AO render the integrator and its shading kernels: bits 0-7 the
- * DR_INTEGRATOR_* constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass), bit 10 k_shade_ao ran; out[4] the
+ * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED, DR_INTEGRATOR_AO or DR_INTEGRATOR_FEATURE render the integrator and its shading
+ * kernels: bits 0-7 the DR_INTEGRATOR_* constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass), bit 10
+ * k_shade_ao ran, bit 11 k_shade_feature ran (bits 12-14: its DR_FEATURE_* channel); out[4] the
  * calibration batches it ran (0: no pilot), out[5] its batches, out[6] workgroups per CU of a persistent traversal
  * launch, out[7] bit 0: a stage's any-hit launch ran beside its closest-hit launch, bit 1: the camera rays went through the
  * wave-coherent kernel (k_trace_pk), bit 3: the device sampler generated bounce b's blocks only for the pixel
@@ -467,6 +484,10 @@ int32_t dr_sample_floats(int32_t integrator, uint32_t nlights);
  * (direct_lighting_integrator.dart:70-87; low_discrepancy_sampler.dart:43-49), so the vector length depends on
  * the lights; dr_sample_floats assumes nsamples == 1 everywhere. */
 int32_t dr_scene_sample_floats(const DrScene* scene, int32_t integrator);
+/* What a DR_INTEGRATOR_FEATURE render of `channel` over a scene of `nprimitives` primitives would answer, without a scene or a device: DR_OK,
+ * DR_ERR_INVALID (no such channel) or DR_ERR_UNSUPPORTED (DR_FEATURE_ID with 2^24 primitives or more: an index would no longer be exact in the
+ * film's f32), with dr_last_error's text.  dr_render* apply the same rule to their scene. */
+int dr_feature_check(int32_t channel, uint64_t nprimitives);
 
 /* Renderer.render(Scene) (lib/core/renderer.dart:28;
  * sampler_renderer.dart:36-65): traces this task's window and returns the
@@ -576,7 +597,8 @@ const char* dr_version(void);
  * word that was reserved, which stays -1 after every other integrator's render; and DR_INTEGRATOR_AO: a new constant whose three parameters
  * travel in storage no render read under the constants a version-9 host can pass -- ao_nsamples in the padding behind sample_stride, ao_mindist /
  * ao_maxdist in unions with tail / tail_offsets, which that integrator does not read -- so no field moved, the struct keeps its 1352 bytes, and a
- * host built against the earlier version-9 header, which never names the constant, runs unchanged). */
+ * host built against the earlier version-9 header, which never names the constant, runs unchanged; and DR_INTEGRATOR_FEATURE: a new constant
+ * whose channel travels in the padding behind max_tail, read under that constant only, and one new entry point, dr_feature_check). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -681,6 +703,7 @@ DR_ABI_OFFSET(DrRenderDesc, ao_nsamples, 1324);
 DR_ABI_OFFSET(DrRenderDesc, tail, 1328);
 DR_ABI_OFFSET(DrRenderDesc, ao_mindist, 1328);
 DR_ABI_OFFSET(DrRenderDesc, max_tail, 1336);
+DR_ABI_OFFSET(DrRenderDesc, feature_channel, 1340);
 DR_ABI_OFFSET(DrRenderDesc, tail_offsets, 1344);
 DR_ABI_OFFSET(DrRenderDesc, ao_maxdist, 1344);
 DR_ABI_SIZE(DrRenderStats, 200);

@@ -159,6 +159,7 @@ const int OFF_DrRenderDesc_ao_nsamples = 1324;  // DR_INTEGRATOR_AO only (the fo
 const int OFF_DrRenderDesc_tail = 1328;
 const int OFF_DrRenderDesc_ao_mindist = 1328;  // DR_INTEGRATOR_AO only: a double in the tail pointer's storage (that integrator reads no tail)
 const int OFF_DrRenderDesc_max_tail = 1336;
+const int OFF_DrRenderDesc_feature_channel = 1340;  // DR_INTEGRATOR_FEATURE only (the former padding)
 const int OFF_DrRenderDesc_ao_maxdist = 1344;  // likewise, in the storage of tail_offsets
 const int OFF_DrRenderDesc_tail_offsets = 1344;  // host-buffer sampler only: stays NULL here (calloc'd descriptor)
 
@@ -171,6 +172,8 @@ const int DR_COMM_ID_BYTES = 128;
 const int DR_PRIM_QUADRIC = 0xFFFFFFFF, DR_QUADRIC_SPHERE = 1, DR_QUADRIC_DISK = 2;
 const int DR_CAMERA_PERSPECTIVE = 0, DR_CAMERA_ORTHOGRAPHIC = 1, DR_CAMERA_ENVIRONMENT = 2;
 const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2, DR_INTEGRATOR_WHITTED = 3, DR_INTEGRATOR_AO = 4;
+const int DR_INTEGRATOR_FEATURE = 5;  // the first-hit feature integrator (FeatureIntegrator below): DrRenderDesc.feature_channel
+const int DR_FEATURE_NG = 0, DR_FEATURE_NS = 1, DR_FEATURE_DEPTH = 2, DR_FEATURE_UV = 3, DR_FEATURE_ID = 4;
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
 const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
@@ -223,6 +226,25 @@ typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
 typedef _ErrD = Pointer<Utf8> Function();
+
+/// The first-hit feature integrator (DESIGN.md 2.14): the library's own surface integrator, which the reference does not have.  Li is one
+/// quantity of the camera ray's Intersection -- channel DR_FEATURE_NG / _NS (0.5 * (normal + 1)), _DEPTH (t, t, t), _UV (u, v, 0) or _ID
+/// (primitive + 1, material + 1, 1), and 0 where the ray hits nothing -- a guide image rendered through the same sampler and film as the
+/// beauty image.  It exists on the device only (DR_INTEGRATOR_FEATURE, k_shade_feature): the object carries the channel to
+/// HipSamplerRenderer, and a host renderer that asks it for Li is told so.
+class FeatureIntegrator extends SurfaceIntegrator {
+  FeatureIntegrator(this.channel) {
+    if (channel < DR_FEATURE_NG || channel > DR_FEATURE_ID) {
+      throw new ArgumentError('feature integrator: unknown channel (DR_FEATURE_NG, _NS, _DEPTH, _UV or _ID)');
+    }
+  }
+
+  Spectrum Li(Scene scene, Renderer renderer, RayDifferential ray, Intersection isect, Sample sample, RNG rng) {
+    throw new UnsupportedError('feature integrator: evaluated on the device (HipSamplerRenderer)');
+  }
+
+  final int channel;
+}
 
 /// A zero-initialised block of native memory with typed little-endian writers: one per C struct (array).
 class _Blob {
@@ -844,6 +866,11 @@ class HipSamplerRenderer extends Renderer {
         rd.i32(OFF_DrRenderDesc_ao_nsamples, ao.nSamples);
         rd.f64(OFF_DrRenderDesc_ao_mindist, minDist);
         rd.f64(OFF_DrRenderDesc_ao_maxdist, maxDist);
+      } else if (surfaceIntegrator is FeatureIntegrator) {  // max_depth is not read
+        final FeatureIntegrator feat = surfaceIntegrator;
+        rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_FEATURE);
+        rd.i32(OFF_DrRenderDesc_max_depth, 0);
+        rd.i32(OFF_DrRenderDesc_feature_channel, feat.channel);
       } else {
         _unsupported('surface integrator ${surfaceIntegrator.runtimeType}');
       }
