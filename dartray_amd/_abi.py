@@ -159,6 +159,10 @@ class DrRenderStats(C.Structure):
                 ("shade_mis", C.c_uint64), ("shade_shadow", C.c_uint64), ("pilot_ms", C.c_double)]
 
 
+class DrDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float)]
+
+
 DR_COMM_ID_BYTES = 128
 DR_ABI_VERSION = 9  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
 
@@ -176,6 +180,10 @@ EXPORTS = {
                                     C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dr_loop_subdivide_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dr_denoise_atrous_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p]),
+    "dr_denoise_atrous": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p]),
+    "dr_denoise_atrous_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "dr_scene_create": (C.c_int, [C.POINTER(DrSceneDesc), C.POINTER(C.c_void_p)]),
     "dr_scene_destroy": (None, [C.c_void_p]),
     "dr_scene_get_trace_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 2)]),

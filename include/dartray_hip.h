@@ -419,6 +419,34 @@ int dr_loop_subdivide_device(const uint32_t* indices, uint64_t nfaces, const flo
                              float* N_out, uint32_t* indices_out, uint64_t vert_cap, uint64_t face_cap, uint64_t* nverts_out,
                              uint64_t* nfaces_out);
 
+/* The edge-avoiding a-trous denoiser (the reference has none): a post-process beside the render path, guided by
+ * the images of DR_INTEGRATOR_FEATURE.  Row-major f32 images: rgb[h][w][3] (the beauty image), normal[h][w][3] (any 3-vector guide; a
+ * DR_FEATURE_NS / _NG image as it stands), depth[h][w] (a scalar guide; channel 0 of a DR_FEATURE_DEPTH image), out[h][w][3].
+ * Level i = 0 .. iterations - 1 filters the level before it (level 0: rgb) with the 5 x 5 B3-spline taps at step 2^i; a tap's weight is
+ * divided by (1 + k * d) for each of the three squared distances d (colour, normal, depth) whose k is not 0.  k = 1 / sigma^2; the
+ * colour term's k is k_color * 4^i at level i.  A pixel with a non-finite colour, normal or depth is copied through bit for bit and is
+ * no tap of any other pixel.  f32 arithmetic, one rounding per operator: the three entry points below write the same bytes. */
+typedef struct DrDenoiseParams {
+  int32_t iterations; /* 1 .. 8 */
+  float k_color;      /* finite, >= 0; 0: the term is off.  k_color * 4^(iterations - 1) must be finite in f32 */
+  float k_normal;
+  float k_depth;
+} DrDenoiseParams; /* 16 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer, w or h < 1, w * h >= 2^31, iterations outside 1 .. 8, a k that is negative or not
+ * finite, a last level's colour k that is not finite, `out` overlapping an input (or the scratch buffer).
+ * dr_denoise_atrous_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_denoise_atrous_host(const float* rgb, const float* normal, const float* depth, int32_t w, int32_t h, const DrDenoiseParams* params,
+                           float* out);
+/* The same ON THE GPU (dr_denoise_device.hip), host buffers: uploads, filters, copies back.  Needs dr_init. */
+int dr_denoise_atrous(const float* rgb, const float* normal, const float* depth, int32_t w, int32_t h, const DrDenoiseParams* params,
+                      float* out);
+/* The same on device buffers, asynchronous on the given hipStream_t.  scratch_dev == NULL: the size query -- writes the bytes of scratch
+ * an image of w x h needs to *scratch_bytes and does nothing else (the image pointers are not read and may be NULL).  Otherwise
+ * *scratch_bytes is the size of scratch_dev (too small is DR_ERR_INVALID), which must be 16-byte aligned and is the call's to overwrite
+ * until the stream has run it. */
+int dr_denoise_atrous_device(const void* rgb_dev, const void* normal_dev, const void* depth_dev, int32_t w, int32_t h,
+                             const DrDenoiseParams* params, void* out_dev, void* scratch_dev, uint64_t* scratch_bytes, void* hip_stream);
+
 /* Scene upload (replaces the construction of lib/core/scene.dart Scene). */
 int dr_scene_create(const DrSceneDesc* desc, DrScene** out);
 void dr_scene_destroy(DrScene* scene);
@@ -598,7 +626,9 @@ const char* dr_version(void);
  * travel in storage no render read under the constants a version-9 host can pass -- ao_nsamples in the padding behind sample_stride, ao_mindist /
  * ao_maxdist in unions with tail / tail_offsets, which that integrator does not read -- so no field moved, the struct keeps its 1352 bytes, and a
  * host built against the earlier version-9 header, which never names the constant, runs unchanged; and DR_INTEGRATOR_FEATURE: a new constant
- * whose channel travels in the padding behind max_tail, read under that constant only, and one new entry point, dr_feature_check). */
+ * whose channel travels in the padding behind max_tail, read under that constant only, and one new entry point, dr_feature_check; and the
+ * denoiser: one new struct, DrDenoiseParams, that only its three new entry points read -- dr_denoise_atrous_host, dr_denoise_atrous and
+ * dr_denoise_atrous_device -- no existing struct, constant or call means anything else). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -711,6 +741,10 @@ DR_ABI_OFFSET(DrRenderStats, trace_ms, 72);
 DR_ABI_OFFSET(DrRenderStats, film_ms, 144);
 DR_ABI_OFFSET(DrRenderStats, shade_items, 152);
 DR_ABI_OFFSET(DrRenderStats, pilot_ms, 192);
+DR_ABI_SIZE(DrDenoiseParams, 16);
+DR_ABI_OFFSET(DrDenoiseParams, k_color, 4);
+DR_ABI_OFFSET(DrDenoiseParams, k_normal, 8);
+DR_ABI_OFFSET(DrDenoiseParams, k_depth, 12);
 
 #ifdef __cplusplus
 }

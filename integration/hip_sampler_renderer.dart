@@ -162,6 +162,12 @@ const int OFF_DrRenderDesc_max_tail = 1336;
 const int OFF_DrRenderDesc_feature_channel = 1340;  // DR_INTEGRATOR_FEATURE only (the former padding)
 const int OFF_DrRenderDesc_ao_maxdist = 1344;  // likewise, in the storage of tail_offsets
 const int OFF_DrRenderDesc_tail_offsets = 1344;  // host-buffer sampler only: stays NULL here (calloc'd descriptor)
+// DrDenoiseParams (the a-trous denoiser, DESIGN.md 2.15): int32 iterations (1 .. 8) at 0, then three f32 sharpness values k = 1 / sigma^2
+const int SIZEOF_DrDenoiseParams = 16;
+const int OFF_DrDenoiseParams_iterations = 0;
+const int OFF_DrDenoiseParams_k_color = 4;
+const int OFF_DrDenoiseParams_k_normal = 8;
+const int OFF_DrDenoiseParams_k_depth = 12;
 
 // enums of the header
 const int DR_MATERIAL_MATTE = 0, DR_MATERIAL_MIRROR = 1, DR_MATERIAL_GLASS = 2, DR_MATERIAL_PLASTIC = 3;
@@ -222,6 +228,10 @@ typedef _LoopSubdivideC = Int32 Function(Pointer<Uint32>, Uint64, Pointer<Float>
     Uint64, Uint64, Pointer<Uint64>, Pointer<Uint64>);
 typedef _LoopSubdivideD = int Function(Pointer<Uint32>, int, Pointer<Float>, int, int, Pointer<Float>, Pointer<Float>, Pointer<Uint32>,
     int, int, Pointer<Uint64>, Pointer<Uint64>);
+// dr_denoise_atrous (the edge-avoiding a-trous filter on the GPU, host buffers; DESIGN.md 2.15): rgb[h][w][3], normal[h][w][3], depth[h][w],
+// w, h, DrDenoiseParams (16 bytes, the OFF_DrDenoiseParams_* offsets above), out[h][w][3].  (Signature only, never compiled, like the rest.)
+typedef _DenoiseAtrousC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>);
+typedef _DenoiseAtrousD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -282,6 +292,8 @@ class HipSamplerRenderer extends Renderer {
   /// LoopSubdivision.refine behind the C ABI: the host builder and, after dr_init, the device builder (same bytes).
   static final _LoopSubdivideD loopSubdivide = _lib.lookupFunction<_LoopSubdivideC, _LoopSubdivideD>('dr_loop_subdivide');
   static final _LoopSubdivideD loopSubdivideDevice = _lib.lookupFunction<_LoopSubdivideC, _LoopSubdivideD>('dr_loop_subdivide_device');
+  /// The a-trous denoiser over a finished image and its FeatureIntegrator normal and depth images (after dr_init).
+  static final _DenoiseAtrousD denoiseAtrous = _lib.lookupFunction<_DenoiseAtrousC, _DenoiseAtrousD>('dr_denoise_atrous');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
   /// library of another layout version is refused before any struct crosses the boundary.
   static const int ABI_VERSION = 9;
