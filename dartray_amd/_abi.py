@@ -17,6 +17,7 @@ DR_INTEGRATOR_DIRECT_ONE = 2
 DR_INTEGRATOR_WHITTED = 3
 DR_INTEGRATOR_AO = 4  # ao_nsamples / ao_mindist / ao_maxdist; max_depth is not read
 DR_INTEGRATOR_FEATURE = 5  # feature_channel; max_depth is not read
+DR_INTEGRATOR_DIFFUSE_PRT = 7  # (6 stays unassigned) prt_nsamples / prt_lmax; max_depth is not read
 DR_FEATURE_NG, DR_FEATURE_NS, DR_FEATURE_DEPTH, DR_FEATURE_UV, DR_FEATURE_ID = 0, 1, 2, 3, 4
 DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
@@ -143,6 +144,9 @@ class DrRenderDesc(C.Structure):
     ao_maxdist = _Overlay(1344, C.c_double)
     # DR_INTEGRATOR_FEATURE's channel: the padding behind max_tail
     feature_channel = _Overlay(1340, C.c_int32)
+    # DR_INTEGRATOR_DIFFUSE_PRT's two parameters: union members at the offsets of ao_nsamples and feature_channel (each read under one integrator only)
+    prt_nsamples = _Overlay(1324, C.c_int32)
+    prt_lmax = _Overlay(1340, C.c_int32)
 
 
 class DrRenderStats(C.Structure):
@@ -196,6 +200,8 @@ EXPORTS = {
     "dr_sample_floats": (C.c_int32, [C.c_int32, C.c_uint32]),
     "dr_scene_sample_floats": (C.c_int32, [C.c_void_p, C.c_int32]),
     "dr_feature_check": (C.c_int, [C.c_int32, C.c_uint64]),
+    "dr_prt_incident": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
+    "dr_sh_evaluate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "dr_render": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_device": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_sharded": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_int32, C.c_void_p, C.c_void_p]),

@@ -126,6 +126,62 @@ class AmbientOcclusionIntegrator:
         return AmbientOcclusionIntegrator(ps.get("nsamples", 2048), ps.get("mindist", 1.0e-4), ps.get("maxdist", float("inf")))
 
 
+class DiffusePRTIntegrator:
+    """surface_integrators/diffuse_prt_integrator.dart:23-92: the lights' direct radiance at the centre of the world bound projected onto
+    (lmax + 1)^2 spherical harmonics once (preprocess), the cosine-weighted visibility of every camera hit projected onto the same basis with
+    nSamples = RoundUpPow2(ns) occlusion rays, Li = Le + Kd * clamp(their dot product).  On the device DR_INTEGRATOR_DIFFUSE_PRT (k_shade_prt,
+    dr_prt_project.hip).  Materials: matte with sigma 0; a scene with any other is refused by name at render time."""
+
+    LMAX_MAX = 8
+
+    def __init__(self, lmax=4, nSamples=4096):
+        self.lmax = int(lmax)
+        if self.lmax < 1:
+            raise ValueError("diffuse PRT: lmax must be at least 1 (the Legendre recurrence stores P(1, 0) unconditionally)")
+        if self.lmax > self.LMAX_MAX:
+            raise ValueError("diffuse PRT: lmax above 8 (a camera sample's transfer coefficients, (lmax + 1)^2 words, live in a per-slot side buffer)")
+        if int(nSamples) < 1:
+            raise ValueError("diffuse PRT: nsamples must be at least 1")
+        self.nSamples = RoundUpPow2(int(nSamples))                 # :26
+        if self.nSamples > 4096:
+            raise ValueError("diffuse PRT: nsamples above 4096 after rounding up to a power of two (the samplers' cap)")
+
+    kind = _abi.DR_INTEGRATOR_DIFFUSE_PRT
+    maxDepth = 1  # (not read by the device under this integrator; SamplerRenderer.describe marshals every integrator's)
+    li_draws_recorded = False  # (the scramble's two randomUint() are keyed (pixel, sample) draws in every sampler mode, DESIGN.md 2.16)
+
+    def requestSamples(self, sampler, scene):
+        """The reference's requestSamples is empty (:42-43): no slots of its own."""
+        return [], []
+
+    def check_sampler(self, sampler):
+        """SamplerRenderer.describe: what this integrator asks of the renderer's sampler."""
+        if isinstance(sampler, AdaptiveSampler):
+            raise ValueError("diffuse PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no "
+                             "test; every other sampler mode is)")
+        if getattr(sampler, "sampler_mode", None) == _abi.DR_SAMPLER_HOST_BUFFER and sampler.li_seed is None:
+            raise ValueError("a DiffusePRTIntegrator draws its scramble from the keyed (pixel, sample) streams in every sampler mode: "
+                             "give the HostBufferSampler the seed of the render it replays (seed=...)")
+
+    def to_abi(self, d):
+        """SamplerRenderer.describe, behind the sampler's own fields: the two parameters (union members at the offsets of ao_nsamples and
+        feature_channel, which only their own integrators read: include/dartray_hip.h)."""
+        d.prt_nsamples = self.nSamples
+        d.prt_lmax = self.lmax
+
+    def incident(self, scene, shutterOpen=0.0):
+        """preprocess (:33-40) on the device: c_in after ReduceRinging, [(lmax + 1)^2, 3] f32 (dr_prt_incident)."""
+        out = np.zeros(((self.lmax + 1) ** 2, 3), np.float32)
+        _abi.check(_abi.lib().dr_prt_incident(scene._device().handle, self.lmax, float(shutterOpen), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def Create(params=None):
+        """DiffusePRTIntegrator.Create (:83-87): `lmax` 4, `nsamples` 4096."""
+        ps = params or {}
+        return DiffusePRTIntegrator(ps.get("lmax", 4), ps.get("nsamples", 4096))
+
+
 class FeatureIntegrator:
     """The first-hit feature integrator (DR_INTEGRATOR_FEATURE, k_shade_feature; the reference has no such class): Li is one
     quantity of the camera ray's Intersection -- `channel` "ng" / "ns" (0.5 * (normal + 1), geometric / shading), "depth" (t, t, t), "uv"
@@ -243,6 +299,10 @@ class SamplerRenderer:
         n = C.c_uint64(0)
         _abi.check(_abi.lib().dr_generate_halton_samples(dev.handle, C.byref(d), first, count, k.ctypes.data, xy.ctypes.data, out.ctypes.data, nf, C.byref(n)))
         return k[:n.value].copy(), xy[:n.value].copy(), out[:n.value].copy()
+
+    def prt_incident(self, scene):
+        """The incident-light coefficients a DiffusePRTIntegrator render of `scene` uses (dr_prt_incident), [(lmax + 1)^2, 3] f32."""
+        return self.surfaceIntegrator.incident(scene, self.camera.shutterOpen)
 
     def render(self, scene):
         film = self.camera.film

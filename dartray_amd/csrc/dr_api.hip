@@ -549,6 +549,25 @@ int planRender(RenderPlan& P) {
       P.nStages = 1;
       break;
     }
+    case IntegratorKind::DiffusePRT: {
+      // DiffusePRTIntegrator (diffuse_prt_integrator.dart:24-31,83-87): nSamples = RoundUpPow2(ns) occlusion rays per camera hit, one
+      // per stage, in ambient occlusion's rounds of 128.  Materials other than a Lambertian matte are refused by name: rho2's 36-sample estimate
+      // of their lobes has no device function outside the kernels that own them.
+      if (const char* why = prtRefusal(rd->prt_lmax, rd->prt_nsamples, true)) return fail(DR_ERR_INVALID, why);
+      static const char* const names[] = {"matte with sigma != 0 (Oren-Nayar)", "matte", "mirror", "glass", "plastic"};
+      for (size_t i = 0; i < sc->prtMaterials.size(); ++i)
+        if (sc->prtMaterials[i] != DR_MATERIAL_MATTE)
+          return fail(DR_ERR_UNSUPPORTED, std::string("diffuse PRT: material ") + names[std::min(3, std::max(-1, sc->prtMaterials[i])) + 1] + " (material " +
+                                              std::to_string(i) + " of the scene) is not supported: only matte with sigma 0 is");
+      uint32_t ns = 1;
+      while (ns < (uint32_t)rd->prt_nsamples) ns <<= 1;  // RoundUpPow2 (common.dart:117-125)
+      P.prt.nSamples = (int)ns;
+      P.prt.perRound = std::min(P.prt.nSamples, 128);
+      P.prt.rounds = P.prt.nSamples / P.prt.perRound;
+      P.prt.lmax = rd->prt_lmax;
+      P.nStages = P.prt.perRound + 1;
+      break;
+    }
   }
   rp.dlSpecular = P.dlSpec ? 1 : 0;
   rp.deferredNee = P.integ->pathStages ? 1 : 0;
@@ -666,7 +685,8 @@ int planBatches(RenderPlan& P) {
                                                  : (uint64_t)rd->max_tail * 8);
     const uint64_t perSlot = (uint64_t)P.maxStateWords * 4 + (uint64_t)(P.wsSf.svWords() + 15) / 16 + 20 + tailPerSlot + (!P.traits->deviceGenerated ? (uint64_t)rd->sample_stride * 4 : 0) +
                              (sf.compact ? (uint64_t)(16 * sf.nBlocks + spp - 1) / spp : 0) +  // scramble words + generator states, per (block, pixel)
-                             (P.dlSpec ? (uint64_t)std::max(1, rd->max_depth) * sizeof(SpecFrame) + 12 : 0);
+                             (P.dlSpec ? (uint64_t)std::max(1, rd->max_depth) * sizeof(SpecFrame) + 12 : 0) +
+                             (P.prt.lmax ? (uint64_t)sh_terms(P.prt.lmax) * 4 + 8 : 0);  // diffuse PRT: the slot's transfer coefficients + the round lists
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
       const uint64_t have = (uint64_t)sc->ws.cap * ((uint64_t)sc->ws.stateWords * 4 + sc->ws.svWords / 16 + 20);
@@ -743,9 +763,16 @@ int prepareRender(RenderPlan& P) {
     HIP_TRY(sc->ws.roundA.alloc(sc->ws.cap));
     HIP_TRY(sc->ws.roundB.alloc(sc->ws.cap));
   }
-  if (P.ao.rounds > 1) {  // ambient occlusion in rounds: the slots that hit, handed from a round's last stage to the next round's first
+  if (P.shadowRounds() > 1) {  // ambient occlusion / diffuse PRT in rounds: the slots that hit, handed from a round's last stage to the next round's first
     HIP_TRY(sc->ws.roundA.alloc(sc->ws.cap));
     HIP_TRY(sc->ws.roundB.alloc(sc->ws.cap));
+  }
+  if (P.integrator == IntegratorKind::DiffusePRT) {
+    // the side buffer of transfer coefficients, [Terms(lmax)][wsCap] -- this plan's batch capacity, which planBatches shrank to fit, not the
+    // capacity an earlier, larger render left the workspace with -- and, once per scene and lmax, before the first batch, the incident light
+    HIP_TRY(sc->ws.prt.alloc((size_t)P.wsCap * (size_t)sh_terms(P.prt.lmax)));
+    rc = prtIncident(sc, P.prt.lmax, rd->camera.shutter_open, P.s);
+    if (rc) return rc;
   }
   if (P.envStage) HIP_TRY(sc->ws.envQ.alloc(sc->ws.cap));
   P.tgrid = traceGrid();
@@ -842,6 +869,7 @@ int32_t lastInfoWord(const RenderPlan& P) {
     case IntegratorKind::Whitted: return DR_INTEGRATOR_WHITTED | 0x100 | (P.dlSpec ? 0x200 : 0);
     case IntegratorKind::AmbientOcclusion: return DR_INTEGRATOR_AO | 0x400;  // bit 10: k_shade_ao
     case IntegratorKind::Feature: return DR_INTEGRATOR_FEATURE | 0x800 | (P.feature.channel << 12);  // bit 11: k_shade_feature; bits 12-14: its channel
+    case IntegratorKind::DiffusePRT: return DR_INTEGRATOR_DIFFUSE_PRT | 0x8000;  // bit 15: k_shade_prt
   }
   return -1;
 }

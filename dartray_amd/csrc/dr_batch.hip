@@ -228,7 +228,7 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
   const bool log = stageCounts && round == 0;
   // ambient occlusion, the last stage of a round that another one follows: its output list -- the slots that hit, every one with rays still
   // to send -- is the next round's input and must outlive the reset of the stage counters: it goes to a round list and a round word
-  if (P.integrator == IntegratorKind::AmbientOcclusion && b + 1 == P.nStages && round + 1 < P.ao.rounds) {
+  if (b + 1 == P.nStages && round + 1 < P.shadowRounds()) {
     q.activeOut = (round & 1) ? w.roundB.p : w.roundA.p;
     q.nActiveOut = C + CounterLayout::roundNext(round);
     HIP_TRY(hipMemsetAsync(q.nActiveOut, 0, sizeof(uint32_t), s));
@@ -250,6 +250,13 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
       break;
     }
     case IntegratorKind::Feature: L.shade_feature(sc->d, stS, q, P.feature.channel, P.sgrid, s); break;  // (the only stage: nothing is traced behind it)
+    case IntegratorKind::DiffusePRT: {  // the stages and rounds of ambient occlusion; the fold adds to the slot's transfer coefficients (Workspace::prt)
+      const int first = round * P.prt.perRound;
+      const PrtArgs a = {P.prt.nSamples, P.prt.lmax, P.wsCap, 0u, w.prt.p, sc->prt.K.p, sc->prt.cin.p};
+      L.shade_prt(sc->d, rp, stS, q, a, b > 0 ? first + b - 1 : -1, b < P.prt.perRound ? first + b : -1, P.sgrid, s);
+      shadowRaysOnly = true;
+      break;
+    }
   }
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {
@@ -404,7 +411,7 @@ int BatchRunner::run() {
       rc = stage(b, round, roundQ, nRound);
       if (rc) return rc;
     }
-    if (round + 1 < P.ao.rounds) {  // ambient occlusion: the next 128 rays of every slot that hit (no count read back: the rounds are known)
+    if (round + 1 < P.shadowRounds()) {  // ambient occlusion, diffuse PRT: the next 128 rays of every slot that hit (no count read back: the rounds are known)
       roundQ = (round & 1) ? w.roundB.p : w.roundA.p;
       nRound = C + CounterLayout::roundNext(round);
       continue;

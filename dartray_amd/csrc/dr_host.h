@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "dr_kernels.h"
+#include "dr_prt.h"
 
 namespace dr_host {
 
@@ -79,12 +80,13 @@ struct Workspace {
     }
   } halton;
   DevBuf<float> filterTable, aosSamples;
+  DevBuf<float> prt;  // diffuse PRT: the transfer coefficients of every slot, [Terms(lmax)][cap]
   int spillGrid = 0;
   size_t bytes() const {  // device memory held right now (dr_scene_workspace_bytes): every buffer above
     return tiles.bytes() + scr.bytes() + genState.bytes() + tail.bytes() + tailOff.bytes() + activeA.bytes() + activeB.bytes() + closestQ.bytes() +
            anyQ.bytes() + counters.bytes() + spill.bytes() + envQ.bytes() + alive.bytes() + roundA.bytes() + roundB.bytes() + specFrames.bytes() +
            specSp.bytes() + pix.bytes() + adaptList.bytes() + adaptCount.bytes() + halton.idx.bytes() + halton.keyPix.bytes() + halton.blk.bytes() +
-           filterTable.bytes() + aosSamples.bytes();
+           filterTable.bytes() + aosSamples.bytes() + prt.bytes();
   }
 };
 
@@ -164,6 +166,14 @@ struct DrScene {
   int32_t lastInfo[8] = {0, 0, 0, -1, 0, 0, 0, 0};
   uint32_t adaptiveN = 0;  // dr_scene_get_adaptive_pixels: entries of ws.adaptList the last render left (0 after any other sampler's render)
   std::vector<int32_t> lightNSamples;
+  // diffuse PRT: per material DrMaterial.type, or -1 for a matte material with sigma != 0 (Oren-Nayar) -- what planRender refuses by
+  // name; and the incident-light coefficients of the last lmax asked for (prtIncident: c_in[Terms(lmax)][3], the K table; lmax 0: none yet)
+  std::vector<int32_t> prtMaterials;
+  struct {
+    DevBuf<double> K;
+    DevBuf<float> cin;
+    int lmax = 0;
+  } prt;
   bool hasSpecular = false;  // some material is a mirror / glass
   bool hasDeltaLight = false;
   // DirectLighting sample layout (direct_lighting_integrator.dart:70-87), fixed by the lights' nsamples
@@ -254,7 +264,7 @@ struct SampleForm {
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
   X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
-  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(film, launch_film)
+  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(film, launch_film)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -284,7 +294,8 @@ constexpr SamplerTraits kSamplerTraits[] = {
 // The surface integrators of the C ABI (DrRenderDesc.integrator) as the planner sees them, and what each one declares: every decision of
 // dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
 // source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
-enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature };
+// (no kind 6: the ABI leaves that value unassigned -- see DR_INTEGRATOR_DIFFUSE_PRT in dartray_hip.h -- and knownIntegrator refuses it like any other unknown value)
+enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7 };
 struct IntegratorTraits {
   bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
   int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
@@ -308,12 +319,25 @@ constexpr IntegratorTraits kIntegratorTraits[] = {
      "ambient occlusion integrator: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"},
     // Feature (no reference class): no requestSamples -- tau + scatter only; one stage, no ray beyond the camera's; max_depth and
     // the lights are not read
-    {false, 2, 0, false, false, nullptr, "feature integrator: the adaptive sampler is not supported"}};
+    {false, 2, 0, false, false, nullptr, "feature integrator: the adaptive sampler is not supported"},
+    {true, 0, 0, false, false, nullptr, nullptr},  // (6: unassigned, never read -- knownIntegrator says no -- and spelt as DirectAll, which an unknown value counts as)
+    // DiffusePRT (diffuse_prt_integrator.dart:42-81): an empty requestSamples -- tau + scatter only; one any-hit ray per stage, nsamples of
+    // them per camera hit in rounds of the stage loop, as for AmbientOcclusion; max_depth is not read
+    {false, 2, 0, false, false, nullptr,
+     "diffuse PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"}};
 static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
                   (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
                   (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && (int)IntegratorKind::Feature == DR_INTEGRATOR_FEATURE &&
-                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 6, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
-inline bool knownIntegrator(int32_t v) { return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])); }
+                  (int)IntegratorKind::DiffusePRT == DR_INTEGRATOR_DIFFUSE_PRT && sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 8, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
+// The one value inside the table's range that names no integrator: its row is a placeholder.  An integrator added later takes the value behind the
+// last one, not this one -- what the library answers for it is pinned behaviour (tests/test_feature_integrator.py)
+constexpr int32_t kUnassignedIntegrator = 6;
+static_assert(DR_INTEGRATOR_FEATURE < kUnassignedIntegrator && kUnassignedIntegrator < DR_INTEGRATOR_DIFFUSE_PRT &&
+                  kIntegratorTraits[kUnassignedIntegrator].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator].adaptive,
+              "the unassigned value lies between the feature and the diffuse PRT integrator and its row is the placeholder");
+inline bool knownIntegrator(int32_t v) {
+  return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && v != kUnassignedIntegrator;
+}
 
 // The feature integrator's refusals (dr_feature_check, planRender): null, or the text and its code
 inline const char* featureRefusal(int32_t channel, uint64_t nprims, int* code) {
@@ -365,6 +389,9 @@ struct RenderPlan {
   // (a round is perRound + 1 stages: CounterLayout::maxStages() bounds it); the rays' extent
   struct { int nSamples = 0, perRound = 0, rounds = 0; double minDist = 0.0, maxDist = 0.0; } ao;
   struct { int channel = 0; } feature;  // Feature: DR_FEATURE_*
+  // DiffusePRT: the rays in rounds exactly as AmbientOcclusion's; lmax
+  struct { int nSamples = 0, perRound = 0, rounds = 0, lmax = 0; } prt;
+  int shadowRounds() const { return integrator == IntegratorKind::DiffusePRT ? prt.rounds : ao.rounds; }  // rounds of one-ray stages (else 0)
   // the device sampler's launches for one batch (BatchRunner::loadSamples, the two sample dumps)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
   // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'

@@ -792,6 +792,9 @@ int SceneBuilder::finish() {
     if (desc->materials[i].type != DR_MATERIAL_MATTE) sc->d.hasSpec = 1;
     else if (desc->materials[i].sigma != 0.0) sc->d.hasSpec = 1;  // Oren-Nayar: general shading kernels too
   if (sc->hasDeltaLight) sc->d.hasSpec = 1;  // point lights are handled by the general kernels
+  sc->prtMaterials.clear();  // diffuse PRT names the materials it does not serve (planRender)
+  for (uint32_t i = 0; i < desc->nmaterials; ++i)
+    sc->prtMaterials.push_back(desc->materials[i].type == DR_MATERIAL_MATTE && desc->materials[i].sigma != 0.0 ? -1 : desc->materials[i].type);
   sc->hasSpecular = false;
   for (uint32_t i = 0; i < desc->nmaterials; ++i)
     if (desc->materials[i].type == DR_MATERIAL_MIRROR || desc->materials[i].type == DR_MATERIAL_GLASS) sc->hasSpecular = true;

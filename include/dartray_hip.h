@@ -244,6 +244,16 @@ typedef struct DrFilm {
  * DR_ERR_INVALID, DR_SAMPLER_ADAPTIVE with it DR_ERR_UNSUPPORTED, DR_FEATURE_ID over a scene of 2^24 primitives or more DR_ERR_UNSUPPORTED
  * (dr_feature_check says so without a scene); every other sampler mode is served. */
 #define DR_INTEGRATOR_FEATURE 5
+/* DiffusePRTIntegrator (diffuse_prt_integrator.dart:23-92 with core/spherical_harmonics.dart): soft environment and area
+ * lighting with self-shadowing from occlusion rays only.  Once per scene and lmax the lights' direct radiance at the centre of the world bound
+ * is projected onto (lmax + 1)^2 spherical harmonics (dr_prt_incident returns these coefficients); at every camera hit prt_nsamples rays
+ * Ray(p, w, rayEpsilon), w = UniformSampleSphere(Sample02(i, scramble)) with Dot(w, n) > 0 for the SHADING normal n facing the camera ray, project
+ * the cosine-weighted visibility onto the same basis, and Li = Le + Kd * clamp(dot of the two).  Its parameters travel in
+ * DrRenderDesc.prt_nsamples / prt_lmax; max_depth is not read.  It requests no sample slots (dr_sample_floats: 7) and the two randomUint() of the
+ * scramble are draws 0 and 1 of the sample's keyed in-Li stream (kind 2) in EVERY sampler mode, DR_SAMPLER_HOST_BUFFER included.  prt_nsamples is
+ * rounded up to a power of two as the constructor does; below 1 or above 4096, prt_lmax below 1 or above 8 are DR_ERR_INVALID; a scene with a
+ * material other than matte with sigma 0 and DR_SAMPLER_ADAPTIVE are DR_ERR_UNSUPPORTED, by name.  No host wait between the rounds of 128 rays. */
+#define DR_INTEGRATOR_DIFFUSE_PRT 7 /* (6 stays unassigned: dr_sample_floats and dr_render* keep answering it as they answer every unknown value) */
 /* DrRenderDesc.feature_channel: R, G, B at a hit.  Every value is >= 0 (the renderer blacks out a sample of negative luminance). */
 #define DR_FEATURE_NG 0    /* 0.5 * (isect.dg.nn + 1): the geometric normal, world space, reverseOrientation applied */
 #define DR_FEATURE_NS 1    /* 0.5 * (bsdf.dgShading.nn + 1): Triangle.getShadingGeometry (per-vertex N / S); else the geometric one */
@@ -320,7 +330,10 @@ typedef struct DrRenderDesc {
   const int32_t* pixel_xy;  /* [nsamples/spp][2] raster pixel of each group of spp samples */
   const float* sample_vec;  /* [nsamples][sample_stride]: imageU, imageV, lensU, lensV, time, oneD..., twoD... */
   int32_t sample_stride;
-  int32_t ao_nsamples;      /* DR_INTEGRATOR_AO: AmbientOcclusionIntegrator's ns (the former padding at offset 1324: read under that integrator only) */
+  union {
+    int32_t ao_nsamples;    /* DR_INTEGRATOR_AO: AmbientOcclusionIntegrator's ns (the former padding at offset 1324: read under that integrator only) */
+    int32_t prt_nsamples;   /* DR_INTEGRATOR_DIFFUSE_PRT: DiffusePRTIntegrator's ns (reference default 4096), read under that integrator only */
+  };
   /* DR_INTEGRATOR_AO draws from keyed streams in every sampler mode and reads no tail: under it, and only under it, the storage of the two tail
    * pointers carries AmbientOcclusionIntegrator.minDist / maxDist (Dart doubles).  Under every other integrator the unions are `tail` and
    * `tail_offsets` as they always were: same names, same offsets, same meaning. */
@@ -329,7 +342,10 @@ typedef struct DrRenderDesc {
     double ao_mindist;      /* DR_INTEGRATOR_AO: minDist (reference default 1e-4) */
   };
   int32_t max_tail;
-  int32_t feature_channel;  /* DR_INTEGRATOR_FEATURE: DR_FEATURE_* (the former padding at offset 1340: read under that integrator only) */
+  union {
+    int32_t feature_channel; /* DR_INTEGRATOR_FEATURE: DR_FEATURE_* (the former padding at offset 1340: read under that integrator only) */
+    int32_t prt_lmax;        /* DR_INTEGRATOR_DIFFUSE_PRT: lmax, 1 .. 8 (reference default 4), read under that integrator only */
+  };
   /* Optional packed form of `tail` (round 5): tail_offsets[nsamples + 1], non-decreasing; sample s owns
    * tail[tail_offsets[s] .. tail_offsets[s + 1]) -- the values it actually drew, in draw order (position p of the fixed
    * form = element p of the run; a read past the run yields 0.0 like the zero fill of the fixed form); max_tail stays the
@@ -466,9 +482,9 @@ int dr_scene_set_trace_kernels(DrScene* scene, const uint32_t kernels[2]);
 int dr_scene_get_pilot(const DrScene* scene, float ms_per_gb_out[6]);
 /* Diagnostics: what the scene's LAST dr_render_device call actually ran with, switches (dr_set_option / environment)
  * included -- out[0] path-state layout (64 / 4), out[1] / out[2] the traversal kernel of its closest-hit / any-hit launches
- * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED, DR_INTEGRATOR_AO or DR_INTEGRATOR_FEATURE render the integrator and its shading
+ * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED, DR_INTEGRATOR_AO, DR_INTEGRATOR_FEATURE or DR_INTEGRATOR_DIFFUSE_PRT render the integrator and its shading
  * kernels: bits 0-7 the DR_INTEGRATOR_* constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass), bit 10
- * k_shade_ao ran, bit 11 k_shade_feature ran (bits 12-14: its DR_FEATURE_* channel); out[4] the
+ * k_shade_ao ran, bit 11 k_shade_feature ran (bits 12-14: its DR_FEATURE_* channel), bit 15 k_shade_prt ran; out[4] the
  * calibration batches it ran (0: no pilot), out[5] its batches, out[6] workgroups per CU of a persistent traversal
  * launch, out[7] bit 0: a stage's any-hit launch ran beside its closest-hit launch, bit 1: the camera rays went through the
  * wave-coherent kernel (k_trace_pk), bit 3: the device sampler generated bounce b's blocks only for the pixel
@@ -516,6 +532,13 @@ int32_t dr_scene_sample_floats(const DrScene* scene, int32_t integrator);
  * DR_ERR_INVALID (no such channel) or DR_ERR_UNSUPPORTED (DR_FEATURE_ID with 2^24 primitives or more: an index would no longer be exact in the
  * film's f32), with dr_last_error's text.  dr_render* apply the same rule to their scene. */
 int dr_feature_check(int32_t channel, uint64_t nprimitives);
+/* DiffusePRTIntegrator.preprocess on the device: the scene's incident-light coefficients c_in for `lmax`, after
+ * ReduceRinging, as out[(lmax + 1)^2][3] (RGB) -- what a DR_INTEGRATOR_DIFFUSE_PRT render of the scene uses (computed once per scene and lmax).
+ * shutter_open is the reference's sample time; no light of the device path reads it.  lmax below 1 or above 8: DR_ERR_INVALID. */
+int dr_prt_incident(DrScene* scene, int32_t lmax, double shutter_open, float* out);
+/* SphericalHarmonics.Evaluate on the host, as the device evaluates it (one header compiled for both): the (lmax + 1)^2 harmonics of each of
+ * the n unit directions dirs[n][3] into out[n][(lmax + 1)^2], f64.  Needs no device.  lmax below 1 or above 8: DR_ERR_INVALID. */
+int dr_sh_evaluate(const double* dirs, int64_t n, int32_t lmax, double* out);
 
 /* Renderer.render(Scene) (lib/core/renderer.dart:28;
  * sampler_renderer.dart:36-65): traces this task's window and returns the
@@ -628,7 +651,9 @@ const char* dr_version(void);
  * host built against the earlier version-9 header, which never names the constant, runs unchanged; and DR_INTEGRATOR_FEATURE: a new constant
  * whose channel travels in the padding behind max_tail, read under that constant only, and one new entry point, dr_feature_check; and the
  * denoiser: one new struct, DrDenoiseParams, that only its three new entry points read -- dr_denoise_atrous_host, dr_denoise_atrous and
- * dr_denoise_atrous_device -- no existing struct, constant or call means anything else). */
+ * dr_denoise_atrous_device -- no existing struct, constant or call means anything else; and DR_INTEGRATOR_DIFFUSE_PRT: a new constant whose two
+ * parameters are union members at the offsets of ao_nsamples (prt_nsamples) and feature_channel (prt_lmax) -- storage that is read under one
+ * integrator's constant only -- and two new entry points, dr_prt_incident and dr_sh_evaluate: no field moved, 1352 bytes). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -734,6 +759,8 @@ DR_ABI_OFFSET(DrRenderDesc, tail, 1328);
 DR_ABI_OFFSET(DrRenderDesc, ao_mindist, 1328);
 DR_ABI_OFFSET(DrRenderDesc, max_tail, 1336);
 DR_ABI_OFFSET(DrRenderDesc, feature_channel, 1340);
+DR_ABI_OFFSET(DrRenderDesc, prt_nsamples, 1324);
+DR_ABI_OFFSET(DrRenderDesc, prt_lmax, 1340);
 DR_ABI_OFFSET(DrRenderDesc, tail_offsets, 1344);
 DR_ABI_OFFSET(DrRenderDesc, ao_maxdist, 1344);
 DR_ABI_SIZE(DrRenderStats, 200);

@@ -160,6 +160,8 @@ const int OFF_DrRenderDesc_tail = 1328;
 const int OFF_DrRenderDesc_ao_mindist = 1328;  // DR_INTEGRATOR_AO only: a double in the tail pointer's storage (that integrator reads no tail)
 const int OFF_DrRenderDesc_max_tail = 1336;
 const int OFF_DrRenderDesc_feature_channel = 1340;  // DR_INTEGRATOR_FEATURE only (the former padding)
+const int OFF_DrRenderDesc_prt_nsamples = 1324;  // DR_INTEGRATOR_DIFFUSE_PRT only: a union member at ao_nsamples' offset
+const int OFF_DrRenderDesc_prt_lmax = 1340;  // DR_INTEGRATOR_DIFFUSE_PRT only: a union member at feature_channel's offset
 const int OFF_DrRenderDesc_ao_maxdist = 1344;  // likewise, in the storage of tail_offsets
 const int OFF_DrRenderDesc_tail_offsets = 1344;  // host-buffer sampler only: stays NULL here (calloc'd descriptor)
 // DrDenoiseParams (the a-trous denoiser, DESIGN.md 2.15): int32 iterations (1 .. 8) at 0, then three f32 sharpness values k = 1 / sigma^2
@@ -179,6 +181,7 @@ const int DR_PRIM_QUADRIC = 0xFFFFFFFF, DR_QUADRIC_SPHERE = 1, DR_QUADRIC_DISK =
 const int DR_CAMERA_PERSPECTIVE = 0, DR_CAMERA_ORTHOGRAPHIC = 1, DR_CAMERA_ENVIRONMENT = 2;
 const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2, DR_INTEGRATOR_WHITTED = 3, DR_INTEGRATOR_AO = 4;
 const int DR_INTEGRATOR_FEATURE = 5;  // the first-hit feature integrator (FeatureIntegrator below): DrRenderDesc.feature_channel
+const int DR_INTEGRATOR_DIFFUSE_PRT = 7;  // DiffusePRTIntegrator (6 is unassigned): DrRenderDesc.prt_nsamples / prt_lmax
 const int DR_FEATURE_NG = 0, DR_FEATURE_NS = 1, DR_FEATURE_DEPTH = 2, DR_FEATURE_UV = 3, DR_FEATURE_ID = 4;
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
@@ -878,6 +881,14 @@ class HipSamplerRenderer extends Renderer {
         rd.i32(OFF_DrRenderDesc_ao_nsamples, ao.nSamples);
         rd.f64(OFF_DrRenderDesc_ao_mindist, minDist);
         rd.f64(OFF_DrRenderDesc_ao_maxdist, maxDist);
+      } else if ('${surfaceIntegrator.runtimeType}' == 'DiffusePRTIntegrator') {
+        // nSamples (already RoundUpPow2'd by the constructor) and lmax: diffuse_prt_integrator.dart:89-90; max_depth is not read
+        final dynamic prt = surfaceIntegrator;
+        final int lmax = prt.lmax;
+        rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_DIFFUSE_PRT);
+        rd.i32(OFF_DrRenderDesc_max_depth, 1);
+        rd.i32(OFF_DrRenderDesc_prt_nsamples, prt.nSamples);
+        rd.i32(OFF_DrRenderDesc_prt_lmax, lmax);
       } else if (surfaceIntegrator is FeatureIntegrator) {  // max_depth is not read
         final FeatureIntegrator feat = surfaceIntegrator;
         rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_FEATURE);
