@@ -18,6 +18,7 @@ DR_INTEGRATOR_WHITTED = 3
 DR_INTEGRATOR_AO = 4  # ao_nsamples / ao_mindist / ao_maxdist; max_depth is not read
 DR_INTEGRATOR_FEATURE = 5  # feature_channel; max_depth is not read
 DR_INTEGRATOR_DIFFUSE_PRT = 7  # (6 stays unassigned) prt_nsamples / prt_lmax; max_depth is not read
+DR_INTEGRATOR_GLOSSY_PRT = 9  # (8 stays unassigned) prt_nsamples / prt_lmax; Kd, Ks, roughness by dr_scene_set_glossy_prt; max_depth is not read
 DR_FEATURE_NG, DR_FEATURE_NS, DR_FEATURE_DEPTH, DR_FEATURE_UV, DR_FEATURE_ID = 0, 1, 2, 3, 4
 DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
@@ -144,9 +145,14 @@ class DrRenderDesc(C.Structure):
     ao_maxdist = _Overlay(1344, C.c_double)
     # DR_INTEGRATOR_FEATURE's channel: the padding behind max_tail
     feature_channel = _Overlay(1340, C.c_int32)
-    # DR_INTEGRATOR_DIFFUSE_PRT's two parameters: union members at the offsets of ao_nsamples and feature_channel (each read under one integrator only)
+    # DR_INTEGRATOR_DIFFUSE_PRT's and DR_INTEGRATOR_GLOSSY_PRT's two parameters: union members at the offsets of ao_nsamples and feature_channel (each read under one integrator only)
     prt_nsamples = _Overlay(1324, C.c_int32)
     prt_lmax = _Overlay(1340, C.c_int32)
+
+
+class DrGlossyPrtParams(C.Structure):
+    """GlossyPRTIntegrator's Kd, Ks, roughness (dr_scene_set_glossy_prt): roughness is a Dart double."""
+    _fields_ = [("Kd", C.c_float * 3), ("Ks", C.c_float * 3), ("roughness", C.c_double)]
 
 
 class DrRenderStats(C.Structure):
@@ -202,6 +208,11 @@ EXPORTS = {
     "dr_feature_check": (C.c_int, [C.c_int32, C.c_uint64]),
     "dr_prt_incident": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
     "dr_sh_evaluate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
+    "dr_scene_set_glossy_prt": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dr_prt_bsdf_matrix": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "dr_sh_rotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "dr_sh_bsdf_matrix_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "dr_sh_rotate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "dr_render": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_device": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_sharded": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_int32, C.c_void_p, C.c_void_p]),

@@ -353,11 +353,12 @@ class _DeviceScene:
         return {"state_layout": int(arr[0]), "closest_kernel": int(arr[1]), "any_hit_kernel": int(arr[2]),
                 "pilot_batches": int(arr[4]), "batches": int(arr[5]), "trace_wg_per_cu": int(arr[6]), "overlap_any": int(arr[7]) & 1,
                 "coherent_camera": (int(arr[7]) >> 1) & 1, "lazy_gen": (int(arr[7]) >> 3) & 1,
-                # arr[3]: -1, or after a WhittedIntegrator / AmbientOcclusionIntegrator / FeatureIntegrator / DiffusePRTIntegrator render the integrator and its shading kernels
+                # arr[3]: -1, or after a WhittedIntegrator / AmbientOcclusionIntegrator / FeatureIntegrator / DiffusePRTIntegrator / GlossyPRTIntegrator render the integrator and its shading kernels
                 "integrator": None if arr[3] < 0 else {_abi.DR_INTEGRATOR_WHITTED: "whitted", _abi.DR_INTEGRATOR_AO: "ambientocclusion",
-                                                       _abi.DR_INTEGRATOR_FEATURE: "feature", _abi.DR_INTEGRATOR_DIFFUSE_PRT: "diffuseprt"}.get(int(arr[3]) & 255),
+                                                       _abi.DR_INTEGRATOR_FEATURE: "feature", _abi.DR_INTEGRATOR_DIFFUSE_PRT: "diffuseprt",
+                                                       _abi.DR_INTEGRATOR_GLOSSY_PRT: "glossyprt"}.get(int(arr[3]) & 255),
                 "shade_kernels": [] if arr[3] < 0 else [k for bit, k in ((8, "k_shade_whitted"), (9, "k_shade_spec"), (10, "k_shade_ao"),
-                                                                         (11, "k_shade_feature"), (15, "k_shade_prt")) if (int(arr[3]) >> bit) & 1],
+                                                                         (11, "k_shade_feature"), (15, "k_shade_prt"), (16, "k_shade_gprt"), (16, "k_gprt_finish")) if (int(arr[3]) >> bit) & 1],
                 "feature_channel": (int(arr[3]) >> 12) & 7 if arr[3] >= 0 and (int(arr[3]) >> 11) & 1 else None}
 
     def adaptive_pixels(self):

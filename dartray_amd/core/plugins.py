@@ -5,7 +5,7 @@ from .cameras import EnvironmentCamera, OrthographicCamera, PerspectiveCamera
 from .film import BoxFilter, GaussianFilter, ImageFilm, LanczosSincFilter, MitchellFilter, TriangleFilter
 from .lights import DiffuseAreaLight
 from .materials import MatteMaterial
-from .renderer import (AmbientOcclusionIntegrator, DiffusePRTIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, PathIntegrator, SamplerRenderer,
+from .renderer import (AmbientOcclusionIntegrator, DiffusePRTIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, GlossyPRTIntegrator, PathIntegrator, SamplerRenderer,
                        WhittedIntegrator)
 from .samplers import (AdaptiveSampler, HaltonSampler, LinearPixelSampler, LowDiscrepancySampler, RandomPixelSampler, RandomSampler,
                        StratifiedSampler, TilePixelSampler)
@@ -34,6 +34,7 @@ def RegisterStandardPlugins():
     Plugin.register("surfaceIntegrator", "ambientocclusion", AmbientOcclusionIntegrator.Create)
     Plugin.register("surfaceIntegrator", "feature", FeatureIntegrator.Create)
     Plugin.register("surfaceIntegrator", "diffuseprt", DiffusePRTIntegrator.Create)
+    Plugin.register("surfaceIntegrator", "glossyprt", GlossyPRTIntegrator.Create)
     Plugin.register("volumeIntegrator", "emission", lambda ps=None: EmissionIntegrator((ps or {}).get("stepsize", 1.0)))
     Plugin.register("renderer", "sampler", SamplerRenderer)
     Plugin.register("sampler", "lowdiscrepancy", LowDiscrepancySampler)

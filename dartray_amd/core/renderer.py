@@ -182,6 +182,79 @@ class DiffusePRTIntegrator:
         return DiffusePRTIntegrator(ps.get("lmax", 4), ps.get("nsamples", 4096))
 
 
+class GlossyPRTIntegrator:
+    """surface_integrators/glossy_prt_integrator.dart:23-134: the incident light c_in as DiffusePRTIntegrator projects it and the BSDF matrix B of
+    Lambertian(Kd) + Microfacet(Ks, FresnelDielectric(1.5, 1), Blinn(1 / roughness)) once (preprocess); at every camera hit the transfer matrix T
+    from nSamples = RoundUpPow2(ns) occlusion rays, Li = Le + clamp(sum_i (B . Rotate(T . c_in))[i] * Ylm_i(woLocal)).  On the device
+    DR_INTEGRATOR_GLOSSY_PRT (k_shade_gprt, k_gprt_finish, dr_prt_project.hip).  It reads no material function: every material
+    the device path has is accepted."""
+
+    LMAX_MAX = 4
+
+    def __init__(self, Kd=0.5, Ks=0.25, roughness=0.1, lmax=4, nSamples=4096):
+        rgb = lambda v: tuple(float(x) for x in (v if np.ndim(v) else (v, v, v)))
+        self.Kd, self.Ks, self.roughness = rgb(Kd), rgb(Ks), float(roughness)
+        self.lmax = int(lmax)
+        if self.lmax < 1:
+            raise ValueError("glossy PRT: lmax must be at least 1 (the Legendre recurrence stores P(1, 0) unconditionally)")
+        if self.lmax > self.LMAX_MAX:
+            raise ValueError("glossy PRT: lmax above 4 (the x-rotation rows are restated band by band, and a wave's registers hold the 325 "
+                             "distinct elements of a transfer matrix at lmax 4)")
+        if int(nSamples) < 1:
+            raise ValueError("glossy PRT: nsamples must be at least 1")
+        self.nSamples = RoundUpPow2(int(nSamples))                 # :25
+        if self.nSamples > 4096:
+            raise ValueError("glossy PRT: nsamples above 4096 after rounding up to a power of two (the samplers' cap)")
+
+    kind = _abi.DR_INTEGRATOR_GLOSSY_PRT
+    maxDepth = 1  # (not read by the device under this integrator; SamplerRenderer.describe marshals every integrator's)
+    li_draws_recorded = False  # (the scramble's two randomUint() are keyed (pixel, sample) draws in every sampler mode, DESIGN.md 2.17)
+
+    def requestSamples(self, sampler, scene):
+        """The reference's requestSamples is empty (:53-54): no slots of its own."""
+        return [], []
+
+    def check_sampler(self, sampler):
+        """SamplerRenderer.describe: what this integrator asks of the renderer's sampler."""
+        if isinstance(sampler, AdaptiveSampler):
+            raise ValueError("glossy PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no "
+                             "test; every other sampler mode is)")
+        if getattr(sampler, "sampler_mode", None) == _abi.DR_SAMPLER_HOST_BUFFER and sampler.li_seed is None:
+            raise ValueError("a GlossyPRTIntegrator draws its scramble from the keyed (pixel, sample) streams in every sampler mode: "
+                             "give the HostBufferSampler the seed of the render it replays (seed=...)")
+
+    def to_abi(self, d):
+        """SamplerRenderer.describe: the two parameters that travel in the descriptor (the union members diffuse PRT uses, read under this
+        integrator's constant); Kd, Ks and roughness are set on the scene (bind)."""
+        d.prt_nsamples = self.nSamples
+        d.prt_lmax = self.lmax
+
+    def bind(self, scene):
+        """Sets Kd, Ks, roughness on the device scene (dr_scene_set_glossy_prt), where the BSDF matrix is cached per parameter set."""
+        p = _abi.DrGlossyPrtParams((C.c_float * 3)(*self.Kd), (C.c_float * 3)(*self.Ks), self.roughness)
+        _abi.check(_abi.lib().dr_scene_set_glossy_prt(scene._device().handle, C.byref(p)))
+
+    def incident(self, scene, shutterOpen=0.0):
+        """preprocess (:27-44) on the device: c_in after ReduceRinging, [(lmax + 1)^2, 3] f32 (dr_prt_incident)."""
+        out = np.zeros(((self.lmax + 1) ** 2, 3), np.float32)
+        _abi.check(_abi.lib().dr_prt_incident(scene._device().handle, self.lmax, float(shutterOpen), out.ctypes.data))
+        return out
+
+    def bsdf_matrix(self, scene, nsamples_b=1024):
+        """preprocess (:46-48) on the device: B, [(lmax + 1)^2, (lmax + 1)^2, 3] f32 (dr_prt_bsdf_matrix); a render uses nsamples_b = 1024."""
+        self.bind(scene)
+        t = (self.lmax + 1) ** 2
+        out = np.zeros((t, t, 3), np.float32)
+        _abi.check(_abi.lib().dr_prt_bsdf_matrix(scene._device().handle, self.lmax, int(nsamples_b), out.ctypes.data))
+        return out
+
+    @staticmethod
+    def Create(params=None):
+        """GlossyPRTIntegrator.Create (:118-125): `Kd` 0.5, `Ks` 0.25, `roughness` 0.1, `lmax` 4, `nsamples` 4096."""
+        ps = params or {}
+        return GlossyPRTIntegrator(ps.get("Kd", 0.5), ps.get("Ks", 0.25), ps.get("roughness", 0.1), ps.get("lmax", 4), ps.get("nsamples", 4096))
+
+
 class FeatureIntegrator:
     """The first-hit feature integrator (DR_INTEGRATOR_FEATURE, k_shade_feature; the reference has no such class): Li is one
     quantity of the camera ray's Intersection -- `channel` "ng" / "ns" (0.5 * (normal + 1), geometric / shading), "depth" (t, t, t), "uv"
@@ -304,8 +377,14 @@ class SamplerRenderer:
         """The incident-light coefficients a DiffusePRTIntegrator render of `scene` uses (dr_prt_incident), [(lmax + 1)^2, 3] f32."""
         return self.surfaceIntegrator.incident(scene, self.camera.shutterOpen)
 
+    def prt_bsdf_matrix(self, scene, nsamples_b=1024):
+        """The BSDF matrix a GlossyPRTIntegrator render of `scene` uses (dr_prt_bsdf_matrix), [(lmax + 1)^2, (lmax + 1)^2, 3] f32."""
+        return self.surfaceIntegrator.bsdf_matrix(scene, nsamples_b)
+
     def render(self, scene):
         film = self.camera.film
+        if hasattr(self.surfaceIntegrator, "bind"):  # (an integrator with parameters that live on the scene: GlossyPRTIntegrator)
+            self.surfaceIntegrator.bind(scene)
         d, keep = self.describe()
         out_film = np.zeros((film.height, film.width, 4), dtype=np.float32)
         out_rgb = np.zeros((film.height, film.width, 3), dtype=np.float32)
@@ -325,6 +404,8 @@ class SamplerRenderer:
         the communicator of dr_comm_init, and on the root rank the OutputImage; other ranks return None.  What
         RenderManager's fan-out and rectangle merge do in the host (render_manager.dart:100-141), as one C call."""
         film = self.camera.film
+        if hasattr(self.surfaceIntegrator, "bind"):
+            self.surfaceIntegrator.bind(scene)
         d, keep = self.describe()
         lib = _abi.lib()
         is_root = lib.dr_comm_world() <= 1 or lib.dr_comm_rank() == root
@@ -348,6 +429,8 @@ class SamplerRenderer:
     def render_device(self, scene, film_ptr, stream=0):
         """Renderer.render with the film left in HBM: accumulates this renderer's share into the
         [height, width, 4] f32 device buffer at `film_ptr` on HIP stream `stream` (asynchronous)."""
+        if hasattr(self.surfaceIntegrator, "bind"):
+            self.surfaceIntegrator.bind(scene)
         d, keep = self.describe()
         dev = scene._device()
         _abi.check(_abi.lib().dr_render_device(dev.handle, C.byref(d), film_ptr, stream))

@@ -568,6 +568,20 @@ int planRender(RenderPlan& P) {
       P.nStages = P.prt.perRound + 1;
       break;
     }
+    case IntegratorKind::GlossyPRT: {
+      // GlossyPRTIntegrator (glossy_prt_integrator.dart:24-25,118-125): DiffusePRT's rays, stages and rounds -- every ray is traced --
+      // and no material function is read, so no material is refused
+      if (const char* why = gprtRefusal(rd->prt_lmax, rd->prt_nsamples, true)) return fail(DR_ERR_INVALID, why);
+      uint32_t ns = 1;
+      while (ns < (uint32_t)rd->prt_nsamples) ns <<= 1;  // RoundUpPow2 (common.dart:117-125)
+      P.gprt.nSamples = (int)ns;
+      P.gprt.perRound = std::min(P.gprt.nSamples, 128);
+      P.gprt.rounds = P.gprt.nSamples / P.gprt.perRound;
+      P.gprt.lmax = rd->prt_lmax;
+      P.gprt.words = std::max(1, P.gprt.nSamples / 32);
+      P.nStages = P.gprt.perRound + 1;
+      break;
+    }
   }
   rp.dlSpecular = P.dlSpec ? 1 : 0;
   rp.deferredNee = P.integ->pathStages ? 1 : 0;
@@ -686,7 +700,8 @@ int planBatches(RenderPlan& P) {
     const uint64_t perSlot = (uint64_t)P.maxStateWords * 4 + (uint64_t)(P.wsSf.svWords() + 15) / 16 + 20 + tailPerSlot + (!P.traits->deviceGenerated ? (uint64_t)rd->sample_stride * 4 : 0) +
                              (sf.compact ? (uint64_t)(16 * sf.nBlocks + spp - 1) / spp : 0) +  // scramble words + generator states, per (block, pixel)
                              (P.dlSpec ? (uint64_t)std::max(1, rd->max_depth) * sizeof(SpecFrame) + 12 : 0) +
-                             (P.prt.lmax ? (uint64_t)sh_terms(P.prt.lmax) * 4 + 8 : 0);  // diffuse PRT: the slot's transfer coefficients + the round lists
+                             (P.prt.lmax ? (uint64_t)sh_terms(P.prt.lmax) * 4 + 8 : 0) +  // diffuse PRT: the slot's transfer coefficients + the round lists
+                             (P.gprt.lmax ? (uint64_t)P.gprt.words * 4 + 4 + 8 : 0);  // glossy PRT: the slot's visibility words, its hit mark + the round lists
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
       const uint64_t have = (uint64_t)sc->ws.cap * ((uint64_t)sc->ws.stateWords * 4 + sc->ws.svWords / 16 + 20);
@@ -772,6 +787,14 @@ int prepareRender(RenderPlan& P) {
     // capacity an earlier, larger render left the workspace with -- and, once per scene and lmax, before the first batch, the incident light
     HIP_TRY(sc->ws.prt.alloc((size_t)P.wsCap * (size_t)sh_terms(P.prt.lmax)));
     rc = prtIncident(sc, P.prt.lmax, rd->camera.shutter_open, P.s);
+    if (rc) return rc;
+  }
+  if (P.integrator == IntegratorKind::GlossyPRT) {
+    // the side buffers, sized like diffuse PRT's by this plan's batch capacity, and, once per scene and key, before the first batch, the incident
+    // light and the BSDF matrix (ComputeBSDFMatrix(..., 1024, lmax): glossy_prt_integrator.dart:48)
+    HIP_TRY(sc->ws.gprtBits.alloc((size_t)P.wsCap * (size_t)P.gprt.words));
+    HIP_TRY(sc->ws.gprtMark.alloc((size_t)P.wsCap));
+    rc = gprtBsdfMatrix(sc, P.gprt.lmax, 1024, rd->camera.shutter_open, P.s);
     if (rc) return rc;
   }
   if (P.envStage) HIP_TRY(sc->ws.envQ.alloc(sc->ws.cap));
@@ -870,6 +893,7 @@ int32_t lastInfoWord(const RenderPlan& P) {
     case IntegratorKind::AmbientOcclusion: return DR_INTEGRATOR_AO | 0x400;  // bit 10: k_shade_ao
     case IntegratorKind::Feature: return DR_INTEGRATOR_FEATURE | 0x800 | (P.feature.channel << 12);  // bit 11: k_shade_feature; bits 12-14: its channel
     case IntegratorKind::DiffusePRT: return DR_INTEGRATOR_DIFFUSE_PRT | 0x8000;  // bit 15: k_shade_prt
+    case IntegratorKind::GlossyPRT: return DR_INTEGRATOR_GLOSSY_PRT | 0x10000;  // bit 16: k_shade_gprt + k_gprt_finish
   }
   return -1;
 }

@@ -53,6 +53,7 @@ class BatchRunner {
   void logTrace(StageLog& g, int any);
   void readCtrNow(TraceCounters* c);
   StageQueues stageQueues(int b, const uint32_t* roundQ, const uint32_t* nRound);
+  GprtArgs gprtArgs() const;  // glossy PRT: the side buffers and the scene's tables
   int stage(int b, int round, const uint32_t* roundQ, const uint32_t* nRound);
   int specRound(int round, const uint32_t*& roundQ, const uint32_t*& nRound, bool& done);
   int finish();
@@ -203,6 +204,10 @@ void BatchRunner::logTrace(StageLog& g, int any) {
   (any ? g.a1 : g.c1) = sc->traceEvents.back().e1;
 }
 
+GprtArgs BatchRunner::gprtArgs() const {
+  return GprtArgs{P.gprt.nSamples, P.gprt.lmax, P.wsCap, (uint32_t)P.gprt.words, w.gprtBits.p, w.gprtMark.p, sc->prt.K.p, sc->prt.cin.p, sc->gprt.B.p};
+}
+
 StageQueues BatchRunner::stageQueues(int b, const uint32_t* roundQ, const uint32_t* nRound) {
   StageQueues q;
   auto cnt = [&](int j, int stg) { return C + CounterLayout::stageCount(j, stg); };
@@ -254,6 +259,13 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
       const int first = round * P.prt.perRound;
       const PrtArgs a = {P.prt.nSamples, P.prt.lmax, P.wsCap, 0u, w.prt.p, sc->prt.K.p, sc->prt.cin.p};
       L.shade_prt(sc->d, rp, stS, q, a, b > 0 ? first + b - 1 : -1, b < P.prt.perRound ? first + b : -1, P.sgrid, s);
+      shadowRaysOnly = true;
+      break;
+    }
+    case IntegratorKind::GlossyPRT: {  // the same stages and rounds; the fold records one visibility bit (Workspace::gprtBits)
+      const int first = round * P.gprt.perRound;
+      L.shade_gprt(sc->d, rp, stS, q, gprtArgs(), b > 0 ? first + b - 1 : -1, b < P.gprt.perRound ? first + b : -1, P.sgrid, s);
+      if (b + 1 == P.nStages && round + 1 == P.gprt.rounds) L.gprt_finish(stS, gprtArgs(), s);  // behind the last fold: the rest of Li, one wave per slot
       shadowRaysOnly = true;
       break;
     }

@@ -16,6 +16,7 @@
 
 #include "dr_kernels.h"
 #include "dr_prt.h"
+#include "dr_gprt.h"
 
 namespace dr_host {
 
@@ -81,12 +82,13 @@ struct Workspace {
   } halton;
   DevBuf<float> filterTable, aosSamples;
   DevBuf<float> prt;  // diffuse PRT: the transfer coefficients of every slot, [Terms(lmax)][cap]
+  DevBuf<uint32_t> gprtBits, gprtMark;  // glossy PRT: one visibility bit per ray and slot, [max(1, nSamples / 32)][cap], and the slots that hit, [cap]
   int spillGrid = 0;
   size_t bytes() const {  // device memory held right now (dr_scene_workspace_bytes): every buffer above
     return tiles.bytes() + scr.bytes() + genState.bytes() + tail.bytes() + tailOff.bytes() + activeA.bytes() + activeB.bytes() + closestQ.bytes() +
            anyQ.bytes() + counters.bytes() + spill.bytes() + envQ.bytes() + alive.bytes() + roundA.bytes() + roundB.bytes() + specFrames.bytes() +
            specSp.bytes() + pix.bytes() + adaptList.bytes() + adaptCount.bytes() + halton.idx.bytes() + halton.keyPix.bytes() + halton.blk.bytes() +
-           filterTable.bytes() + aosSamples.bytes() + prt.bytes();
+           filterTable.bytes() + aosSamples.bytes() + prt.bytes() + gprtBits.bytes() + gprtMark.bytes();
   }
 };
 
@@ -173,7 +175,18 @@ struct DrScene {
     DevBuf<double> K;
     DevBuf<float> cin;
     int lmax = 0;
+    uint32_t after[2] = {0u, 0u};  // the two randomUint() of the preprocess RNG behind the lights' draws: ComputeBSDFMatrix's scramble
   } prt;
+  // glossy PRT: Kd, Ks, roughness (dr_scene_set_glossy_prt; the reference's defaults until then) and the BSDF matrix
+  // B[Terms][Terms][3] of the key (lmax, ns, Kd, Ks, roughness) it was last computed for (gprtBsdfMatrix; lmax 0: none yet)
+  struct {
+    float Kd[3] = {0.5f, 0.5f, 0.5f}, Ks[3] = {0.25f, 0.25f, 0.25f};
+    double roughness = 0.1;
+    DevBuf<float> B;
+    int lmax = 0, ns = 0;
+    float keyKd[3] = {0.f, 0.f, 0.f}, keyKs[3] = {0.f, 0.f, 0.f};
+    double keyRoughness = 0.0;
+  } gprt;
   bool hasSpecular = false;  // some material is a mirror / glass
   bool hasDeltaLight = false;
   // DirectLighting sample layout (direct_lighting_integrator.dart:70-87), fixed by the lights' nsamples
@@ -264,7 +277,7 @@ struct SampleForm {
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
   X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
-  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(film, launch_film)
+  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(shade_gprt, launch_shade_gprt) X(gprt_finish, launch_gprt_finish) X(film, launch_film)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -295,7 +308,7 @@ constexpr SamplerTraits kSamplerTraits[] = {
 // dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
 // source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
 // (no kind 6: the ABI leaves that value unassigned -- see DR_INTEGRATOR_DIFFUSE_PRT in dartray_hip.h -- and knownIntegrator refuses it like any other unknown value)
-enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7 };
+enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7, GlossyPRT = 9 };
 struct IntegratorTraits {
   bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
   int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
@@ -324,19 +337,30 @@ constexpr IntegratorTraits kIntegratorTraits[] = {
     // DiffusePRT (diffuse_prt_integrator.dart:42-81): an empty requestSamples -- tau + scatter only; one any-hit ray per stage, nsamples of
     // them per camera hit in rounds of the stage loop, as for AmbientOcclusion; max_depth is not read
     {false, 2, 0, false, false, nullptr,
-     "diffuse PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"}};
+     "diffuse PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"},
+    {true, 0, 0, false, false, nullptr, nullptr},  // (8: unassigned like 6 -- what the library answers for it is pinned by tests/test_prt_integrator.py)
+    // GlossyPRT (glossy_prt_integrator.dart:53-116): an empty requestSamples -- tau + scatter only; DiffusePRT's stages and rounds,
+    // then one finish launch per batch; max_depth is not read
+    {false, 2, 0, false, false, nullptr,
+     "glossy PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"}};
 static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
                   (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
                   (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && (int)IntegratorKind::Feature == DR_INTEGRATOR_FEATURE &&
-                  (int)IntegratorKind::DiffusePRT == DR_INTEGRATOR_DIFFUSE_PRT && sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 8, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
+                  (int)IntegratorKind::DiffusePRT == DR_INTEGRATOR_DIFFUSE_PRT && (int)IntegratorKind::GlossyPRT == DR_INTEGRATOR_GLOSSY_PRT &&
+                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 10, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
 // The one value inside the table's range that names no integrator: its row is a placeholder.  An integrator added later takes the value behind the
 // last one, not this one -- what the library answers for it is pinned behaviour (tests/test_feature_integrator.py)
 constexpr int32_t kUnassignedIntegrator = 6;
 static_assert(DR_INTEGRATOR_FEATURE < kUnassignedIntegrator && kUnassignedIntegrator < DR_INTEGRATOR_DIFFUSE_PRT &&
                   kIntegratorTraits[kUnassignedIntegrator].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator].adaptive,
               "the unassigned value lies between the feature and the diffuse PRT integrator and its row is the placeholder");
+// ... and the second one, between the two PRT integrators, for the same reason (tests/test_prt_integrator.py pins dr_sample_floats(8, 3))
+constexpr int32_t kUnassignedIntegrator2 = 8;
+static_assert(DR_INTEGRATOR_DIFFUSE_PRT < kUnassignedIntegrator2 && kUnassignedIntegrator2 < DR_INTEGRATOR_GLOSSY_PRT &&
+                  kIntegratorTraits[kUnassignedIntegrator2].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator2].adaptive,
+              "the second unassigned value lies between the diffuse and the glossy PRT integrator and its row is the placeholder");
 inline bool knownIntegrator(int32_t v) {
-  return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && v != kUnassignedIntegrator;
+  return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && v != kUnassignedIntegrator && v != kUnassignedIntegrator2;
 }
 
 // The feature integrator's refusals (dr_feature_check, planRender): null, or the text and its code
@@ -391,7 +415,9 @@ struct RenderPlan {
   struct { int channel = 0; } feature;  // Feature: DR_FEATURE_*
   // DiffusePRT: the rays in rounds exactly as AmbientOcclusion's; lmax
   struct { int nSamples = 0, perRound = 0, rounds = 0, lmax = 0; } prt;
-  int shadowRounds() const { return integrator == IntegratorKind::DiffusePRT ? prt.rounds : ao.rounds; }  // rounds of one-ray stages (else 0)
+  // GlossyPRT: the same rounds; words of visibility bits per slot
+  struct { int nSamples = 0, perRound = 0, rounds = 0, lmax = 0, words = 0; } gprt;
+  int shadowRounds() const { return integrator == IntegratorKind::DiffusePRT ? prt.rounds : integrator == IntegratorKind::GlossyPRT ? gprt.rounds : ao.rounds; }  // rounds of one-ray stages (else 0)
   // the device sampler's launches for one batch (BatchRunner::loadSamples, the two sample dumps)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
   // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'

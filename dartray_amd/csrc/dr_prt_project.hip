@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "dr_host.h"
+#include "dr_gprt.h"
 #include "dr_rng.h"
 #include "dr_li_sampling.h"
 
@@ -177,6 +178,65 @@ __global__ void __launch_bounds__(256) k_prt_ringing(float* cd, int lmax) {
   cd[tc] = (float)((double)cd[tc] * sh_ringing_scale(l, 0.005));
 }
 
+// ---- the glossy PRT integrator's BSDF matrix ----
+struct GprtBsdf {
+  float Kd[3], Ks[3];
+  double bexp, pdfN;
+};
+// w[i] = UniformSampleSphere(Sample02(i, scramble)) and Evaluate(w[i], lmax, Ylm, lmax_terms * i) into the Float32List: one lane per direction
+__global__ void __launch_bounds__(128) k_gprt_dirs(uint32_t scr0, uint32_t scr1, int n, int lmax, const double* K, float* w, float* Y) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const uint32_t scramble[2] = {scr0, scr1};
+  float v[3];
+  sh_sample_sphere((uint32_t)i, scramble, v);
+  float Yl[DR_SH_MAX_TERMS];
+  sh_evaluate((double)v[0], (double)v[1], (double)v[2], lmax, K, Yl);
+  const int terms = sh_terms(lmax);
+  for (int k = 0; k < 3; ++k) w[3 * (size_t)i + k] = v[k];
+  for (int k = 0; k < terms; ++k) Y[(size_t)i * terms + k] = Yl[k];
+}
+// f[osamp][isamp]: one lane per pair
+__global__ void __launch_bounds__(256) k_gprt_pairs(GprtBsdf b, int n, const float* w, float* f) {
+  const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (uint32_t)n * (uint32_t)n) return;
+  const uint32_t o = idx / (uint32_t)n, i = idx % (uint32_t)n;
+  sh_bsdf_pair(b.Kd, b.Ks, b.bexp, w + 3 * (size_t)o, w + 3 * (size_t)i, b.pdfN, f + 3 * (size_t)idx);
+}
+// B[i][j][ch] = the serial f32 sum over osamp, then isamp, of f * (Ylm[isamp][j] * Ylm[osamp][i]): one lane per (i, j, channel)
+__global__ void __launch_bounds__(64) k_gprt_bsum(int n, int terms, const float* Y, const float* f, float* B) {
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (t >= 3 * terms * terms) return;
+  const int ch = t % 3, j = (t / 3) % terms, i = t / (3 * terms);
+  float acc = 0.f;
+  for (int o = 0; o < n; ++o) {
+    const float Yoi = Y[(size_t)o * terms + i];
+    const float* fo = f + (size_t)o * n * 3 + ch;
+    int is = 0;
+    for (; is + 8 <= n; is += 8) {
+      float fv[8], yv[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        fv[k] = fo[3 * (size_t)(is + k)];
+        yv[k] = Y[(size_t)(is + k) * terms + j];
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) acc = sh_bsdf_step(acc, fv[k], yv[k], Yoi);
+    }
+    for (; is < n; ++is) acc = sh_bsdf_step(acc, fo[3 * (size_t)is], Y[(size_t)is * terms + j], Yoi);
+  }
+  B[t] = acc;
+}
+// dr_sh_rotate_device: sh_to_zyz and sh_rotate_channel by one lane per (frame, channel)
+__global__ void __launch_bounds__(64) k_gprt_rotate(const float* c_in, const float* m16, int lmax, int nframes, float* out) {
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (t >= 3 * nframes) return;
+  const int fr = t / 3, ch = t % 3, terms = sh_terms(lmax);
+  double alpha, beta, gamma;
+  sh_to_zyz(m16 + 16 * (size_t)fr, &alpha, &beta, &gamma);
+  sh_rotate_channel(c_in + (size_t)fr * terms * 3 + ch, 3, alpha, beta, gamma, lmax, out + (size_t)fr * terms * 3 + ch);
+}
+
 uint32_t roundUpPow2(uint32_t v) {
   uint32_t n = 1;
   while (n < v) n <<= 1;
@@ -276,6 +336,60 @@ int prtIncident(DrScene* sc, int lmax, double shutterOpen, hipStream_t s) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
   sc->prt.lmax = lmax;
+  // GlossyPRTIntegrator.preprocess hands the SAME RNG to ComputeBSDFMatrix (glossy_prt_integrator.dart:42-48): its scramble is the two draws behind
+  // whatever the lights consumed (the draws do not depend on lmax)
+  sc->prt.after[0] = rng.randomUint();
+  sc->prt.after[1] = rng.randomUint();
+  return DR_OK;
+}
+
+// ComputeBSDFMatrix (core/spherical_harmonics.dart:609-672) in the two-kernel pattern above: the directions and their Float32List harmonics, then
+// f * |cos| / pdf_nSamples of every (osamp, isamp) pair (black: +0), then one lane per (i, j, channel) adding the pairs in the reference's order.
+int gprtBsdfMatrix(DrScene* sc, int lmax, int ns, double shutterOpen, hipStream_t s) {
+  int rc = prtIncident(sc, lmax, shutterOpen, s);
+  if (rc) return rc;
+  auto& g = sc->gprt;
+  if (g.B.p && g.lmax == lmax && g.ns == ns && memcmp(g.keyKd, g.Kd, sizeof(g.Kd)) == 0 && memcmp(g.keyKs, g.Ks, sizeof(g.Ks)) == 0 &&
+      memcmp(&g.keyRoughness, &g.roughness, sizeof(double)) == 0)
+    return DR_OK;
+  g.lmax = 0;
+  const int terms = sh_terms(lmax);
+  DevBuf<float> w, Y, f;
+  HIP_TRY(w.alloc((size_t)ns * 3));
+  HIP_TRY(Y.alloc((size_t)ns * terms));
+  HIP_TRY(f.alloc((size_t)ns * ns * 3));
+  HIP_TRY(g.B.alloc((size_t)3 * DR_GPRT_MAX_TERMS * DR_GPRT_MAX_TERMS));
+  GprtBsdf b;
+  memcpy(b.Kd, g.Kd, sizeof(b.Kd));
+  memcpy(b.Ks, g.Ks, sizeof(b.Ks));
+  b.bexp = sh_blinn_exponent(g.roughness);
+  b.pdfN = sh_bsdf_pdf_nsamples(ns);
+  hipLaunchKernelGGL(k_gprt_dirs, dim3((ns + 127) / 128), dim3(128), 0, s, sc->prt.after[0], sc->prt.after[1], ns, lmax, sc->prt.K.p, w.p, Y.p);
+  const uint32_t npairs = (uint32_t)ns * (uint32_t)ns;
+  hipLaunchKernelGGL(k_gprt_pairs, dim3((npairs + 255) / 256), dim3(256), 0, s, b, ns, w.p, f.p);
+  const int nOut = 3 * terms * terms;
+  hipLaunchKernelGGL(k_gprt_bsum, dim3((nOut + 63) / 64), dim3(64), 0, s, ns, terms, Y.p, f.p, g.B.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s));
+  g.lmax = lmax;
+  g.ns = ns;
+  memcpy(g.keyKd, g.Kd, sizeof(g.Kd));
+  memcpy(g.keyKs, g.Ks, sizeof(g.Ks));
+  g.keyRoughness = g.roughness;
+  return DR_OK;
+}
+
+int gprtRotateDevice(const float* c_in, const float* m16, int lmax, int nframes, float* out) {
+  const int terms = sh_terms(lmax);
+  DevBuf<float> dc, dm, dout;
+  HIP_TRY(dc.alloc((size_t)nframes * terms * 3));
+  HIP_TRY(dm.alloc((size_t)nframes * 16));
+  HIP_TRY(dout.alloc((size_t)nframes * terms * 3));
+  HIP_TRY(hipMemcpy(dc.p, c_in, (size_t)nframes * terms * 3 * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dm.p, m16, (size_t)nframes * 16 * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_gprt_rotate, dim3((3 * nframes + 63) / 64), dim3(64), 0, nullptr, dc.p, dm.p, lmax, nframes, dout.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, (size_t)nframes * terms * 3 * sizeof(float), hipMemcpyDeviceToHost));
   return DR_OK;
 }
 
@@ -289,6 +403,66 @@ int dr_prt_incident(DrScene* sc, int32_t lmax, double shutter_open, float* out) 
   const int rc = prtIncident(sc, lmax, shutter_open, nullptr);
   if (rc) return rc;
   HIP_TRY(hipMemcpy(out, sc->prt.cin.p, 3 * sh_terms(lmax) * sizeof(float), hipMemcpyDeviceToHost));
+  return DR_OK;
+}
+
+int dr_scene_set_glossy_prt(DrScene* sc, const DrGlossyPrtParams* p) {
+  if (!sc || !p) return fail(DR_ERR_INVALID, "null argument");
+  memcpy(sc->gprt.Kd, p->Kd, sizeof(p->Kd));
+  memcpy(sc->gprt.Ks, p->Ks, sizeof(p->Ks));
+  sc->gprt.roughness = p->roughness;
+  return DR_OK;
+}
+
+int dr_prt_bsdf_matrix(DrScene* sc, int32_t lmax, int32_t nsamples_b, float* out) {
+  if (!sc || !out) return fail(DR_ERR_INVALID, "null argument");
+  if (const char* why = gprtRefusal(lmax, 1, false)) return fail(DR_ERR_INVALID, why);
+  if (nsamples_b < 1 || nsamples_b > 1024) return fail(DR_ERR_INVALID, "glossy PRT: the BSDF matrix's nsamples_b must be 1 to 1024");
+  const int rc = gprtBsdfMatrix(sc, lmax, nsamples_b, 0.0, nullptr);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(out, sc->gprt.B.p, (size_t)3 * sh_terms(lmax) * sh_terms(lmax) * sizeof(float), hipMemcpyDeviceToHost));
+  return DR_OK;
+}
+
+int dr_sh_rotate(const float* c_in, const float* m16, int32_t lmax, float* out) {
+  if (!c_in || !m16 || !out) return fail(DR_ERR_INVALID, "null argument");
+  if (const char* why = gprtRefusal(lmax, 1, false)) return fail(DR_ERR_INVALID, why);
+  double alpha, beta, gamma;
+  sh_to_zyz(m16, &alpha, &beta, &gamma);
+  for (int ch = 0; ch < 3; ++ch) sh_rotate_channel(c_in + ch, 3, alpha, beta, gamma, lmax, out + ch);
+  return DR_OK;
+}
+
+int dr_sh_rotate_device(const float* c_in, const float* m16, int32_t lmax, int32_t nframes, float* out) {
+  if (!c_in || !m16 || !out || nframes < 1) return fail(DR_ERR_INVALID, "null argument");
+  if (const char* why = gprtRefusal(lmax, 1, false)) return fail(DR_ERR_INVALID, why);
+  return gprtRotateDevice(c_in, m16, lmax, nframes, out);
+}
+
+int dr_sh_bsdf_matrix_host(const float* Kd, const float* Ks, double roughness, const uint32_t* scramble, int32_t nsamples_b, int32_t lmax, float* out) {
+  if (!Kd || !Ks || !scramble || !out) return fail(DR_ERR_INVALID, "null argument");
+  if (const char* why = gprtRefusal(lmax, 1, false)) return fail(DR_ERR_INVALID, why);
+  if (nsamples_b < 1 || nsamples_b > 1024) return fail(DR_ERR_INVALID, "glossy PRT: the BSDF matrix's nsamples_b must be 1 to 1024");
+  const int terms = sh_terms(lmax), n = nsamples_b;
+  double K[DR_SH_MAX_TERMS];
+  sh_K_table(lmax, K);
+  std::vector<float> w((size_t)n * 3), Y((size_t)n * terms);
+  for (int i = 0; i < n; ++i) {
+    sh_sample_sphere((uint32_t)i, scramble, &w[3 * (size_t)i]);
+    sh_evaluate((double)w[3 * (size_t)i], (double)w[3 * (size_t)i + 1], (double)w[3 * (size_t)i + 2], lmax, K, &Y[(size_t)i * terms]);
+  }
+  const double bexp = sh_blinn_exponent(roughness), pdfN = sh_bsdf_pdf_nsamples(n);
+  for (int k = 0; k < 3 * terms * terms; ++k) out[k] = 0.f;
+  for (int o = 0; o < n; ++o)
+    for (int is = 0; is < n; ++is) {
+      float f[3];
+      sh_bsdf_pair(Kd, Ks, bexp, &w[3 * (size_t)o], &w[3 * (size_t)is], pdfN, f);
+      if (!(f[0] != 0.0f || f[1] != 0.0f || f[2] != 0.0f)) continue;
+      for (int i = 0; i < terms; ++i)
+        for (int j = 0; j < terms; ++j)
+          for (int ch = 0; ch < 3; ++ch)
+            out[(size_t)(i * terms + j) * 3 + ch] = sh_bsdf_step(out[(size_t)(i * terms + j) * 3 + ch], f[ch], Y[(size_t)is * terms + j], Y[(size_t)o * terms + i]);
+    }
   return DR_OK;
 }
 

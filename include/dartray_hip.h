@@ -254,6 +254,17 @@ typedef struct DrFilm {
  * rounded up to a power of two as the constructor does; below 1 or above 4096, prt_lmax below 1 or above 8 are DR_ERR_INVALID; a scene with a
  * material other than matte with sigma 0 and DR_SAMPLER_ADAPTIVE are DR_ERR_UNSUPPORTED, by name.  No host wait between the rounds of 128 rays. */
 #define DR_INTEGRATOR_DIFFUSE_PRT 7 /* (6 stays unassigned: dr_sample_floats and dr_render* keep answering it as they answer every unknown value) */
+/* GlossyPRTIntegrator (glossy_prt_integrator.dart:23-134 with core/spherical_harmonics.dart): view-dependent highlights
+ * under soft environment and area light, from occlusion rays only.  Once per scene the incident light c_in (as for DR_INTEGRATOR_DIFFUSE_PRT)
+ * and the BSDF matrix B of Lambertian(Kd) + Microfacet(Ks, FresnelDielectric(1.5, 1), Blinn(1 / roughness)) over 1024 x 1024 direction pairs
+ * (dr_scene_set_glossy_prt sets Kd, Ks, roughness; dr_prt_bsdf_matrix returns B); at every camera hit prt_nsamples rays Ray(p, w, rayEpsilon),
+ * w = UniformSampleSphere(Sample02(i, scramble)) -- every one traced -- give the transfer matrix T, and
+ * Li = Le + clamp(sum_i (B . Rotate(T . c_in))[i] * Ylm_i(woLocal)), Rotate being the reference's (its lists share objects: DESIGN.md,
+ * "Reference quirks that are reproduced").  Parameters in DrRenderDesc.prt_nsamples / prt_lmax; max_depth is not read; no sample slots
+ * (dr_sample_floats: 7); the scramble's two randomUint() are draws 0 and 1 of the sample's keyed in-Li stream (kind 2) in every sampler mode.
+ * prt_nsamples is rounded up to a power of two; below 1 or above 4096, prt_lmax below 1 or above 4 are DR_ERR_INVALID; DR_SAMPLER_ADAPTIVE is
+ * DR_ERR_UNSUPPORTED, by name.  It reads no material function, so no material is refused. */
+#define DR_INTEGRATOR_GLOSSY_PRT 9 /* (8, like 6, stays unassigned and is answered as every unknown value is) */
 /* DrRenderDesc.feature_channel: R, G, B at a hit.  Every value is >= 0 (the renderer blacks out a sample of negative luminance). */
 #define DR_FEATURE_NG 0    /* 0.5 * (isect.dg.nn + 1): the geometric normal, world space, reverseOrientation applied */
 #define DR_FEATURE_NS 1    /* 0.5 * (bsdf.dgShading.nn + 1): Triangle.getShadingGeometry (per-vertex N / S); else the geometric one */
@@ -332,7 +343,7 @@ typedef struct DrRenderDesc {
   int32_t sample_stride;
   union {
     int32_t ao_nsamples;    /* DR_INTEGRATOR_AO: AmbientOcclusionIntegrator's ns (the former padding at offset 1324: read under that integrator only) */
-    int32_t prt_nsamples;   /* DR_INTEGRATOR_DIFFUSE_PRT: DiffusePRTIntegrator's ns (reference default 4096), read under that integrator only */
+    int32_t prt_nsamples;   /* DR_INTEGRATOR_DIFFUSE_PRT / DR_INTEGRATOR_GLOSSY_PRT: the integrator's ns (reference default 4096), read under those two only */
   };
   /* DR_INTEGRATOR_AO draws from keyed streams in every sampler mode and reads no tail: under it, and only under it, the storage of the two tail
    * pointers carries AmbientOcclusionIntegrator.minDist / maxDist (Dart doubles).  Under every other integrator the unions are `tail` and
@@ -344,7 +355,7 @@ typedef struct DrRenderDesc {
   int32_t max_tail;
   union {
     int32_t feature_channel; /* DR_INTEGRATOR_FEATURE: DR_FEATURE_* (the former padding at offset 1340: read under that integrator only) */
-    int32_t prt_lmax;        /* DR_INTEGRATOR_DIFFUSE_PRT: lmax, 1 .. 8 (reference default 4), read under that integrator only */
+    int32_t prt_lmax;        /* DR_INTEGRATOR_DIFFUSE_PRT: lmax, 1 .. 8; DR_INTEGRATOR_GLOSSY_PRT: 1 .. 4 (reference default 4), read under those two only */
   };
   /* Optional packed form of `tail` (round 5): tail_offsets[nsamples + 1], non-decreasing; sample s owns
    * tail[tail_offsets[s] .. tail_offsets[s + 1]) -- the values it actually drew, in draw order (position p of the fixed
@@ -484,7 +495,8 @@ int dr_scene_get_pilot(const DrScene* scene, float ms_per_gb_out[6]);
  * included -- out[0] path-state layout (64 / 4), out[1] / out[2] the traversal kernel of its closest-hit / any-hit launches
  * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED, DR_INTEGRATOR_AO, DR_INTEGRATOR_FEATURE or DR_INTEGRATOR_DIFFUSE_PRT render the integrator and its shading
  * kernels: bits 0-7 the DR_INTEGRATOR_* constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass), bit 10
- * k_shade_ao ran, bit 11 k_shade_feature ran (bits 12-14: its DR_FEATURE_* channel), bit 15 k_shade_prt ran; out[4] the
+ * k_shade_ao ran, bit 11 k_shade_feature ran (bits 12-14: its DR_FEATURE_* channel), bit 15 k_shade_prt ran, bit 16 k_shade_gprt and k_gprt_finish
+ * ran (DR_INTEGRATOR_GLOSSY_PRT); out[4] the
  * calibration batches it ran (0: no pilot), out[5] its batches, out[6] workgroups per CU of a persistent traversal
  * launch, out[7] bit 0: a stage's any-hit launch ran beside its closest-hit launch, bit 1: the camera rays went through the
  * wave-coherent kernel (k_trace_pk), bit 3: the device sampler generated bounce b's blocks only for the pixel
@@ -539,6 +551,28 @@ int dr_prt_incident(DrScene* scene, int32_t lmax, double shutter_open, float* ou
 /* SphericalHarmonics.Evaluate on the host, as the device evaluates it (one header compiled for both): the (lmax + 1)^2 harmonics of each of
  * the n unit directions dirs[n][3] into out[n][(lmax + 1)^2], f64.  Needs no device.  lmax below 1 or above 8: DR_ERR_INVALID. */
 int dr_sh_evaluate(const double* dirs, int64_t n, int32_t lmax, double* out);
+/* GlossyPRTIntegrator's Kd, Ks and roughness.  roughness is a Dart double (1 / 0.1 is 10, 1 / 0.1f is not), so it
+ * travels as one. */
+typedef struct DrGlossyPrtParams {
+  float Kd[3];       /* reference default 0.5 */
+  float Ks[3];       /* reference default 0.25 */
+  double roughness;  /* reference default 0.1 */
+} DrGlossyPrtParams;
+/* Sets the scene's glossy PRT parameters (the reference's defaults until the first call).  The BSDF matrix is computed at the next
+ * DR_INTEGRATOR_GLOSSY_PRT render or dr_prt_bsdf_matrix call and kept per (lmax, nsamples_b, Kd, Ks, roughness).  Nothing is validated, as in
+ * the reference: negative or NaN colours go into the matrix as they are; the Blinn exponent 1 / roughness is clamped to 10000 when it is above
+ * that or NaN (blinn.dart:24-28), so roughness 0 means 10000 and a negative roughness a negative exponent. */
+int dr_scene_set_glossy_prt(DrScene* scene, const DrGlossyPrtParams* params);
+/* ComputeBSDFMatrix on the device with nsamples_b directions (a render always uses 1024; 1 .. 1024 here), out[(lmax + 1)^2][(lmax + 1)^2][3].
+ * Its scramble is the two draws of the preprocess RNG behind the lights' projection.  lmax below 1 or above 4: DR_ERR_INVALID. */
+int dr_prt_bsdf_matrix(DrScene* scene, int32_t lmax, int32_t nsamples_b, float* out);
+/* Host builds of the headers the device compiles.  Need no device.
+ * dr_sh_rotate: SphericalHarmonics.Rotate of c_in[(lmax + 1)^2][3] by the Matrix4x4 m16 (row major) into out, object sharing included.
+ * dr_sh_bsdf_matrix_host: ComputeBSDFMatrix with the given scramble words.  dr_sh_rotate_device: dr_sh_rotate of nframes (c_in, m16) pairs, one
+ * device lane per frame and channel. */
+int dr_sh_rotate(const float* c_in, const float* m16, int32_t lmax, float* out);
+int dr_sh_bsdf_matrix_host(const float* Kd, const float* Ks, double roughness, const uint32_t* scramble, int32_t nsamples_b, int32_t lmax, float* out);
+int dr_sh_rotate_device(const float* c_in, const float* m16, int32_t lmax, int32_t nframes, float* out);
 
 /* Renderer.render(Scene) (lib/core/renderer.dart:28;
  * sampler_renderer.dart:36-65): traces this task's window and returns the
@@ -653,7 +687,9 @@ const char* dr_version(void);
  * denoiser: one new struct, DrDenoiseParams, that only its three new entry points read -- dr_denoise_atrous_host, dr_denoise_atrous and
  * dr_denoise_atrous_device -- no existing struct, constant or call means anything else; and DR_INTEGRATOR_DIFFUSE_PRT: a new constant whose two
  * parameters are union members at the offsets of ao_nsamples (prt_nsamples) and feature_channel (prt_lmax) -- storage that is read under one
- * integrator's constant only -- and two new entry points, dr_prt_incident and dr_sh_evaluate: no field moved, 1352 bytes). */
+ * integrator's constant only -- and two new entry points, dr_prt_incident and dr_sh_evaluate: no field moved, 1352 bytes; and
+ * DR_INTEGRATOR_GLOSSY_PRT: a new constant that reads the same two union members, one new struct, DrGlossyPrtParams, that only its new entry point
+ * dr_scene_set_glossy_prt reads, and four more new entry points: dr_prt_bsdf_matrix, dr_sh_rotate, dr_sh_bsdf_matrix_host, dr_sh_rotate_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 

@@ -182,6 +182,9 @@ const int DR_CAMERA_PERSPECTIVE = 0, DR_CAMERA_ORTHOGRAPHIC = 1, DR_CAMERA_ENVIR
 const int DR_INTEGRATOR_DIRECT_ALL = 0, DR_INTEGRATOR_PATH = 1, DR_INTEGRATOR_DIRECT_ONE = 2, DR_INTEGRATOR_WHITTED = 3, DR_INTEGRATOR_AO = 4;
 const int DR_INTEGRATOR_FEATURE = 5;  // the first-hit feature integrator (FeatureIntegrator below): DrRenderDesc.feature_channel
 const int DR_INTEGRATOR_DIFFUSE_PRT = 7;  // DiffusePRTIntegrator (6 is unassigned): DrRenderDesc.prt_nsamples / prt_lmax
+const int DR_INTEGRATOR_GLOSSY_PRT = 9;  // GlossyPRTIntegrator (8 is unassigned): the same two fields; Kd, Ks, roughness by dr_scene_set_glossy_prt
+// DrGlossyPrtParams: f32 Kd[3] at 0, f32 Ks[3] at 12, f64 roughness at 24
+const int SIZEOF_DrGlossyPrtParams = 32, OFF_DrGlossyPrtParams_Kd = 0, OFF_DrGlossyPrtParams_Ks = 12, OFF_DrGlossyPrtParams_roughness = 24;
 const int DR_FEATURE_NG = 0, DR_FEATURE_NS = 1, DR_FEATURE_DEPTH = 2, DR_FEATURE_UV = 3, DR_FEATURE_ID = 4;
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
@@ -211,6 +214,8 @@ typedef _CommInitD = int Function(int, int, Pointer<Uint8>, int);
 typedef _CommVoidC = Int32 Function();
 typedef _SetOptionC = Int32 Function(Pointer<Utf8>, Pointer<Utf8>);
 typedef _SetOptionD = int Function(Pointer<Utf8>, Pointer<Utf8>);
+typedef _SetGlossyPrtC = Int32 Function(Pointer<Void>, Pointer<Uint8>);  // (scene, DrGlossyPrtParams*)
+typedef _SetGlossyPrtD = int Function(Pointer<Void>, Pointer<Uint8>);
 typedef _SetLayoutC = Int32 Function(Pointer<Void>, Int32);
 typedef _SetLayoutD = int Function(Pointer<Void>, int);
 typedef _CommVoidD = int Function();
@@ -322,6 +327,7 @@ class HipSamplerRenderer extends Renderer {
   static final _CommVoidD _commRank = _lib.lookupFunction<_CommVoidC, _CommVoidD>('dr_comm_rank');
   static final _CommVoidD _commAvailable = _lib.lookupFunction<_CommVoidC, _CommVoidD>('dr_comm_available');
   static final _SetOptionD _setOption = _lib.lookupFunction<_SetOptionC, _SetOptionD>('dr_set_option');
+  static final _SetGlossyPrtD _setGlossyPrt = _lib.lookupFunction<_SetGlossyPrtC, _SetGlossyPrtD>('dr_scene_set_glossy_prt');
   static final _SetLayoutD _setStateLayout = _lib.lookupFunction<_SetLayoutC, _SetLayoutD>('dr_scene_set_state_layout');
   static final _GetLayoutD _getStateLayout = _lib.lookupFunction<_GetLayoutC, _GetLayoutD>('dr_scene_get_state_layout');
   static final _KernelsD _getTraceKernels = _lib.lookupFunction<_KernelsC, _KernelsD>('dr_scene_get_trace_kernels');
@@ -889,6 +895,25 @@ class HipSamplerRenderer extends Renderer {
         rd.i32(OFF_DrRenderDesc_max_depth, 1);
         rd.i32(OFF_DrRenderDesc_prt_nsamples, prt.nSamples);
         rd.i32(OFF_DrRenderDesc_prt_lmax, lmax);
+      } else if ('${surfaceIntegrator.runtimeType}' == 'GlossyPRTIntegrator') {
+        // nSamples (already RoundUpPow2'd by the constructor) and lmax (1 .. 4 on the device): glossy_prt_integrator.dart:130-131; Kd, Ks and
+        // roughness (:127-129) are set on the scene, where the BSDF matrix is cached per parameter set; max_depth is not read
+        final dynamic gprt = surfaceIntegrator;
+        final int lmax = gprt.lmax;
+        rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_GLOSSY_PRT);
+        rd.i32(OFF_DrRenderDesc_max_depth, 1);
+        rd.i32(OFF_DrRenderDesc_prt_nsamples, gprt.nSamples);
+        rd.i32(OFF_DrRenderDesc_prt_lmax, lmax);
+        final _Blob gp = _Blob(SIZEOF_DrGlossyPrtParams);
+        try {
+          final RGBColor kd = gprt.Kd.toRGB(), ks = gprt.Ks.toRGB();
+          gp.f32s(OFF_DrGlossyPrtParams_Kd, [kd.c[0], kd.c[1], kd.c[2]]);
+          gp.f32s(OFF_DrGlossyPrtParams_Ks, [ks.c[0], ks.c[1], ks.c[2]]);
+          gp.f64(OFF_DrGlossyPrtParams_roughness, gprt.roughness);
+          _check(_setGlossyPrt(handle.value, gp.ptr));
+        } finally {
+          gp.free();
+        }
       } else if (surfaceIntegrator is FeatureIntegrator) {  // max_depth is not read
         final FeatureIntegrator feat = surfaceIntegrator;
         rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_FEATURE);
