@@ -19,6 +19,7 @@ DR_INTEGRATOR_AO = 4  # ao_nsamples / ao_mindist / ao_maxdist; max_depth is not 
 DR_INTEGRATOR_FEATURE = 5  # feature_channel; max_depth is not read
 DR_INTEGRATOR_DIFFUSE_PRT = 7  # (6 stays unassigned) prt_nsamples / prt_lmax; max_depth is not read
 DR_INTEGRATOR_GLOSSY_PRT = 9  # (8 stays unassigned) prt_nsamples / prt_lmax; Kd, Ks, roughness by dr_scene_set_glossy_prt; max_depth is not read
+DR_INTEGRATOR_USE_PROBES = 11  # (10 stays unassigned) the grid by dr_scene_set_probes; the scene's DirectLighting "all" slots; max_depth is not read
 DR_FEATURE_NG, DR_FEATURE_NS, DR_FEATURE_DEPTH, DR_FEATURE_UV, DR_FEATURE_ID = 0, 1, 2, 3, 4
 DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
@@ -155,6 +156,12 @@ class DrGlossyPrtParams(C.Structure):
     _fields_ = [("Kd", C.c_float * 3), ("Ks", C.c_float * 3), ("roughness", C.c_double)]
 
 
+class DrProbesDesc(C.Structure):
+    """CreateProbesRenderer's parameters (dr_probes_grid / dr_probes_candidates / dr_probes_bake): include/dartray_hip.h."""
+    _fields_ = [("lmax", C.c_int32), ("include_indirect", C.c_int32), ("npoints", C.c_int32), ("has_bounds", C.c_int32),
+                ("bounds", C.c_float * 6), ("camera_pos", C.c_float * 3), ("pad", C.c_float), ("spacing", C.c_double), ("time", C.c_double)]
+
+
 class DrRenderStats(C.Structure):
     _fields_ = [("camera_samples", C.c_uint64), ("film_samples", C.c_uint64),
                 ("closest_rays", C.c_uint64), ("any_rays", C.c_uint64),
@@ -213,6 +220,11 @@ EXPORTS = {
     "dr_sh_rotate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "dr_sh_bsdf_matrix_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "dr_sh_rotate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "dr_probes_surface_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    "dr_probes_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dr_probes_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "dr_probes_bake": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "dr_scene_set_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "dr_render": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_device": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_sharded": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_int32, C.c_void_p, C.c_void_p]),

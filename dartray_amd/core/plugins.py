@@ -6,7 +6,7 @@ from .film import BoxFilter, GaussianFilter, ImageFilm, LanczosSincFilter, Mitch
 from .lights import DiffuseAreaLight
 from .materials import MatteMaterial
 from .renderer import (AmbientOcclusionIntegrator, DiffusePRTIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, GlossyPRTIntegrator, PathIntegrator, SamplerRenderer,
-                       WhittedIntegrator)
+                       UseProbesIntegrator, WhittedIntegrator)
 from .samplers import (AdaptiveSampler, HaltonSampler, LinearPixelSampler, LowDiscrepancySampler, RandomPixelSampler, RandomSampler,
                        StratifiedSampler, TilePixelSampler)
 from .shapes import TriangleMesh
@@ -35,6 +35,7 @@ def RegisterStandardPlugins():
     Plugin.register("surfaceIntegrator", "feature", FeatureIntegrator.Create)
     Plugin.register("surfaceIntegrator", "diffuseprt", DiffusePRTIntegrator.Create)
     Plugin.register("surfaceIntegrator", "glossyprt", GlossyPRTIntegrator.Create)
+    Plugin.register("surfaceIntegrator", "useprobes", UseProbesIntegrator.Create)
     Plugin.register("volumeIntegrator", "emission", lambda ps=None: EmissionIntegrator((ps or {}).get("stepsize", 1.0)))
     Plugin.register("renderer", "sampler", SamplerRenderer)
     Plugin.register("sampler", "lowdiscrepancy", LowDiscrepancySampler)

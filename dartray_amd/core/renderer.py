@@ -255,6 +255,90 @@ class GlossyPRTIntegrator:
         return GlossyPRTIntegrator(ps.get("Kd", 0.5), ps.get("Ks", 0.25), ps.get("roughness", 0.1), ps.get("lmax", 4), ps.get("nsamples", 4096))
 
 
+class ProbeGrid:
+    """A grid of radiance probes in the reference's Float32List form (create_probes_renderer.dart:139-160): lmax, includeDirect, includeIndirect,
+    nProbes[3], the six bounds, the coefficients [cell][(lmax + 1)^2][3], three zeros.  `save` / `load`: the text form the reference's ReadFloatFile
+    parses (common.dart:188-236) -- numbers of digits, '.', 'e', '-', '+' between white space, '#' comments -- every value with the nine
+    significant digits that give a float32 back bit for bit."""
+
+    def __init__(self, data):
+        self.data = np.ascontiguousarray(data, np.float32).reshape(-1)
+        if len(self.data) < 15:
+            raise ValueError("a probe grid has at least 15 floats")
+
+    lmax = property(lambda self: int(self.data[0]))
+    includeDirect = property(lambda self: int(self.data[1]))
+    includeIndirect = property(lambda self: int(self.data[2]))
+    nProbes = property(lambda self: tuple(int(v) for v in self.data[3:6]))
+    bounds = property(lambda self: self.data[6:12].copy())
+
+    @property
+    def coefficients(self):
+        """[cells, (lmax + 1)^2, 3] f32, cell = x + y * nProbes[0] + z * nProbes[0] * nProbes[1]."""
+        return self.data[12:-3].reshape(-1, (self.lmax + 1) ** 2, 3)
+
+    def save(self, path):
+        if not np.isfinite(self.data).all():
+            raise ValueError("a probe grid with a value that is not finite has no text form (ReadFloatFile reads digits, '.', 'e', '-', '+')")
+        with open(path, "w") as f:
+            f.write("# radiance probes: lmax includeDirect includeIndirect nProbes[3] bounds[6] coefficients zeros[3]\n")
+            for i in range(0, len(self.data), 6):
+                f.write(" ".join("%.9g" % float(v) for v in self.data[i:i + 6]) + "\n")   # (the last number needs the newline: ReadFloatFile drops one that ends the text)
+
+    @staticmethod
+    def load(path):
+        vals = []
+        with open(path) as f:
+            for line in f:
+                vals.extend(float(t) for t in line.split("#", 1)[0].split())
+        return ProbeGrid(np.array(vals, np.float64).astype(np.float32))
+
+
+class UseProbesIntegrator:
+    """surface_integrators/use_probes_integrator.dart:23-185: Li = Le + rho * INV_PI * clamp(E(n)), E the irradiance function of a grid of radiance
+    probes -- interpolated trilinearly at the hit, convolved with the clamped cosine, evaluated at the shading normal facing the camera ray.  On the
+    device DR_INTEGRATOR_USE_PROBES (k_shade_probes).  `probes`: a ProbeGrid (SamplerRenderer.create_probes bakes one), a float
+    array in its form, or a file name.  Materials: matte with sigma 0; a grid baked without direct light is refused by name at render time."""
+
+    def __init__(self, probes=None):
+        if isinstance(probes, str):
+            try:
+                probes = ProbeGrid.load(probes)
+            except (OSError, ValueError) as e:
+                raise ValueError("use probes: cannot read the probe file %r (the `filename` parameter, default \"probes.out\": bake one with "
+                                 "SamplerRenderer.create_probes(scene).save(filename)): %s" % (probes, e)) from e
+        self.probes = probes if isinstance(probes, ProbeGrid) or probes is None else ProbeGrid(probes)
+
+    kind = _abi.DR_INTEGRATOR_USE_PROBES
+    maxDepth = 1  # (not read by the device under this integrator; SamplerRenderer.describe marshals every integrator's)
+    li_draws_recorded = False  # (Li draws nothing that feeds its result: rho2's jitter is skipped for Lambertian lobes, DESIGN.md 2.18)
+    bind_for_dumps = True  # (generate_samples / generate_halton_samples plan like a render: the plan refuses a scene without a grid)
+
+    def requestSamples(self, sampler, scene):
+        """:74-88: a light and a BSDF slot pair of sampler.roundSize(nSamples) entries per light -- DirectLighting "all"'s -- although Li reads none."""
+        ns = [sampler.roundSize(L.nSamples) for L in scene.lights]
+        return [n for k in ns for n in (k, k)], [n for k in ns for n in (k, k)]
+
+    def check_sampler(self, sampler):
+        """SamplerRenderer.describe: what this integrator asks of the renderer's sampler."""
+        if isinstance(sampler, AdaptiveSampler):
+            raise ValueError("use probes: the adaptive sampler is not supported (its second pass has no test under this integrator; every other "
+                             "sampler mode is)")
+
+    def bind(self, scene):
+        """Attaches the grid to the device scene (dr_scene_set_probes); none: detaches whatever an earlier integrator attached."""
+        h = scene._device().handle
+        if self.probes is None:
+            _abi.check(_abi.lib().dr_scene_set_probes(h, None, 0))
+        else:
+            _abi.check(_abi.lib().dr_scene_set_probes(h, self.probes.data.ctypes.data, len(self.probes.data)))
+
+    @staticmethod
+    def Create(params=None):
+        """UseProbesIntegrator.Create (:172-175): `filename` "probes.out"."""
+        return UseProbesIntegrator((params or {}).get("filename", "probes.out"))
+
+
 class FeatureIntegrator:
     """The first-hit feature integrator (DR_INTEGRATOR_FEATURE, k_shade_feature; the reference has no such class): Li is one
     quantity of the camera ray's Intersection -- `channel` "ng" / "ns" (0.5 * (normal + 1), geometric / shading), "depth" (t, t, t), "uv"
@@ -349,6 +433,8 @@ class SamplerRenderer:
     def generate_samples(self, scene, pixels):
         """dr_generate_samples: the device sampler's vectors for the raster pixels `pixels` ([n, 2]) -> [n * spp, nFloats] f32
         (AdaptiveSampler: the first pass's, spp = minSamples)."""
+        if getattr(self.surfaceIntegrator, "bind_for_dumps", False):  # (the dump plans like a render, and UseProbesIntegrator's plan asks for the scene's grid)
+            self.surfaceIntegrator.bind(scene)
         d, keep = self.describe()
         dev = scene._device()
         pixels = np.ascontiguousarray(pixels, dtype=np.int32).reshape(-1, 2)
@@ -360,6 +446,8 @@ class SamplerRenderer:
     def generate_halton_samples(self, scene, first=0, count=None):
         """dr_generate_halton_samples: the device sampler's accepted samples among the indices [first, first + count) of this task's
         sequence (count None: to its end) -> (k [n] uint64, pixel_xy [n, 2] int32, vectors [n, nFloats] f32), in increasing k."""
+        if getattr(self.surfaceIntegrator, "bind_for_dumps", False):
+            self.surfaceIntegrator.bind(scene)
         d, keep = self.describe()
         dev = scene._device()
         if count is None:
@@ -376,6 +464,50 @@ class SamplerRenderer:
     def prt_incident(self, scene):
         """The incident-light coefficients a DiffusePRTIntegrator render of `scene` uses (dr_prt_incident), [(lmax + 1)^2, 3] f32."""
         return self.surfaceIntegrator.incident(scene, self.camera.shutterOpen)
+
+    def _probes_desc(self, lmax=4, spacing=1.0, bounds=None, time=0.0, npoints=32768, indirectlighting=False):
+        d = _abi.DrProbesDesc()
+        d.lmax, d.include_indirect, d.npoints, d.has_bounds = int(lmax), 1 if indirectlighting else 0, int(npoints), 0 if bounds is None else 1
+        if bounds is not None:
+            d.bounds[:] = [float(v) for v in np.asarray(bounds, np.float32).reshape(6)]
+        # Point pCamera = camera.cameraToWorld.transformPoint(camera.shutterOpen, Point.ZERO) (:92-93): the translation column, a Point's f32
+        d.camera_pos[:] = [float(np.float32(self.camera.cameraToWorld.reshape(4, 4)[k, 3])) for k in range(3)]
+        d.spacing, d.time = float(spacing), float(time)
+        return d
+
+    def probes_surface_points(self, scene, npoints=32768, time=0.0):
+        """Stage 1 of the bake (dr_probes_surface_points): the surface points the random walks from the camera deposit, [n, 3] f32."""
+        d = self._probes_desc(npoints=npoints, time=time)
+        out, n = np.zeros((int(npoints) + 32, 3), np.float32), C.c_int32(0)
+        _abi.check(_abi.lib().dr_probes_surface_points(scene._device().handle, d.camera_pos, d.time, d.npoints, out.ctypes.data, C.byref(n)))
+        return out[:n.value].copy()
+
+    def probes_grid(self, scene, spacing=1.0, bounds=None):
+        """(nProbes (3 ints), bounds [6] f32) of a bake with these parameters (dr_probes_grid)."""
+        d, n, b = self._probes_desc(spacing=spacing, bounds=bounds), (C.c_int32 * 3)(), (C.c_float * 6)()
+        _abi.check(_abi.lib().dr_probes_grid(scene._device().handle, C.byref(d), n, b))
+        return tuple(n), np.array(b, np.float32)
+
+    def probes_candidates(self, scene, points, spacing=1.0, bounds=None, time=0.0):
+        """Stage 2 of the bake (dr_probes_candidates): (nFound [cells], accepted [cells, 32], -1 behind the last) for the given surface points."""
+        d = self._probes_desc(spacing=spacing, bounds=bounds, time=time)
+        n, _ = self.probes_grid(scene, spacing, bounds)
+        cells = n[0] * n[1] * n[2]
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        nfound, acc = np.zeros(cells, np.int32), np.zeros((cells, 32), np.int32)
+        _abi.check(_abi.lib().dr_probes_candidates(scene._device().handle, C.byref(d), pts.ctypes.data, len(pts), nfound.ctypes.data, acc.ctypes.data))
+        return nfound, acc
+
+    def create_probes(self, scene, lmax=4, spacing=1.0, bounds=None, time=0.0, npoints=32768, indirectlighting=False):
+        """CreateProbesRenderer.render (renderers/create_probes_renderer.dart:51-168) on the device (dr_probes_bake): shadowed direct light
+        projected onto (lmax + 1)^2 spherical harmonics at up to 32 visible points per cell of a grid over `bounds` (default: the scene's world
+        bound), as a ProbeGrid.  indirectlighting defaults to FALSE here -- the reference's default is true -- because that half, a full render
+        per probe direction, is not served: asking for it is refused by name."""
+        d = self._probes_desc(lmax, spacing, bounds, time, npoints, indirectlighting)
+        n, _ = self.probes_grid(scene, spacing, bounds)
+        out = np.zeros(15 + n[0] * n[1] * n[2] * (int(lmax) + 1) ** 2 * 3, np.float32)
+        _abi.check(_abi.lib().dr_probes_bake(scene._device().handle, C.byref(d), out.ctypes.data, len(out)))
+        return ProbeGrid(out)
 
     def prt_bsdf_matrix(self, scene, nsamples_b=1024):
         """The BSDF matrix a GlossyPRTIntegrator render of `scene` uses (dr_prt_bsdf_matrix), [(lmax + 1)^2, (lmax + 1)^2, 3] f32."""

@@ -250,6 +250,12 @@ int traceGridFor(int wgPerCU) {
   return g_numCU * std::max(1, std::min(wgPerCU, 8));
 }
 
+namespace dr_host {
+// (dr_probes.hip traces rays of its own through launch_intersect: the grid that sizes the spill stacks, and the stacks)
+int traceGridMax() { return traceGrid(); }
+int ensureTraceSpill(DrScene* sc) { return ensureSpill(sc, sc->ws, traceGrid()); }
+}  // namespace dr_host
+
 extern "C" {
 
 const char* dr_last_error(void) { return g_err.c_str(); }
@@ -582,6 +588,20 @@ int planRender(RenderPlan& P) {
       P.nStages = P.gprt.perRound + 1;
       break;
     }
+    case IntegratorKind::UseProbes: {
+      // UseProbesIntegrator (use_probes_integrator.dart:90-162): the camera hit and the scene's probe grid, one stage, nothing traced
+      // behind it.  rho2 of anything but a Lambertian matte has no device function outside the kernels that own it: refused by name, as under diffuse PRT
+      if (sc->probes.lmax == 0) return fail(DR_ERR_INVALID, "use probes: no probe grid is set on the scene (dr_scene_set_probes)");
+      if (sc->probes.includeDirect == 0)
+        return fail(DR_ERR_UNSUPPORTED, "use probes: a grid with includeDirect 0 is not supported (that path adds UniformSampleAllLights at every hit); bake with directlighting true");
+      static const char* const names[] = {"matte with sigma != 0 (Oren-Nayar)", "matte", "mirror", "glass", "plastic"};
+      for (size_t i = 0; i < sc->prtMaterials.size(); ++i)
+        if (sc->prtMaterials[i] != DR_MATERIAL_MATTE)
+          return fail(DR_ERR_UNSUPPORTED, std::string("use probes: material ") + names[std::min(3, std::max(-1, sc->prtMaterials[i])) + 1] + " (material " +
+                                              std::to_string(i) + " of the scene) is not supported: only matte with sigma 0 is");
+      P.nStages = 1;
+      break;
+    }
   }
   rp.dlSpecular = P.dlSpec ? 1 : 0;
   rp.deferredNee = P.integ->pathStages ? 1 : 0;
@@ -894,6 +914,7 @@ int32_t lastInfoWord(const RenderPlan& P) {
     case IntegratorKind::Feature: return DR_INTEGRATOR_FEATURE | 0x800 | (P.feature.channel << 12);  // bit 11: k_shade_feature; bits 12-14: its channel
     case IntegratorKind::DiffusePRT: return DR_INTEGRATOR_DIFFUSE_PRT | 0x8000;  // bit 15: k_shade_prt
     case IntegratorKind::GlossyPRT: return DR_INTEGRATOR_GLOSSY_PRT | 0x10000;  // bit 16: k_shade_gprt + k_gprt_finish
+    case IntegratorKind::UseProbes: return DR_INTEGRATOR_USE_PROBES | 0x20000;  // bit 17: k_shade_probes
   }
   return -1;
 }

@@ -269,6 +269,12 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
       shadowRaysOnly = true;
       break;
     }
+    case IntegratorKind::UseProbes: {  // (the only stage: nothing is traced behind it)
+      const auto& g = sc->probes;
+      const ProbeArgs a = {g.lmax, {g.n[0], g.n[1], g.n[2]}, {g.b[0], g.b[1], g.b[2]}, {g.b[3], g.b[4], g.b[5]}, g.cin.p, g.K.p};
+      L.shade_probes(sc->d, stS, q, a, P.sgrid, s);
+      break;
+    }
   }
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {

@@ -17,6 +17,7 @@
 #include "dr_kernels.h"
 #include "dr_prt.h"
 #include "dr_gprt.h"
+#include "dr_probes.h"
 
 namespace dr_host {
 
@@ -187,6 +188,14 @@ struct DrScene {
     float keyKd[3] = {0.f, 0.f, 0.f}, keyKs[3] = {0.f, 0.f, 0.f};
     double keyRoughness = 0.0;
   } gprt;
+  // radiance probes: the grid dr_scene_set_probes attached -- lmax (0: none), includeDirectInProbes, nProbes, the bounds, the
+  // coefficients c_in[cell][Terms(lmax)][3] and the K table on the device -- which a DR_INTEGRATOR_USE_PROBES render reads
+  struct {
+    DevBuf<double> K;
+    DevBuf<float> cin;
+    int lmax = 0, includeDirect = 0, n[3] = {0, 0, 0};
+    float b[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  } probes;
   bool hasSpecular = false;  // some material is a mirror / glass
   bool hasDeltaLight = false;
   // DirectLighting sample layout (direct_lighting_integrator.dart:70-87), fixed by the lights' nsamples
@@ -277,7 +286,7 @@ struct SampleForm {
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
   X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
-  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(shade_gprt, launch_shade_gprt) X(gprt_finish, launch_gprt_finish) X(film, launch_film)
+  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(shade_gprt, launch_shade_gprt) X(gprt_finish, launch_gprt_finish) X(shade_probes, launch_shade_probes) X(film, launch_film)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -308,7 +317,7 @@ constexpr SamplerTraits kSamplerTraits[] = {
 // dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
 // source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
 // (no kind 6: the ABI leaves that value unassigned -- see DR_INTEGRATOR_DIFFUSE_PRT in dartray_hip.h -- and knownIntegrator refuses it like any other unknown value)
-enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7, GlossyPRT = 9 };
+enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7, GlossyPRT = 9, UseProbes = 11 };
 struct IntegratorTraits {
   bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
   int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
@@ -342,12 +351,16 @@ constexpr IntegratorTraits kIntegratorTraits[] = {
     // GlossyPRT (glossy_prt_integrator.dart:53-116): an empty requestSamples -- tau + scatter only; DiffusePRT's stages and rounds,
     // then one finish launch per batch; max_depth is not read
     {false, 2, 0, false, false, nullptr,
-     "glossy PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"}};
+     "glossy PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"},
+    {true, 0, 0, false, false, nullptr, nullptr},  // (10: unassigned like 6 and 8 -- what the library answers for it is pinned by tests/test_glossy_prt_integrator.py)
+    // UseProbes (use_probes_integrator.dart:74-88): requestSamples asks for the scene's DirectLighting "all" slots although Li never
+    // reads them (the grid includes the direct light); one stage, no ray beyond the camera's; max_depth is not read
+    {true, 0, 0, false, false, nullptr, "use probes: the adaptive sampler is not supported (its second pass has no test under this integrator; every other sampler mode is)"}};
 static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
                   (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
                   (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && (int)IntegratorKind::Feature == DR_INTEGRATOR_FEATURE &&
                   (int)IntegratorKind::DiffusePRT == DR_INTEGRATOR_DIFFUSE_PRT && (int)IntegratorKind::GlossyPRT == DR_INTEGRATOR_GLOSSY_PRT &&
-                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 10, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
+                  (int)IntegratorKind::UseProbes == DR_INTEGRATOR_USE_PROBES && sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 12, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
 // The one value inside the table's range that names no integrator: its row is a placeholder.  An integrator added later takes the value behind the
 // last one, not this one -- what the library answers for it is pinned behaviour (tests/test_feature_integrator.py)
 constexpr int32_t kUnassignedIntegrator = 6;
@@ -359,8 +372,14 @@ constexpr int32_t kUnassignedIntegrator2 = 8;
 static_assert(DR_INTEGRATOR_DIFFUSE_PRT < kUnassignedIntegrator2 && kUnassignedIntegrator2 < DR_INTEGRATOR_GLOSSY_PRT &&
                   kIntegratorTraits[kUnassignedIntegrator2].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator2].adaptive,
               "the second unassigned value lies between the diffuse and the glossy PRT integrator and its row is the placeholder");
+// ... and the third, between the glossy PRT and the probe integrator (tests/test_glossy_prt_integrator.py pins dr_sample_floats(10, 3))
+constexpr int32_t kUnassignedIntegrator3 = 10;
+static_assert(DR_INTEGRATOR_GLOSSY_PRT < kUnassignedIntegrator3 && kUnassignedIntegrator3 < DR_INTEGRATOR_USE_PROBES &&
+                  kIntegratorTraits[kUnassignedIntegrator3].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator3].adaptive,
+              "the third unassigned value lies between the glossy PRT and the probe integrator and its row is the placeholder");
 inline bool knownIntegrator(int32_t v) {
-  return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && v != kUnassignedIntegrator && v != kUnassignedIntegrator2;
+  return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && v != kUnassignedIntegrator && v != kUnassignedIntegrator2 &&
+         v != kUnassignedIntegrator3;
 }
 
 // The feature integrator's refusals (dr_feature_check, planRender): null, or the text and its code

@@ -265,6 +265,12 @@ typedef struct DrFilm {
  * prt_nsamples is rounded up to a power of two; below 1 or above 4096, prt_lmax below 1 or above 4 are DR_ERR_INVALID; DR_SAMPLER_ADAPTIVE is
  * DR_ERR_UNSUPPORTED, by name.  It reads no material function, so no material is refused. */
 #define DR_INTEGRATOR_GLOSSY_PRT 9 /* (8, like 6, stays unassigned and is answered as every unknown value is) */
+/* UseProbesIntegrator (use_probes_integrator.dart:23-185): Li = Le + rho * INV_PI * clamp(E(n)), E the irradiance
+ * function of the scene's radiance-probe grid (dr_scene_set_probes) interpolated trilinearly at the hit and convolved with the clamped cosine.
+ * One shading launch (k_shade_probes) behind the camera rays, no further ray.  Its sample slots are the scene's DirectLighting "all" slots
+ * (requestSamples asks for them; Li does not read them).  No grid on the scene: DR_ERR_INVALID; a grid with includeDirect 0, a material other
+ * than matte with sigma 0, DR_SAMPLER_ADAPTIVE: DR_ERR_UNSUPPORTED, by name.  max_depth is not read. */
+#define DR_INTEGRATOR_USE_PROBES 11 /* (10, like 6 and 8, stays unassigned) */
 /* DrRenderDesc.feature_channel: R, G, B at a hit.  Every value is >= 0 (the renderer blacks out a sample of negative luminance). */
 #define DR_FEATURE_NG 0    /* 0.5 * (isect.dg.nn + 1): the geometric normal, world space, reverseOrientation applied */
 #define DR_FEATURE_NS 1    /* 0.5 * (bsdf.dgShading.nn + 1): Triangle.getShadingGeometry (per-vertex N / S); else the geometric one */
@@ -574,6 +580,35 @@ int dr_sh_rotate(const float* c_in, const float* m16, int32_t lmax, float* out);
 int dr_sh_bsdf_matrix_host(const float* Kd, const float* Ks, double roughness, const uint32_t* scramble, int32_t nsamples_b, int32_t lmax, float* out);
 int dr_sh_rotate_device(const float* c_in, const float* m16, int32_t lmax, int32_t nframes, float* out);
 
+/* Radiance probes: CreateProbesRenderer's bake of shadowed direct light onto a 3-D grid of spherical-harmonic probes
+ * (renderers/create_probes_renderer.dart), on the device, in stages that can each be called alone. */
+typedef struct DrProbesDesc {
+  int32_t lmax;             /* 1 .. 8 (reference default 4) */
+  int32_t include_indirect; /* must be 0: `indirectlighting` (a full render per probe) is refused by name.  The reference's default is true */
+  int32_t npoints;          /* surface points of the visibility test; the reference's constant is 32768 */
+  int32_t has_bounds;       /* 0: `bounds` is scene.worldBound */
+  float bounds[6];          /* x0 y0 z0 x1 y1 z1 */
+  float camera_pos[3];      /* camera.cameraToWorld(shutterOpen, Point.ZERO): where the random walks start */
+  float pad;
+  double spacing;           /* samplespacing (reference default 1.0) */
+  double time;              /* (reference default 0.0; no shape of the device path moves) */
+} DrProbesDesc;
+/* Stage 1 (:78-121): the points the random walks from camera_pos deposit -- the camera position, then per walk up to 32 closest hits against the
+ * scene or, where it misses, the bounding sphere of its world bound -- on one RNG(5489) stream.  out: room for npoints + 31 points (the
+ * inner loop does not re-check the length); *count_out: how many were written. */
+int dr_probes_surface_points(DrScene* scene, const float camera_pos[3], double time, int32_t npoints, float* out, int32_t* count_out);
+/* nProbes[i] = max(1, ceil(delta[i] / spacing)) and the bounds the desc means (lmax and npoints are not read). */
+int dr_probes_grid(const DrScene* scene, const DrProbesDesc* desc, int32_t nprobes_out[3], float bounds_out[6]);
+/* Stage 2 (:254-309): per cell the first 32 of its 256 candidates, in index order, that some of the given points sees:
+ * nfound_out[cells], accepted_out[cells][32] (candidate indices, -1 behind the last).  desc: bounds and spacing. */
+int dr_probes_candidates(DrScene* scene, const DrProbesDesc* desc, const float* points, int32_t npoints, int32_t* nfound_out, int32_t* accepted_out);
+/* Stages 1 to 3: the reference's Float32List -- lmax, includeDirect (1), includeIndirect (0), nProbes[3], the six bounds, the coefficients
+ * [cell][(lmax + 1)^2][3], three zeros -- into out[nfloats], nfloats = 15 + cells * (lmax + 1)^2 * 3 exactly (dr_probes_grid gives the cells). */
+int dr_probes_bake(DrScene* scene, const DrProbesDesc* desc, float* out, int64_t nfloats);
+/* Attaches a probe grid in that form to the scene for DR_INTEGRATOR_USE_PROBES renders (a copy is kept on the device); data NULL detaches it.
+ * The header is checked against n: lmax in 1 .. 8, nProbes whole numbers in 1 .. 4096, n = 15 + cells * (lmax + 1)^2 * 3, else DR_ERR_INVALID. */
+int dr_scene_set_probes(DrScene* scene, const float* data, int64_t n);
+
 /* Renderer.render(Scene) (lib/core/renderer.dart:28;
  * sampler_renderer.dart:36-65): traces this task's window and returns the
  * film.  film_out: [height*width*4] f32 (X, Y, Z, weightSum) -- ImageFilm's
@@ -689,7 +724,10 @@ const char* dr_version(void);
  * parameters are union members at the offsets of ao_nsamples (prt_nsamples) and feature_channel (prt_lmax) -- storage that is read under one
  * integrator's constant only -- and two new entry points, dr_prt_incident and dr_sh_evaluate: no field moved, 1352 bytes; and
  * DR_INTEGRATOR_GLOSSY_PRT: a new constant that reads the same two union members, one new struct, DrGlossyPrtParams, that only its new entry point
- * dr_scene_set_glossy_prt reads, and four more new entry points: dr_prt_bsdf_matrix, dr_sh_rotate, dr_sh_bsdf_matrix_host, dr_sh_rotate_device). */
+ * dr_scene_set_glossy_prt reads, and four more new entry points: dr_prt_bsdf_matrix, dr_sh_rotate, dr_sh_bsdf_matrix_host, dr_sh_rotate_device; and
+ * DR_INTEGRATOR_USE_PROBES: a new constant that reads no field of DrRenderDesc beyond the common ones, one new struct, DrProbesDesc, that only
+ * the new entry points read -- dr_probes_surface_points, dr_probes_grid, dr_probes_candidates, dr_probes_bake -- and dr_scene_set_probes: nothing
+ * existing moved or changed its meaning, so the version stays 9). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 

@@ -185,6 +185,12 @@ const int DR_INTEGRATOR_DIFFUSE_PRT = 7;  // DiffusePRTIntegrator (6 is unassign
 const int DR_INTEGRATOR_GLOSSY_PRT = 9;  // GlossyPRTIntegrator (8 is unassigned): the same two fields; Kd, Ks, roughness by dr_scene_set_glossy_prt
 // DrGlossyPrtParams: f32 Kd[3] at 0, f32 Ks[3] at 12, f64 roughness at 24
 const int SIZEOF_DrGlossyPrtParams = 32, OFF_DrGlossyPrtParams_Kd = 0, OFF_DrGlossyPrtParams_Ks = 12, OFF_DrGlossyPrtParams_roughness = 24;
+const int DR_INTEGRATOR_USE_PROBES = 11;  // UseProbesIntegrator (10 is unassigned): the grid by dr_scene_set_probes; no field of its own
+// DrProbesDesc: i32 lmax at 0, include_indirect (must be 0) at 4, npoints at 8, has_bounds at 12, f32 bounds[6] at 16, f32 camera_pos[3] at 40,
+// f64 spacing at 56, f64 time at 64
+const int SIZEOF_DrProbesDesc = 72, OFF_DrProbesDesc_lmax = 0, OFF_DrProbesDesc_include_indirect = 4, OFF_DrProbesDesc_npoints = 8,
+    OFF_DrProbesDesc_has_bounds = 12, OFF_DrProbesDesc_bounds = 16, OFF_DrProbesDesc_camera_pos = 40, OFF_DrProbesDesc_spacing = 56,
+    OFF_DrProbesDesc_time = 64;
 const int DR_FEATURE_NG = 0, DR_FEATURE_NS = 1, DR_FEATURE_DEPTH = 2, DR_FEATURE_UV = 3, DR_FEATURE_ID = 4;
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
@@ -216,6 +222,18 @@ typedef _SetOptionC = Int32 Function(Pointer<Utf8>, Pointer<Utf8>);
 typedef _SetOptionD = int Function(Pointer<Utf8>, Pointer<Utf8>);
 typedef _SetGlossyPrtC = Int32 Function(Pointer<Void>, Pointer<Uint8>);  // (scene, DrGlossyPrtParams*)
 typedef _SetGlossyPrtD = int Function(Pointer<Void>, Pointer<Uint8>);
+// radiance probes (DESIGN.md 2.18): (scene, data, n); (scene, DrProbesDesc*, out, nfloats); (scene, DrProbesDesc*, nprobes[3], bounds[6]);
+// (scene, camera_pos[3], time, npoints, out, count*); (scene, DrProbesDesc*, points, npoints, nfound*, accepted*)
+typedef _SetProbesC = Int32 Function(Pointer<Void>, Pointer<Float>, Int64);
+typedef _SetProbesD = int Function(Pointer<Void>, Pointer<Float>, int);
+typedef _ProbesBakeC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Pointer<Float>, Int64);
+typedef _ProbesBakeD = int Function(Pointer<Void>, Pointer<Uint8>, Pointer<Float>, int);
+typedef _ProbesGridC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Pointer<Int32>, Pointer<Float>);
+typedef _ProbesGridD = int Function(Pointer<Void>, Pointer<Uint8>, Pointer<Int32>, Pointer<Float>);
+typedef _ProbesPointsC = Int32 Function(Pointer<Void>, Pointer<Float>, Double, Int32, Pointer<Float>, Pointer<Int32>);
+typedef _ProbesPointsD = int Function(Pointer<Void>, Pointer<Float>, double, int, Pointer<Float>, Pointer<Int32>);
+typedef _ProbesCandidatesC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Pointer<Float>, Int32, Pointer<Int32>, Pointer<Int32>);
+typedef _ProbesCandidatesD = int Function(Pointer<Void>, Pointer<Uint8>, Pointer<Float>, int, Pointer<Int32>, Pointer<Int32>);
 typedef _SetLayoutC = Int32 Function(Pointer<Void>, Int32);
 typedef _SetLayoutD = int Function(Pointer<Void>, int);
 typedef _CommVoidD = int Function();
@@ -328,6 +346,11 @@ class HipSamplerRenderer extends Renderer {
   static final _CommVoidD _commAvailable = _lib.lookupFunction<_CommVoidC, _CommVoidD>('dr_comm_available');
   static final _SetOptionD _setOption = _lib.lookupFunction<_SetOptionC, _SetOptionD>('dr_set_option');
   static final _SetGlossyPrtD _setGlossyPrt = _lib.lookupFunction<_SetGlossyPrtC, _SetGlossyPrtD>('dr_scene_set_glossy_prt');
+  static final _SetProbesD setProbes = _lib.lookupFunction<_SetProbesC, _SetProbesD>('dr_scene_set_probes');
+  static final _ProbesBakeD probesBake = _lib.lookupFunction<_ProbesBakeC, _ProbesBakeD>('dr_probes_bake');
+  static final _ProbesGridD probesGrid = _lib.lookupFunction<_ProbesGridC, _ProbesGridD>('dr_probes_grid');
+  static final _ProbesPointsD probesSurfacePoints = _lib.lookupFunction<_ProbesPointsC, _ProbesPointsD>('dr_probes_surface_points');
+  static final _ProbesCandidatesD probesCandidates = _lib.lookupFunction<_ProbesCandidatesC, _ProbesCandidatesD>('dr_probes_candidates');
   static final _SetLayoutD _setStateLayout = _lib.lookupFunction<_SetLayoutC, _SetLayoutD>('dr_scene_set_state_layout');
   static final _GetLayoutD _getStateLayout = _lib.lookupFunction<_GetLayoutC, _GetLayoutD>('dr_scene_get_state_layout');
   static final _KernelsD _getTraceKernels = _lib.lookupFunction<_KernelsC, _KernelsD>('dr_scene_get_trace_kernels');
