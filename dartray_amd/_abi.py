@@ -180,6 +180,10 @@ class DrDenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float)]
 
 
+class DrDenoisePairParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float), ("var_floor", C.c_float)]
+
+
 DR_COMM_ID_BYTES = 128
 DR_ABI_VERSION = 9  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
 
@@ -201,6 +205,12 @@ EXPORTS = {
     "dr_denoise_atrous": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p]),
     "dr_denoise_atrous_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p,
                                            C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "dr_denoise_pair_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoisePairParams),
+                                       C.c_void_p, C.c_void_p]),
+    "dr_denoise_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoisePairParams),
+                                  C.c_void_p, C.c_void_p]),
+    "dr_denoise_pair_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoisePairParams),
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "dr_scene_create": (C.c_int, [C.POINTER(DrSceneDesc), C.POINTER(C.c_void_p)]),
     "dr_scene_destroy": (None, [C.c_void_p]),
     "dr_scene_get_trace_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 2)]),

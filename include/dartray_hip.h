@@ -480,6 +480,36 @@ int dr_denoise_atrous(const float* rgb, const float* normal, const float* depth,
 int dr_denoise_atrous_device(const void* rgb_dev, const void* normal_dev, const void* depth_dev, int32_t w, int32_t h,
                              const DrDenoiseParams* params, void* out_dev, void* scratch_dev, uint64_t* scratch_bytes, void* hip_stream);
 
+/* The variance-guided a-trous denoiser over two half-sample renders: a[h][w][3] and b[h][w][3] are two renders of
+ * one scene that differ in the sampler's seed alone, normal and depth the guides above.  Their mean 0.5 * (a + b) is the image that is
+ * filtered, and 0.25 * lum(a - b)^2 the first estimate of its luminance variance, which every level carries on (sum of wt^2 * v over
+ * (sum of wt)^2) and, smoothed over 3 x 3 pixels, uses as the unit of its colour term: a tap's weight is divided by
+ * (1 + k_color * (lum(q) - lum(p))^2 / (variance + var_floor)), with the same k_color at every level, and by the normal and depth terms
+ * above.  out[h][w][3]: the filtered mean; out_var[h][w], which may be NULL: its variance, -1 where the pixel is not valid -- a pixel whose
+ * mean, first variance, normal or depth is not finite, which is copied through (the mean) and is no tap of any other pixel.  f32
+ * arithmetic, one rounding per operator: the three entry points below write the same bytes. */
+typedef struct DrDenoisePairParams {
+  int32_t iterations; /* 1 .. 8 */
+  float k_color;      /* finite, >= 0; 0: the term is off.  1 / sigma^2, sigma in standard deviations of the local noise */
+  float k_normal;     /* as in DrDenoiseParams */
+  float k_depth;
+  float var_floor;    /* finite, > 0: added to the smoothed variance, in squared units of radiance */
+} DrDenoisePairParams; /* 20 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer (out_var excepted), w or h < 1, w * h >= 2^31, iterations outside 1 .. 8, a k that is
+ * negative or not finite, a var_floor that is not finite or not positive, `out` or `out_var` overlapping an input, each other (or the
+ * scratch buffer).
+ * dr_denoise_pair_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_denoise_pair_host(const float* a, const float* b, const float* normal, const float* depth, int32_t w, int32_t h,
+                         const DrDenoisePairParams* params, float* out, float* out_var);
+/* The same ON THE GPU (dr_denoise_pair_device.hip), host buffers: uploads, filters, copies back.  Needs dr_init. */
+int dr_denoise_pair(const float* a, const float* b, const float* normal, const float* depth, int32_t w, int32_t h,
+                    const DrDenoisePairParams* params, float* out, float* out_var);
+/* The same on device buffers, asynchronous on the given hipStream_t; the scratch buffer and its size query as for
+ * dr_denoise_atrous_device (the same size). */
+int dr_denoise_pair_device(const void* a_dev, const void* b_dev, const void* normal_dev, const void* depth_dev, int32_t w, int32_t h,
+                           const DrDenoisePairParams* params, void* out_dev, void* out_var_dev, void* scratch_dev, uint64_t* scratch_bytes,
+                           void* hip_stream);
+
 /* Scene upload (replaces the construction of lib/core/scene.dart Scene). */
 int dr_scene_create(const DrSceneDesc* desc, DrScene** out);
 void dr_scene_destroy(DrScene* scene);
@@ -727,7 +757,8 @@ const char* dr_version(void);
  * dr_scene_set_glossy_prt reads, and four more new entry points: dr_prt_bsdf_matrix, dr_sh_rotate, dr_sh_bsdf_matrix_host, dr_sh_rotate_device; and
  * DR_INTEGRATOR_USE_PROBES: a new constant that reads no field of DrRenderDesc beyond the common ones, one new struct, DrProbesDesc, that only
  * the new entry points read -- dr_probes_surface_points, dr_probes_grid, dr_probes_candidates, dr_probes_bake -- and dr_scene_set_probes: nothing
- * existing moved or changed its meaning, so the version stays 9). */
+ * existing moved or changed its meaning, so the version stays 9; and the pair denoiser: one new struct, DrDenoisePairParams, that only its
+ * three new entry points read -- dr_denoise_pair_host, dr_denoise_pair and dr_denoise_pair_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -846,6 +877,10 @@ DR_ABI_SIZE(DrDenoiseParams, 16);
 DR_ABI_OFFSET(DrDenoiseParams, k_color, 4);
 DR_ABI_OFFSET(DrDenoiseParams, k_normal, 8);
 DR_ABI_OFFSET(DrDenoiseParams, k_depth, 12);
+DR_ABI_SIZE(DrDenoisePairParams, 20);
+DR_ABI_OFFSET(DrDenoisePairParams, k_color, 4);
+DR_ABI_OFFSET(DrDenoisePairParams, k_depth, 12);
+DR_ABI_OFFSET(DrDenoisePairParams, var_floor, 16);
 
 #ifdef __cplusplus
 }

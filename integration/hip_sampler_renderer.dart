@@ -170,6 +170,14 @@ const int OFF_DrDenoiseParams_iterations = 0;
 const int OFF_DrDenoiseParams_k_color = 4;
 const int OFF_DrDenoiseParams_k_normal = 8;
 const int OFF_DrDenoiseParams_k_depth = 12;
+// DrDenoisePairParams (the variance-guided a-trous denoiser over two half renders, DESIGN.md 2.19): int32 iterations (1 .. 8) at 0, the three
+// f32 sharpness values -- k_color in units of the local variance -- and the f32 variance floor (> 0)
+const int SIZEOF_DrDenoisePairParams = 20;
+const int OFF_DrDenoisePairParams_iterations = 0;
+const int OFF_DrDenoisePairParams_k_color = 4;
+const int OFF_DrDenoisePairParams_k_normal = 8;
+const int OFF_DrDenoisePairParams_k_depth = 12;
+const int OFF_DrDenoisePairParams_var_floor = 16;
 
 // enums of the header
 const int DR_MATERIAL_MATTE = 0, DR_MATERIAL_MIRROR = 1, DR_MATERIAL_GLASS = 2, DR_MATERIAL_PLASTIC = 3;
@@ -258,6 +266,13 @@ typedef _LoopSubdivideD = int Function(Pointer<Uint32>, int, Pointer<Float>, int
 // w, h, DrDenoiseParams (16 bytes, the OFF_DrDenoiseParams_* offsets above), out[h][w][3].  (Signature only, never compiled, like the rest.)
 typedef _DenoiseAtrousC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>);
 typedef _DenoiseAtrousD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>);
+// dr_denoise_pair (the variance-guided filter on the GPU, host buffers; DESIGN.md 2.19): a[h][w][3], b[h][w][3] -- two renders that differ in the
+// sampler's seed alone --, normal[h][w][3], depth[h][w], w, h, DrDenoisePairParams (20 bytes, the OFF_DrDenoisePairParams_* offsets above),
+// out[h][w][3], out_var[h][w] or null.  (Signature only, never compiled, like the rest.)
+typedef _DenoisePairC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>,
+    Pointer<Float>);
+typedef _DenoisePairD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>,
+    Pointer<Float>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -320,6 +335,8 @@ class HipSamplerRenderer extends Renderer {
   static final _LoopSubdivideD loopSubdivideDevice = _lib.lookupFunction<_LoopSubdivideC, _LoopSubdivideD>('dr_loop_subdivide_device');
   /// The a-trous denoiser over a finished image and its FeatureIntegrator normal and depth images (after dr_init).
   static final _DenoiseAtrousD denoiseAtrous = _lib.lookupFunction<_DenoiseAtrousC, _DenoiseAtrousD>('dr_denoise_atrous');
+  /// The same over two half-sample renders, whose difference estimates the variance that guides the colour term (after dr_init).
+  static final _DenoisePairD denoisePair = _lib.lookupFunction<_DenoisePairC, _DenoisePairD>('dr_denoise_pair');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
   /// library of another layout version is refused before any struct crosses the boundary.
   static const int ABI_VERSION = 9;
