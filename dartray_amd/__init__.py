@@ -8,3 +8,4 @@ scenes; dist.py shards image tiles over ranks and reduces the film over RCCL.
 from . import _abi  # noqa: F401
 from .core import *  # noqa: F401,F403
 from . import denoise  # noqa: F401,E402
+from . import display  # noqa: F401,E402

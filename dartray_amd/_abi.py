@@ -21,6 +21,9 @@ DR_INTEGRATOR_DIFFUSE_PRT = 7  # (6 stays unassigned) prt_nsamples / prt_lmax; m
 DR_INTEGRATOR_GLOSSY_PRT = 9  # (8 stays unassigned) prt_nsamples / prt_lmax; Kd, Ks, roughness by dr_scene_set_glossy_prt; max_depth is not read
 DR_INTEGRATOR_USE_PROBES = 11  # (10 stays unassigned) the grid by dr_scene_set_probes; the scene's DirectLighting "all" slots; max_depth is not read
 DR_FEATURE_NG, DR_FEATURE_NS, DR_FEATURE_DEPTH, DR_FEATURE_UV, DR_FEATURE_ID = 0, 1, 2, 3, 4
+DR_TONE_CLAMP, DR_TONE_REINHARD, DR_TONE_FILMIC = 0, 1, 2
+DR_ENCODE_SRGB, DR_ENCODE_GAMMA22, DR_ENCODE_REFERENCE = 0, 1, 2
+DR_DISPLAY_BINS = 2048
 DR_SAMPLER_HOST_BUFFER = 0
 DR_SAMPLER_COUNTER = 1
 DR_SAMPLER_STRATIFIED = 2
@@ -184,6 +187,11 @@ class DrDenoisePairParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float), ("var_floor", C.c_float)]
 
 
+class DrDisplayParams(C.Structure):
+    _fields_ = [("curve", C.c_uint32), ("encode", C.c_uint32), ("auto_exposure", C.c_uint32), ("permille", C.c_uint32), ("exposure", C.c_float),
+                ("key", C.c_float), ("inv_white2", C.c_float), ("invalid_rgba", C.c_uint32)]
+
+
 DR_COMM_ID_BYTES = 128
 DR_ABI_VERSION = 9  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
 
@@ -211,6 +219,14 @@ EXPORTS = {
                                   C.c_void_p, C.c_void_p]),
     "dr_denoise_pair_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoisePairParams),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "dr_display_check": (C.c_int, [C.POINTER(DrDisplayParams), C.c_int32, C.c_int32]),
+    "dr_display_table": (C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32]),
+    "dr_display_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p]),
+    "dr_display": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p]),
+    "dr_display_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64),
+                                    C.c_void_p]),
+    "dr_display_exposure_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p, C.c_void_p]),
+    "dr_display_exposure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p, C.c_void_p]),
     "dr_scene_create": (C.c_int, [C.POINTER(DrSceneDesc), C.POINTER(C.c_void_p)]),
     "dr_scene_destroy": (None, [C.c_void_p]),
     "dr_scene_get_trace_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 2)]),

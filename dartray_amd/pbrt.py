@@ -1035,7 +1035,11 @@ def _write_pfm(path, rgb):
 
 
 def main(argv=None):
-    """python -m dartray_amd.pbrt scene.pbrt [-o out.pfm|out.npy] [--spp N] [--xres W --yres H]"""
+    """python -m dartray_amd.pbrt scene.pbrt [-o out.pfm|out.npy|out.png|out.ppm] [--spp N] [--xres W --yres H]
+    [--exposure auto|SCALE] [--tonemap clamp|reinhard|filmic] [--encode srgb|gamma22|reference]
+
+    .png and .ppm go through the display transform (dartray_amd/display.py), which the three last flags choose; .npy and
+    every other suffix hold the linear f32 radiance."""
     import argparse
     import time
     ap = argparse.ArgumentParser(description="Render a PBRT-v2 scene file on the MI355X path")
@@ -1044,7 +1048,16 @@ def main(argv=None):
     ap.add_argument("--spp", type=int)
     ap.add_argument("--xres", type=int)
     ap.add_argument("--yres", type=int)
+    ap.add_argument("--exposure", default="auto", help=".png / .ppm: auto (the median luminance goes to 0.18), or the scale as a number")
+    ap.add_argument("--tonemap", default="reinhard", choices=["clamp", "reinhard", "filmic"])
+    ap.add_argument("--encode", default="srgb", choices=["srgb", "gamma22", "reference"])
     a = ap.parse_args(argv)
+    displayed = bool(a.output) and a.output.endswith((".png", ".ppm"))
+    if displayed and a.exposure != "auto":
+        try:
+            float(a.exposure)
+        except ValueError:
+            ap.error("--exposure must be auto or a number (got %r)" % (a.exposure,))
     ov = {k: v for k, v in (("pixelsamples", a.spp), ("xresolution", a.xres), ("yresolution", a.yres)) if v}
     t0 = time.time()
     api = load(a.scene, render=False, overrides=ov, warn=lambda m: print("warning:", m))
@@ -1055,7 +1068,11 @@ def main(argv=None):
     print(f"parsed + built BVH in {t1 - t0:.2f} s; rendered {out.width}x{out.height} in {t2 - t1:.2f} s "
           f"({st['camera_samples'] / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s)")
     if a.output:
-        if a.output.endswith(".npy"):
+        if displayed:
+            from . import display
+            rgba = display.to_image(out, exposure=None if a.exposure == "auto" else float(a.exposure), curve=a.tonemap, encode=a.encode)
+            (display.write_png if a.output.endswith(".png") else display.write_ppm)(a.output, rgba)
+        elif a.output.endswith(".npy"):
             np.save(a.output, out.rgb)
         else:
             _write_pfm(a.output, out.rgb)

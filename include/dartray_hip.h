@@ -510,6 +510,51 @@ int dr_denoise_pair_device(const void* a_dev, const void* b_dev, const void* nor
                            const DrDenoisePairParams* params, void* out_dev, void* out_var_dev, void* scratch_dev, uint64_t* scratch_bytes,
                            void* hip_stream);
 
+/* The display transform: rgb[h][w][3], row-major f32 linear radiance, becomes out[h][w][4], bytes R, G, B, A = 255.
+ * Per pixel: a non-finite channel makes the pixel invalid (it is no sample of the histogram and comes out as invalid_rgba); a negative channel
+ * is taken as 0; the channels are multiplied by the exposure scale, go through the tone curve and are encoded to a byte each.  The scale is
+ * `exposure`, or with auto_exposure != 0 key over the centre of the luminance-histogram bin (2048 bins, eight per octave: the f32's bits
+ * >> 20) in which the pixel of rank (n - 1) * permille / 1000 among the n counted ones lies; 1 when none is counted.  f32 arithmetic, one
+ * rounding per operator, no transcendental per pixel: the entry points below write the same bytes. */
+#define DR_TONE_CLAMP 0u       /* identity */
+#define DR_TONE_REINHARD 1u    /* Yd = (Y * (1 + Y * inv_white2)) / (1 + Y) on the luminance Y; the colour is scaled by Yd / Y */
+#define DR_TONE_FILMIC 2u      /* (x * (2.51 x + 0.03)) / (x * (2.43 x + 0.59) + 0.14) per channel */
+#define DR_ENCODE_SRGB 0u      /* the number of thresholds T[1..255] <= x; T[k] is the linear value that the sRGB curve takes to (k - 0.5) / 255 */
+#define DR_ENCODE_GAMMA22 1u   /* the same with T[k] = ((k - 0.5) / 255)^2.2 */
+#define DR_ENCODE_REFERENCE 2u /* ImageFilm's: G[clamp(floor(f64(x) * 255.0), 0, 255)], G[i] = clamp(floor(pow(i / 255.0, 1.0 / 2.2) * 255.0), 0, 255) */
+#define DR_DISPLAY_BINS 2048u
+typedef struct DrDisplayParams {
+  uint32_t curve;         /* DR_TONE_* */
+  uint32_t encode;        /* DR_ENCODE_* */
+  uint32_t auto_exposure; /* 0: the scale is `exposure`; else it is found from the histogram */
+  uint32_t permille;      /* 0 .. 1000; 500 is the median */
+  float exposure;         /* finite, > 0 */
+  float key;              /* finite, > 0; the value the picked luminance is mapped to (0.18: middle grey) */
+  float inv_white2;       /* finite, >= 0: 1 / white^2 of the extended Reinhard curve; 0 is the plain Y / (1 + Y) */
+  uint32_t invalid_rgba;  /* r | g << 8 | b << 16 | a << 24 of an invalid pixel (0xff000000: opaque black) */
+} DrDisplayParams; /* 32 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer, an unknown curve or encode, permille > 1000, an exposure or key that is not finite or
+ * not positive, an inv_white2 that is negative or not finite, w or h < 1, w * h >= 2^31, `out` overlapping `rgb` (or the scratch buffer).
+ * dr_display_check states them without an image. */
+int dr_display_check(const DrDisplayParams* params, int32_t w, int32_t h);
+/* The 256 words of an encode's table: for DR_ENCODE_SRGB and _GAMMA22 word 0 is 0 and word k the f32 T[k]; for DR_ENCODE_REFERENCE word i
+ * is G[i].  Computed in f64 with the C library's pow; every entry point reads this table.  n, the words `out` has room for, must be 256. */
+int dr_display_table(uint32_t encode, uint32_t* out, uint32_t n);
+/* dr_display_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_display_host(const float* rgb, int32_t w, int32_t h, const DrDisplayParams* params, uint8_t* out);
+/* The same ON THE GPU (dr_display_device.hip), host buffers: uploads, transforms, copies back.  Needs dr_init. */
+int dr_display(const float* rgb, int32_t w, int32_t h, const DrDisplayParams* params, uint8_t* out);
+/* The same on device buffers, asynchronous on the given hipStream_t, with no wait on the host between the histogram and the encode.
+ * scratch_dev == NULL: the size query -- writes the bytes of scratch a call needs to *scratch_bytes and does nothing else (the image pointers
+ * are not read and may be NULL).  Otherwise *scratch_bytes is the size of scratch_dev (too small is DR_ERR_INVALID), which must be 16-byte
+ * aligned and is the call's to overwrite until the stream has run it: the 2048 counts, then the scale. */
+int dr_display_device(const void* rgb_dev, int32_t w, int32_t h, const DrDisplayParams* params, void* out_dev, void* scratch_dev,
+                      uint64_t* scratch_bytes, void* hip_stream);
+/* The scale auto-exposure picks for this image with params' key and permille (auto_exposure itself is not read), to *scale, and the 2048
+ * counts to hist unless it is NULL.  dr_display_exposure_host: no GPU needed; dr_display_exposure: on the GPU, host buffers, needs dr_init. */
+int dr_display_exposure_host(const float* rgb, int32_t w, int32_t h, const DrDisplayParams* params, float* scale, uint32_t* hist);
+int dr_display_exposure(const float* rgb, int32_t w, int32_t h, const DrDisplayParams* params, float* scale, uint32_t* hist);
+
 /* Scene upload (replaces the construction of lib/core/scene.dart Scene). */
 int dr_scene_create(const DrSceneDesc* desc, DrScene** out);
 void dr_scene_destroy(DrScene* scene);
@@ -758,7 +803,9 @@ const char* dr_version(void);
  * DR_INTEGRATOR_USE_PROBES: a new constant that reads no field of DrRenderDesc beyond the common ones, one new struct, DrProbesDesc, that only
  * the new entry points read -- dr_probes_surface_points, dr_probes_grid, dr_probes_candidates, dr_probes_bake -- and dr_scene_set_probes: nothing
  * existing moved or changed its meaning, so the version stays 9; and the pair denoiser: one new struct, DrDenoisePairParams, that only its
- * three new entry points read -- dr_denoise_pair_host, dr_denoise_pair and dr_denoise_pair_device). */
+ * three new entry points read -- dr_denoise_pair_host, dr_denoise_pair and dr_denoise_pair_device; and the display transform: one new struct,
+ * DrDisplayParams, that only its seven new entry points read -- dr_display_check, dr_display_table, dr_display_host, dr_display,
+ * dr_display_device, dr_display_exposure_host and dr_display_exposure). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -881,6 +928,10 @@ DR_ABI_SIZE(DrDenoisePairParams, 20);
 DR_ABI_OFFSET(DrDenoisePairParams, k_color, 4);
 DR_ABI_OFFSET(DrDenoisePairParams, k_depth, 12);
 DR_ABI_OFFSET(DrDenoisePairParams, var_floor, 16);
+DR_ABI_SIZE(DrDisplayParams, 32);
+DR_ABI_OFFSET(DrDisplayParams, permille, 12);
+DR_ABI_OFFSET(DrDisplayParams, exposure, 16);
+DR_ABI_OFFSET(DrDisplayParams, invalid_rgba, 28);
 
 #ifdef __cplusplus
 }

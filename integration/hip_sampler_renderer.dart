@@ -178,6 +178,20 @@ const int OFF_DrDenoisePairParams_k_color = 4;
 const int OFF_DrDenoisePairParams_k_normal = 8;
 const int OFF_DrDenoisePairParams_k_depth = 12;
 const int OFF_DrDenoisePairParams_var_floor = 16;
+// DrDisplayParams (the display transform, DESIGN.md 2.20): four uint32 -- the tone curve, the encode, auto-exposure on / off, the rank in
+// permille --, three f32 -- the manual scale, the key, 1 / white^2 -- and the uint32 r | g << 8 | b << 16 | a << 24 of an invalid pixel
+const int SIZEOF_DrDisplayParams = 32;
+const int OFF_DrDisplayParams_curve = 0;
+const int OFF_DrDisplayParams_encode = 4;
+const int OFF_DrDisplayParams_auto_exposure = 8;
+const int OFF_DrDisplayParams_permille = 12;
+const int OFF_DrDisplayParams_exposure = 16;
+const int OFF_DrDisplayParams_key = 20;
+const int OFF_DrDisplayParams_inv_white2 = 24;
+const int OFF_DrDisplayParams_invalid_rgba = 28;
+const int DR_TONE_CLAMP = 0, DR_TONE_REINHARD = 1, DR_TONE_FILMIC = 2;
+const int DR_ENCODE_SRGB = 0, DR_ENCODE_GAMMA22 = 1, DR_ENCODE_REFERENCE = 2;
+const int DR_DISPLAY_BINS = 2048;
 
 // enums of the header
 const int DR_MATERIAL_MATTE = 0, DR_MATERIAL_MIRROR = 1, DR_MATERIAL_GLASS = 2, DR_MATERIAL_PLASTIC = 3;
@@ -273,6 +287,10 @@ typedef _DenoisePairC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<F
     Pointer<Float>);
 typedef _DenoisePairD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>,
     Pointer<Float>);
+// dr_display (the display transform on the GPU, host buffers; DESIGN.md 2.20): rgb[h][w][3], w, h, DrDisplayParams (32 bytes, the
+// OFF_DrDisplayParams_* offsets above), out[h][w][4] bytes R, G, B, A.  (Signature only, never compiled, like the rest.)
+typedef _DisplayC = Int32 Function(Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Uint8>);
+typedef _DisplayD = int Function(Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Uint8>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -337,6 +355,8 @@ class HipSamplerRenderer extends Renderer {
   static final _DenoiseAtrousD denoiseAtrous = _lib.lookupFunction<_DenoiseAtrousC, _DenoiseAtrousD>('dr_denoise_atrous');
   /// The same over two half-sample renders, whose difference estimates the variance that guides the colour term (after dr_init).
   static final _DenoisePairD denoisePair = _lib.lookupFunction<_DenoisePairC, _DenoisePairD>('dr_denoise_pair');
+  /// The display transform: linear f32 radiance to RGBA8 through exposure, a tone curve and an 8-bit encode (after dr_init).
+  static final _DisplayD displayImage = _lib.lookupFunction<_DisplayC, _DisplayD>('dr_display');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
   /// library of another layout version is refused before any struct crosses the boundary.
   static const int ABI_VERSION = 9;
