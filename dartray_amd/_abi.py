@@ -192,6 +192,14 @@ class DrDisplayParams(C.Structure):
                 ("key", C.c_float), ("inv_white2", C.c_float), ("invalid_rgba", C.c_uint32)]
 
 
+class DrNurbsPatch(C.Structure):
+    """One NURBS patch (dr_nurbs_dice / dr_nurbs_dice_device): include/dartray_hip.h."""
+    _fields_ = [("nu", C.c_int32), ("uorder", C.c_int32), ("uknots", C.c_void_p), ("u0", C.c_float), ("u1", C.c_float),
+                ("nv", C.c_int32), ("vorder", C.c_int32), ("vknots", C.c_void_p), ("v0", C.c_float), ("v1", C.c_float),
+                ("cp", C.c_void_p), ("homogeneous", C.c_int32), ("diceu", C.c_uint32), ("dicev", C.c_uint32), ("pad", C.c_uint32)]
+
+
+DR_NURBS_MAX_ORDER = 8
 DR_COMM_ID_BYTES = 128
 DR_ABI_VERSION = 9  # include/dartray_hip.h (tests/test_host_logic.py compares the two); lib() refuses a library of another version
 
@@ -209,6 +217,10 @@ EXPORTS = {
                                     C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dr_loop_subdivide_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dr_nurbs_dice": (C.c_int, [C.POINTER(DrNurbsPatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "dr_nurbs_dice_device": (C.c_int, [C.POINTER(DrNurbsPatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "dr_denoise_atrous_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p]),
     "dr_denoise_atrous": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p]),
     "dr_denoise_atrous_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoiseParams), C.c_void_p,

@@ -28,6 +28,7 @@ from .. import _abi  # noqa: F401
 from .._abi import DartRayHipError  # noqa: F401  (re-export)
 from .transform import _bbox_transform, _inv, _m4, _mul, _normalize, look_at, transform_points  # noqa: F401
 from .shapes import Disk, LoopSubdivision, Sphere, TriangleMesh, _Quadric, loop_subdivide  # noqa: F401
+from .shapes import Nurbs, nurbs_dice  # noqa: F401  (core.Nurbs / core.nurbs_dice; not in __all__: the package's star-import list is recorded)
 from .materials import GlassMaterial, MatteMaterial, MirrorMaterial, PlasticMaterial  # noqa: F401
 from .lights import DiffuseAreaLight, DistantLight, InfiniteAreaLight, PointLight, SpotLight, delta_light_kind  # noqa: F401
 from .accel import (HIT_DTYPE, NODE_DTYPE, BVHAccel, GeometricPrimitive, Ray, Scene, _DeviceScene, build_bvh_arrays,  # noqa: F401

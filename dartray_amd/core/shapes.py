@@ -177,3 +177,85 @@ class LoopSubdivision:
         P, N, idx, self.builder = loop_subdivide(self.indices, self.P, self.nLevels, builder)
         return TriangleMesh(idx, transform_points(self.objectToWorld, P), self.reverseOrientation, n=N,
                             objectToWorld=self.objectToWorld, worldToObject=self.worldToObject)
+
+
+def nurbs_dice(nu, uorder, uknots, u0, u1, nv, vorder, vknots, v0, v1, P=None, Pw=None, diceu=30, dicev=30, builder=None):
+    """Nurbs.refine (nurbs.dart:76-154) through the C ABI: (P, N, uv, indices, builder that ran) of the TriangleMesh it creates, object
+    space.  P: nu * nv points [., 3], or else Pw: homogeneous points [., 4]; both u fastest.  Everything crosses as f32.  builder as for
+    loop_subdivide: "device" = dr_nurbs_dice_device (HIP; needs an initialised GPU), "host" = dr_nurbs_dice, None = _choose_builder's
+    rule.  Both write the same bytes, a NaN's sign and payload aside (tests/test_gpu_nurbs.py).  An input on which the evaluation
+    would index outside a list raises DartRayHipError with the refusal's name; two index expressions of the reference's text are repaired
+    (DESIGN.md 2.21)."""
+    builder = _choose_builder(builder)
+    lib = _abi.lib()
+    fn = lib.dr_nurbs_dice_device if builder == "device" else lib.dr_nurbs_dice
+    if (P is None) == (Pw is None):
+        raise ValueError("nurbs_dice needs exactly one of P and Pw")
+    uk = np.ascontiguousarray(uknots, dtype=np.float32).reshape(-1)
+    vk = np.ascontiguousarray(vknots, dtype=np.float32).reshape(-1)
+    cp = np.ascontiguousarray(P if Pw is None else Pw, dtype=np.float32).reshape(-1)
+    nu, uorder, nv, vorder = int(nu), int(uorder), int(nv), int(vorder)
+    if len(uk) != nu + uorder or len(vk) != nv + vorder:
+        raise ValueError("nurbs_dice needs nu + uorder uknots and nv + vorder vknots")
+    if len(cp) != nu * nv * (3 if Pw is None else 4):
+        raise ValueError("nurbs_dice needs nu * nv control points")
+    patch = _abi.DrNurbsPatch(nu, uorder, uk.ctypes.data, float(u0), float(u1), nv, vorder, vk.ctypes.data, float(v0), float(v1),
+                              cp.ctypes.data, 0 if Pw is None else 1, int(diceu), int(dicev), 0)
+    nverts, ntris = C.c_uint64(0), C.c_uint64(0)
+    _abi.check(fn(C.byref(patch), None, None, None, None, 0, 0, C.byref(nverts), C.byref(ntris)))  # the size query
+    Pout = np.empty((nverts.value, 3), np.float32)
+    Nout = np.empty((nverts.value, 3), np.float32)
+    uv = np.empty((nverts.value, 2), np.float32)
+    idx = np.empty((ntris.value, 3), np.uint32)
+    _abi.check(fn(C.byref(patch), Pout.ctypes.data, Nout.ctypes.data, uv.ctypes.data, idx.ctypes.data, nverts.value, ntris.value,
+                  C.byref(nverts), C.byref(ntris)))
+    return Pout, Nout, uv, idx, builder
+
+
+class Nurbs:
+    """shapes/nurbs.dart:23-74: Shape 'nurbs'.  Not intersectable; refine() gives ONE TriangleMesh with per-vertex normals and uvs
+    (:144-153).  P: nu * nv control points, u fastest, [., 3] or -- isHomogeneous -- [., 4].  The refusals happen in refine(), inside the
+    library."""
+
+    def __init__(self, o2w, w2o, reverseOrientation, nu, uorder, uknot, umin, umax, nv, vorder, vknot, vmin, vmax, P, isHomogeneous,
+                 diceu=30, dicev=30):
+        self.objectToWorld = np.ascontiguousarray(np.asarray(o2w, np.float32).reshape(4, 4))
+        self.worldToObject = np.ascontiguousarray(np.asarray(w2o, np.float32).reshape(4, 4))
+        self.reverseOrientation = bool(reverseOrientation)
+        self.nu, self.uorder, self.nv, self.vorder = int(nu), int(uorder), int(nv), int(vorder)
+        self.uknot = np.ascontiguousarray(uknot, dtype=np.float32).reshape(-1)
+        self.vknot = np.ascontiguousarray(vknot, dtype=np.float32).reshape(-1)
+        self.umin, self.umax, self.vmin, self.vmax = float(umin), float(umax), float(vmin), float(vmax)
+        self.isHomogeneous = bool(isHomogeneous)
+        self.P = np.ascontiguousarray(P, dtype=np.float32).reshape(-1, 4 if self.isHomogeneous else 3)
+        self.diceu, self.dicev = int(diceu), int(dicev)
+        self.builder = None  # the builder the last refine() ran
+
+    def canIntersect(self):
+        return False  # :72-74
+
+    def _points(self):
+        """The Points both bounds walk: P as it stands, or x / w, y / w, z / w in f64 stored f32 (:42-44, :63-65)."""
+        P = self.P[:self.nu * self.nv]
+        if not self.isHomogeneous:
+            return P
+        P64 = P.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (P64[:, :3] / P64[:, 3:4]).astype(np.float32)
+
+    def objectBound(self):  # :30-48
+        pts = self._points()
+        return pts.min(0), pts.max(0)
+
+    def worldBound(self):  # :50-70
+        pts = transform_points(self.objectToWorld, self._points())
+        return pts.min(0), pts.max(0)
+
+    def refine(self, builder=None):
+        """TriangleMesh.Create(objectToWorld, worldToObject, reverseOrientation, {indices, P, uv, N}) (:146-153): the positions go to
+        world space like any mesh's, the normals stay in object space with the transform."""
+        kw = {"Pw" if self.isHomogeneous else "P": self.P}
+        P, N, uv, idx, self.builder = nurbs_dice(self.nu, self.uorder, self.uknot, self.umin, self.umax, self.nv, self.vorder, self.vknot,
+                                                 self.vmin, self.vmax, diceu=self.diceu, dicev=self.dicev, builder=builder, **kw)
+        return TriangleMesh(idx, transform_points(self.objectToWorld, P), self.reverseOrientation, n=N, uvs=uv,
+                            objectToWorld=self.objectToWorld, worldToObject=self.worldToObject)

@@ -16,7 +16,7 @@ produce, and hands them to core.BVHAccel / core.SamplerRenderer (the C ABI).
 Matrices follow the reference's numerics (Float32List storage, f64
 expressions): matrix4x4.dart:193-343, transform.dart:83-86,110-129,214-331.
 
-Plugins on the path: shapes trianglemesh (with N / S / uv), heightfield, loopsubdiv, sphere, disk;
+Plugins on the path: shapes trianglemesh (with N / S / uv), heightfield, loopsubdiv, nurbs, sphere, disk;
 materials matte (Lambertian / Oren-Nayar), plastic, mirror, glass; area lights
 on any of those shapes, infinite lights (constant or .npy lat-long map), point,
 spot and distant lights; perspective / orthographic / environment cameras, image film, box / gaussian / mitchell / triangle / sinc filters,
@@ -761,8 +761,10 @@ class DartRay:
             if vi is None or P is None:
                 return None
             return core.LoopSubdivision(o2w.m, o2w.mInv, ro, vi, P, nlevels).refine()
+        if name == "nurbs":                   # nurbs.dart:265-321: refines into ONE TriangleMesh with N and uv
+            return self._makeNurbs(ps)
         if name != "trianglemesh":
-            raise UnsupportedFeature(f"Shape \"{name}\": only 'trianglemesh', 'heightfield', 'loopsubdiv', 'sphere' and 'disk' are on the path "
+            raise UnsupportedFeature(f"Shape \"{name}\": only 'trianglemesh', 'heightfield', 'loopsubdiv', 'nurbs', 'sphere' and 'disk' are on the path "
                                      "(SURVEY.md section 8 row f4)")
         vi = ps.findInt("indices")            # triangle_mesh.dart:91-193
         P = ps.findPoint("P")
@@ -813,6 +815,44 @@ class DartRay:
         return core.TriangleMesh(idx.astype(np.uint32), self.ctm.transformPoints(P), self.gs.reverseOrientation,
                                  n=N, s=S, uvs=None if uvs is None else np.asarray(uvs[:2 * len(P)], np.float32),
                                  objectToWorld=self.ctm.m, worldToObject=self.ctm.mInv)
+
+    def _makeNurbs(self, ps):
+        """Nurbs.Create (nurbs.dart:265-321).  Its asserts -- nu, uorder or the knots missing, a knot count other than nu + uorder -- are
+        refused with file:line (UnsupportedFeature is what the parser gives a position); its three error returns drop the shape.  The reference keeps a file's knots, u0 .. v1 and 'Pw' as the f64 the parser
+        read (param_set.dart:122-126, :534-543; pbrt_parser.dart:497-501) and only 'point P' as f32; the library takes f32, so a value
+        that f32 does not hold is rounded, with a warning."""
+        o2w, ro = self.ctm, self.gs.reverseOrientation
+        dirs = []
+        for d in "uv":
+            n, order, knots = ps.findOneInt("n" + d, -1), ps.findOneInt(d + "order", -1), ps.findFloat(d + "knots")
+            if n == -1 or order == -1 or knots is None:
+                raise UnsupportedFeature(f"Shape \"nurbs\" needs n{d}, {d}order and {d}knots")
+            if len(knots) != n + order:
+                raise UnsupportedFeature(f"Shape \"nurbs\": {len(knots)} {d}knots, expected n{d} + {d}order = {n + order}")
+            if not 1 <= order <= len(knots) or not 0 <= n < len(knots):
+                raise UnsupportedFeature(f"Shape \"nurbs\": n{d} or {d}order does not index the {d}knots")  # the defaults below index them
+            dirs.append((n, order, knots, ps.findOneFloat(d + "0", knots[order - 1]), ps.findOneFloat(d + "1", knots[n])))
+        (nu, uorder, uknots, u0, u1), (nv, vorder, vknots, v0, v1) = dirs
+        P = ps.findPoint("P")
+        homogeneous = P is None
+        if homogeneous:
+            Pw = ps.findFloat("Pw")
+            if Pw is None:
+                self.warn("Must provide control points via 'P' or 'Pw' parameter to NURBS shape.")
+                return None
+            if len(Pw) % 4 != 0:
+                self.warn("Number of 'Pw' control points provided to NURBS shape must be multiple of four")
+                return None
+            P = np.asarray(Pw, dtype=np.float64).reshape(-1, 4)
+        if len(P) != nu * nv:
+            self.warn(f"NURBS shape was expecting {nu}*{nv}={nu * nv} control points, was given {P.size}")
+            return None
+        f64 = np.concatenate([np.asarray(uknots, np.float64), np.asarray(vknots, np.float64), [u0, u1, v0, v1],
+                              P.astype(np.float64).reshape(-1) if homogeneous else []])
+        with np.errstate(over="ignore"):
+            if not np.array_equal(f64.astype(np.float32).astype(np.float64), f64, equal_nan=True):
+                self.warn("Shape \"nurbs\": a knot, u0 .. v1 or a 'Pw' value is not an f32; the reference keeps it as f64, it is rounded to f32 here")
+        return core.Nurbs(o2w.m, o2w.mInv, ro, nu, uorder, uknots, u0, u1, nv, vorder, vknots, v0, v1, P, homogeneous).refine()
 
     def shape(self, name, ps):  # dartray.dart:380-470
         mesh = self._makeShape(name, ps)

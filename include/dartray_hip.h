@@ -452,6 +452,43 @@ int dr_loop_subdivide_device(const uint32_t* indices, uint64_t nfaces, const flo
                              float* N_out, uint32_t* indices_out, uint64_t vert_cap, uint64_t face_cap, uint64_t* nverts_out,
                              uint64_t* nfaces_out);
 
+/* Nurbs (lib/shapes/nurbs.dart:23-321): refine() of Shape "nurbs" -- the patch evaluated at diceu x dicev points
+ * and handed to TriangleMesh.Create as one mesh with P, N and uv.  Everything is f32, as the ABI's other geometry: knots, ranges and control
+ * points.  cp: nu * nv points, u fastest, 3 floats each ('P', homogeneous 0) or 4 ('Pw', homogeneous 1).  diceu / dicev: points per
+ * direction, 0 = the reference's constant 30. */
+#define DR_NURBS_MAX_ORDER 8 /* ours: the de Boor work arrays have a fixed size per lane */
+typedef struct DrNurbsPatch {
+  int32_t nu, uorder;
+  const float* uknots; /* nu + uorder */
+  float u0, u1;
+  int32_t nv, vorder;
+  const float* vknots; /* nv + vorder */
+  float v0, v1;
+  const float* cp;
+  int32_t homogeneous;
+  uint32_t diceu, dicev;
+  uint32_t pad;
+} DrNurbsPatch; /* 72 bytes */
+/* Out, object space: P_out[nverts][3], N_out[nverts][3] (Normalize(Cross(dPdu, dPdv))), uv_out[nverts][2], indices_out[ntris][3] in the
+ * reference's order (:132-142); nverts = diceu * dicev, vertex v * diceu + u, ntris = 2 (diceu - 1)(dicev - 1).  The reference's text
+ * with its arithmetic -- f32 stores, f64 expressions in its operator order -- and TWO index expressions repaired: the
+ * control point of a work slot is read at cpi + (cpOffset * 4 + i) * cpStride (the text's (cpOffset + i) leaves its iso list beyond the
+ * first knot span and raises), and the de Boor step's left operand is cpWork[k + c] (the text's cpWork[j + c] is not the B-spline
+ * recurrence from order 3 on).  Bit for bit the reference's output for order 2 x 2 patches of one span; a NURBS surface everywhere.
+ * NaN where the arithmetic gives NaN (a zero knot span, a zero weight, a zero cross product); nothing is repaired or skipped there.
+ * Two calls, like dr_loop_subdivide: all four outputs NULL validates and writes *nverts / *ntris only; all four set, vert_capacity /
+ * tri_capacity are what the buffers hold, too few is DR_ERR_INVALID with nothing written.
+ * Refused by name, DR_ERR_INVALID (the evaluation would index outside a list or loop on each): a null patch, knot vector or control net;
+ * an order below 2 or above DR_NURBS_MAX_ORDER; nu < uorder or nv < vorder; a knot vector that decreases or holds a non-finite knot;
+ * u0 / u1 outside [uknots[uorder - 1], uknots[nu]], v likewise; diceu or dicev below 2 or above 4096, or diceu * dicev above 2^22;
+ * nu * nv above 2^24.  dr_nurbs_dice runs on the host and needs no GPU. */
+int dr_nurbs_dice(const DrNurbsPatch* patch, float* P_out, float* N_out, float* uv_out, uint32_t* indices_out, uint64_t vert_capacity,
+                  uint64_t tri_capacity, uint64_t* nverts, uint64_t* ntris);
+/* The same ON THE GPU (dr_nurbs_device.hip): identical arguments (host pointers) and byte-identical outputs, except that a NaN's sign
+ * and payload may differ.  One lane per dice point.  Needs dr_init. */
+int dr_nurbs_dice_device(const DrNurbsPatch* patch, float* P_out, float* N_out, float* uv_out, uint32_t* indices_out, uint64_t vert_capacity,
+                         uint64_t tri_capacity, uint64_t* nverts, uint64_t* ntris);
+
 /* The edge-avoiding a-trous denoiser (the reference has none): a post-process beside the render path, guided by
  * the images of DR_INTEGRATOR_FEATURE.  Row-major f32 images: rgb[h][w][3] (the beauty image), normal[h][w][3] (any 3-vector guide; a
  * DR_FEATURE_NS / _NG image as it stands), depth[h][w] (a scalar guide; channel 0 of a DR_FEATURE_DEPTH image), out[h][w][3].
@@ -805,7 +842,8 @@ const char* dr_version(void);
  * existing moved or changed its meaning, so the version stays 9; and the pair denoiser: one new struct, DrDenoisePairParams, that only its
  * three new entry points read -- dr_denoise_pair_host, dr_denoise_pair and dr_denoise_pair_device; and the display transform: one new struct,
  * DrDisplayParams, that only its seven new entry points read -- dr_display_check, dr_display_table, dr_display_host, dr_display,
- * dr_display_device, dr_display_exposure_host and dr_display_exposure). */
+ * dr_display_device, dr_display_exposure_host and dr_display_exposure; and the NURBS shape: one new struct, DrNurbsPatch, that only its
+ * two new entry points read -- dr_nurbs_dice and dr_nurbs_dice_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -932,6 +970,11 @@ DR_ABI_SIZE(DrDisplayParams, 32);
 DR_ABI_OFFSET(DrDisplayParams, permille, 12);
 DR_ABI_OFFSET(DrDisplayParams, exposure, 16);
 DR_ABI_OFFSET(DrDisplayParams, invalid_rgba, 28);
+DR_ABI_SIZE(DrNurbsPatch, 72);
+DR_ABI_OFFSET(DrNurbsPatch, uknots, 8);
+DR_ABI_OFFSET(DrNurbsPatch, nv, 24);
+DR_ABI_OFFSET(DrNurbsPatch, cp, 48);
+DR_ABI_OFFSET(DrNurbsPatch, dicev, 64);
 
 #ifdef __cplusplus
 }

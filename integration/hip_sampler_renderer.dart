@@ -189,6 +189,24 @@ const int OFF_DrDisplayParams_exposure = 16;
 const int OFF_DrDisplayParams_key = 20;
 const int OFF_DrDisplayParams_inv_white2 = 24;
 const int OFF_DrDisplayParams_invalid_rgba = 28;
+// DrNurbsPatch (one NURBS patch, DESIGN.md 2.21): per direction int32 n, int32 order, the address of n + order f32 knots and the f32 range;
+// the address of the nu * nv control points (3 floats each, or 4 when homogeneous is 1); uint32 dice rates (0: 30)
+const int SIZEOF_DrNurbsPatch = 72;
+const int OFF_DrNurbsPatch_nu = 0;
+const int OFF_DrNurbsPatch_uorder = 4;
+const int OFF_DrNurbsPatch_uknots = 8;
+const int OFF_DrNurbsPatch_u0 = 16;
+const int OFF_DrNurbsPatch_u1 = 20;
+const int OFF_DrNurbsPatch_nv = 24;
+const int OFF_DrNurbsPatch_vorder = 28;
+const int OFF_DrNurbsPatch_vknots = 32;
+const int OFF_DrNurbsPatch_v0 = 40;
+const int OFF_DrNurbsPatch_v1 = 44;
+const int OFF_DrNurbsPatch_cp = 48;
+const int OFF_DrNurbsPatch_homogeneous = 56;
+const int OFF_DrNurbsPatch_diceu = 60;
+const int OFF_DrNurbsPatch_dicev = 64;
+const int DR_NURBS_MAX_ORDER = 8;
 const int DR_TONE_CLAMP = 0, DR_TONE_REINHARD = 1, DR_TONE_FILMIC = 2;
 const int DR_ENCODE_SRGB = 0, DR_ENCODE_GAMMA22 = 1, DR_ENCODE_REFERENCE = 2;
 const int DR_DISPLAY_BINS = 2048;
@@ -276,6 +294,13 @@ typedef _LoopSubdivideC = Int32 Function(Pointer<Uint32>, Uint64, Pointer<Float>
     Uint64, Uint64, Pointer<Uint64>, Pointer<Uint64>);
 typedef _LoopSubdivideD = int Function(Pointer<Uint32>, int, Pointer<Float>, int, int, Pointer<Float>, Pointer<Float>, Pointer<Uint32>,
     int, int, Pointer<Uint64>, Pointer<Uint64>);
+// dr_nurbs_dice / dr_nurbs_dice_device (Nurbs.refine on the host / on the GPU; DESIGN.md 2.21): DrNurbsPatch (72 bytes, the OFF_DrNurbsPatch_*
+// offsets above), P_out, N_out, uv_out, indices_out, vert_capacity, tri_capacity, nverts, ntris.  All four outputs null: the size query.
+// (Signatures only, never compiled, like the rest.)
+typedef _NurbsDiceC = Int32 Function(Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Uint32>, Uint64, Uint64,
+    Pointer<Uint64>, Pointer<Uint64>);
+typedef _NurbsDiceD = int Function(Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Uint32>, int, int,
+    Pointer<Uint64>, Pointer<Uint64>);
 // dr_denoise_atrous (the edge-avoiding a-trous filter on the GPU, host buffers; DESIGN.md 2.15): rgb[h][w][3], normal[h][w][3], depth[h][w],
 // w, h, DrDenoiseParams (16 bytes, the OFF_DrDenoiseParams_* offsets above), out[h][w][3].  (Signature only, never compiled, like the rest.)
 typedef _DenoiseAtrousC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>);
@@ -351,6 +376,9 @@ class HipSamplerRenderer extends Renderer {
   /// LoopSubdivision.refine behind the C ABI: the host builder and, after dr_init, the device builder (same bytes).
   static final _LoopSubdivideD loopSubdivide = _lib.lookupFunction<_LoopSubdivideC, _LoopSubdivideD>('dr_loop_subdivide');
   static final _LoopSubdivideD loopSubdivideDevice = _lib.lookupFunction<_LoopSubdivideC, _LoopSubdivideD>('dr_loop_subdivide_device');
+  /// Nurbs.refine behind the C ABI: the host builder and, after dr_init, the device builder (same bytes, a NaN's payload aside).
+  static final _NurbsDiceD nurbsDice = _lib.lookupFunction<_NurbsDiceC, _NurbsDiceD>('dr_nurbs_dice');
+  static final _NurbsDiceD nurbsDiceDevice = _lib.lookupFunction<_NurbsDiceC, _NurbsDiceD>('dr_nurbs_dice_device');
   /// The a-trous denoiser over a finished image and its FeatureIntegrator normal and depth images (after dr_init).
   static final _DenoiseAtrousD denoiseAtrous = _lib.lookupFunction<_DenoiseAtrousC, _DenoiseAtrousD>('dr_denoise_atrous');
   /// The same over two half-sample renders, whose difference estimates the variance that guides the colour term (after dr_init).
