@@ -192,6 +192,10 @@ class DrDisplayParams(C.Structure):
                 ("key", C.c_float), ("inv_white2", C.c_float), ("invalid_rgba", C.c_uint32)]
 
 
+class DrUpsampleParams(C.Structure):
+    _fields_ = [("factor", C.c_int32), ("taps", C.c_int32), ("k_normal", C.c_float), ("k_depth", C.c_float)]
+
+
 class DrNurbsPatch(C.Structure):
     """One NURBS patch (dr_nurbs_dice / dr_nurbs_dice_device): include/dartray_hip.h."""
     _fields_ = [("nu", C.c_int32), ("uorder", C.c_int32), ("uknots", C.c_void_p), ("u0", C.c_float), ("u1", C.c_float),
@@ -239,6 +243,13 @@ EXPORTS = {
                                     C.c_void_p]),
     "dr_display_exposure_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p, C.c_void_p]),
     "dr_display_exposure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p, C.c_void_p]),
+    "dr_upsample_check": (C.c_int, [C.POINTER(DrUpsampleParams), C.c_int32, C.c_int32]),
+    "dr_upsample_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(DrUpsampleParams),
+                                   C.c_void_p]),
+    "dr_upsample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(DrUpsampleParams),
+                              C.c_void_p]),
+    "dr_upsample_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(DrUpsampleParams),
+                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
     "dr_scene_create": (C.c_int, [C.POINTER(DrSceneDesc), C.POINTER(C.c_void_p)]),
     "dr_scene_destroy": (None, [C.c_void_p]),
     "dr_scene_get_trace_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 2)]),

@@ -9,6 +9,11 @@ and its variance-guided form over two half-sample renders (dr_de
     atrous_pair(a, b, normal, depth, ...)         filters the mean of two renders, guided by the variance their difference estimates
     render_denoised_pair(renderer, scene, ...)    renders the two halves and the two guides, and filters
 
+and the joint bilateral upsampler that lets a render trace 1/4 or 1/16 of the camera pixels (dr_upsample*):
+
+    upsample(rgb_lo, normal_lo, depth_lo, normal, depth, ...)    a low-resolution image becomes a full-resolution one under full-resolution guides
+    render_upsampled(low_renderer, full_renderer, scene, ...)    renders the low-resolution image and both sets of guides, and upsamples
+
 The library takes sharpness values k = 1 / sigma^2 (k = 0: the term is off); this module takes the sigmas.
 """
 import copy
@@ -159,4 +164,99 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", **fi
     out.a, out.b, out.normal, out.depth, out.variance = half_a.rgb, half_b.rgb, normal, depth, variance
     with np.errstate(all="ignore"):
         out.noisy = np.float32(0.5) * (out.a + out.b)
+    return out
+
+
+def upsample_params(factor, taps=2, sigma_normal=SIGMA_NORMAL, sigma_depth=SIGMA_DEPTH):
+    return _abi.DrUpsampleParams(int(factor), int(taps), sharpness(sigma_normal), sharpness(sigma_depth))
+
+
+def upsample(rgb_lo, normal_lo, depth_lo, normal, depth, factor=None, taps=2, sigma_normal=SIGMA_NORMAL, sigma_depth=SIGMA_DEPTH, device=True):
+    """rgb_lo [hl, wl, 3], normal_lo [hl, wl, 3], depth_lo [hl, wl] -- an image rendered at 1/factor of the resolution per axis and the guides
+    aligned with it -- and the full-resolution guides normal [h, w, 3], depth [h, w], h = factor * hl, w = factor * wl -> the upsampled
+    [h, w, 3] f32.  factor: 2 or 4; None derives it from the shapes.  taps: 2 or 4, the footprint's side in low-resolution pixels.
+    device=True: dr_upsample, on the GPU; device=False: dr_upsample_host, which needs none and writes the same bytes."""
+    rgb_lo = np.ascontiguousarray(rgb_lo, dtype=np.float32)
+    normal_lo = np.ascontiguousarray(normal_lo, dtype=np.float32)
+    depth_lo = np.ascontiguousarray(depth_lo, dtype=np.float32)
+    normal = np.ascontiguousarray(normal, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if rgb_lo.ndim != 3 or rgb_lo.shape[2] != 3 or normal_lo.shape != rgb_lo.shape or depth_lo.shape != rgb_lo.shape[:2]:
+        raise ValueError("upsample: rgb_lo and normal_lo must be [hl, wl, 3] and depth_lo [hl, wl] (got %r, %r, %r)"
+                         % (rgb_lo.shape, normal_lo.shape, depth_lo.shape))
+    if normal.ndim != 3 or normal.shape[2] != 3 or depth.shape != normal.shape[:2]:
+        raise ValueError("upsample: normal must be [h, w, 3] and depth [h, w] (got %r, %r)" % (normal.shape, depth.shape))
+    hl, wl = depth_lo.shape
+    h, w = depth.shape
+    if factor is None:
+        factor = h // hl if hl else 0
+        if factor not in (2, 4):
+            raise ValueError("upsample: the full-resolution guides must be 2 or 4 times the low-resolution image in both axes (got %r for %r)"
+                             % (depth.shape, depth_lo.shape))
+    factor = int(factor)
+    if (h, w) != (factor * hl, factor * wl):
+        raise ValueError("upsample: the full-resolution guides must be %d times the low-resolution image in both axes (got %r for %r)"
+                         % (factor, depth.shape, depth_lo.shape))
+    p = upsample_params(factor, taps, sigma_normal, sigma_depth)
+    out = np.zeros_like(normal)
+    lib = _abi.lib()
+    if device:
+        _abi.init(_abi._initialised if _abi._initialised is not None else 0)
+    fn = lib.dr_upsample if device else lib.dr_upsample_host
+    _abi.check(fn(rgb_lo.ctypes.data, normal_lo.ctypes.data, depth_lo.ctypes.data, wl, hl, normal.ctypes.data, depth.ctypes.data, C.byref(p),
+                  out.ctypes.data))
+    return out
+
+
+def _upsample_refusals(who, low, full):
+    """What render_upsampled asks of its two renderers, each refusal by name; returns the factor."""
+    for name, r in (("low_renderer", low), ("full_renderer", full)):
+        if isinstance(r.sampler, AdaptiveSampler):
+            raise ValueError("%s: the adaptive sampler is not supported (%s; the feature integrator refuses it)" % (who, name))
+        if r.tileCount > 1:
+            raise ValueError("%s: tileCount > 1 is not supported (%s has tileCount %d): sharded upsampling is out of scope" % (who, name, r.tileCount))
+        if r.taskCount > 1:
+            raise ValueError("%s: taskCount > 1 is not supported (%s has taskCount %d): sharded upsampling is out of scope" % (who, name, r.taskCount))
+        crop = tuple(r.camera.film.cropWindow)
+        if crop != (0.0, 1.0, 0.0, 1.0):
+            raise ValueError("%s: a crop window other than the whole film is not supported (%s has %r)" % (who, name, crop))
+    lf, ff = low.camera.film, full.camera.film
+    lo, hi = (lf.xResolution, lf.yResolution), (ff.xResolution, ff.yResolution)
+    factor = next((f for f in (2, 4) if hi == (f * lo[0], f * lo[1])), None)
+    if factor is None:
+        raise ValueError("%s: full_renderer's film must be exactly 2 or 4 times low_renderer's in both axes (got %d x %d for %d x %d)"
+                         % (who, hi[0], hi[1], lo[0], lo[1]))
+    pose = [getattr(r.camera, "cameraToWorld", None) for r in (low, full)]
+    if pose[0] is not None and pose[1] is not None and not np.array_equal(np.asarray(pose[0]), np.asarray(pose[1])):
+        raise ValueError("%s: low_renderer's and full_renderer's cameras differ in their pose" % (who,))
+    return factor
+
+
+def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", taps=2, denoise=False, **kw):
+    """Renders the beauty image and two FeatureIntegrator images -- `normal_channel` ("ns" or "ng") and "depth" -- with `low_renderer`, whose
+    film is 1/2 or 1/4 of `full_renderer`'s in both axes over the same camera pose, the same two guides with `full_renderer`'s sampler and
+    camera -- its own surface integrator is never run -- and upsamples.  Returns an OutputImage of the full size whose rgb is the result;
+    with denoise=True it is atrous(upsampled, normal, depth, **kw).  The parts stay on it as `low` [hl, wl, 3], `normal_lo`, `depth_lo`,
+    `normal` and `depth`, and `upsampled` [h, w, 3].  kw: sigma_normal and sigma_depth go to both stages; atrous()'s other keywords need
+    denoise=True."""
+    who = "render_upsampled"
+    if normal_channel not in ("ns", "ng"):
+        raise ValueError("%s: normal_channel must be ns or ng (got %r)" % (who, normal_channel))
+    factor = _upsample_refusals(who, low_renderer, full_renderer)
+    guide_kw = {k: kw[k] for k in ("sigma_normal", "sigma_depth") if k in kw}
+    if not denoise and len(guide_kw) != len(kw):
+        raise ValueError("%s: %s given without denoise=True" % (who, ", ".join(sorted(set(kw) - set(guide_kw)))))
+
+    def guides(r):
+        def one(channel):
+            return SamplerRenderer(r.sampler, r.camera, FeatureIntegrator(channel), r.volumeIntegrator, taskNum=r.taskNum, taskCount=r.taskCount,
+                                   tileRank=r.tileRank, tileCount=r.tileCount, tileSize=r.tileSize).render(scene)
+        return one(normal_channel).rgb, np.ascontiguousarray(one("depth").rgb[..., 0])
+    low = low_renderer.render(scene)
+    normal_lo, depth_lo = guides(low_renderer)
+    normal, depth = guides(full_renderer)
+    up = upsample(low.rgb, normal_lo, depth_lo, normal, depth, factor=factor, taps=taps, **guide_kw)
+    film = full_renderer.camera.film
+    out = OutputImage(film.left, film.top, film.width, film.height, atrous(up, normal, depth, **kw) if denoise else up)
+    out.low, out.normal_lo, out.depth_lo, out.normal, out.depth, out.upsampled = low.rgb, normal_lo, depth_lo, normal, depth, up
     return out

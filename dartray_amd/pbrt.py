@@ -468,9 +468,14 @@ class DartRay:
     (core.SamplerRenderer); with `render=True` (the reference's behaviour, dartray.dart:562-585) it also
     renders on the device and leaves the result in `self.outputImage`.  `overrides` mirrors
     RenderOverrides (core/render_overrides.dart): 'xresolution', 'yresolution', 'pixelsamples', 'seed',
-    'taskNum', 'taskCount'."""
+    'taskNum', 'taskCount'.  `upsample` (2 or 4): worldEnd() also builds `self.lowRendererObject`, the same renderer over a film of
+    1 / upsample of the resolution per axis -- the low-resolution half of denoise.render_upsampled."""
 
-    def __init__(self, render=True, overrides=None, warn=None):
+    def __init__(self, render=True, overrides=None, warn=None, upsample=None):
+        if upsample not in (None, 2, 4):
+            raise ValueError("upsample must be 2 or 4 (got %r)" % (upsample,))
+        self.upsample = upsample
+        self.lowRendererObject = None
         self.renderOnWorldEnd = render
         self.overrides = dict(overrides or {})
         self.warn = warn or (lambda msg: None)
@@ -887,7 +892,7 @@ class DartRay:
         raise UnsupportedFeature("ObjectInstance: instancing is not on the path")
 
     # -- worldEnd (dartray.dart:549-780) --------------------------------------
-    def _makeFilm(self):
+    def _makeFilm(self, divide=1):
         o = self.opt
         fp = o["filterParams"]
         name = o["filterName"]
@@ -909,6 +914,9 @@ class DartRay:
         ps = o["filmParams"]                                   # image_film.dart:309-324
         xres = int(self.overrides.get("xresolution", ps.findOneInt("xresolution", 640)))
         yres = int(self.overrides.get("yresolution", ps.findOneInt("yresolution", 480)))
+        if xres % divide or yres % divide:
+            raise ValueError(f"upsample {divide}: the film's resolution, {xres} x {yres}, is not a multiple of {divide} in both axes")
+        xres, yres = xres // divide, yres // divide
         ps.findOneString("filename", "")
         crop = ps.findFloat("cropwindow")
         if crop is None or len(crop) != 4:
@@ -955,14 +963,15 @@ class DartRay:
             return core.DirectLightingIntegrator(1 if st == "one" else 0, maxdepth)
         raise UnsupportedFeature(f"SurfaceIntegrator \"{name}\": only 'path' and 'directlighting' are on the path")
 
-    def makeRenderer(self, **renderer_kw):
-        """_makeRenderer (dartray.dart:640-700): film, camera, sampler, integrators, SamplerRenderer."""
+    def makeRenderer(self, divide=1, **renderer_kw):
+        """_makeRenderer (dartray.dart:640-700): film, camera, sampler, integrators, SamplerRenderer.  divide: the film's resolution is the
+        file's over `divide` in both axes (the low-resolution renderer of an upsampled render)."""
         o = self.opt
         if o["rendererName"] != "sampler":
             raise UnsupportedFeature(f"Renderer \"{o['rendererName']}\": only 'sampler' is on the path")
         if o["samplerName"] not in ("lowdiscrepancy", "stratified", "adaptive"):
             raise UnsupportedFeature(f"Sampler \"{o['samplerName']}\": only 'lowdiscrepancy', 'stratified' and 'adaptive' are on the path")
-        film = self._makeFilm()
+        film = self._makeFilm(divide)
         camera = self._makeCamera(film)
         pname, pps = o["pixelSamplerName"], o["pixelSamplerParams"]          # dartray.dart:980-996
         if pname == "tile":                                                  # tile_pixel_sampler.dart:102-106
@@ -1011,6 +1020,8 @@ class DartRay:
         self._pushedGS.clear()
         self._pushedCTM.clear()
         self.rendererObject = self.makeRenderer()
+        if self.upsample:
+            self.lowRendererObject = self.makeRenderer(divide=self.upsample)
         self.scene = self.makeScene()
         self.sceneLights = list(self.lights)
         self.scenePrimitives = list(self.primitives)
@@ -1050,17 +1061,18 @@ class DartRay:
         return env[0], None
 
 
-def load(path, render=False, overrides=None, warn=None):
+def load(path, render=False, overrides=None, warn=None, upsample=None):
     """Parse a .pbrt (or .pbrt.gz) file; returns the DartRay API object with `.scene`, `.rendererObject`,
-    `.scenePrimitives`, `.sceneLights` (and `.outputImage` when render=True)."""
-    api = DartRay(render=render, overrides=overrides, warn=warn)
+    `.scenePrimitives`, `.sceneLights` (and `.outputImage` when render=True).  upsample=2 or 4: also `.lowRendererObject`, the same
+    renderer over the film's resolution divided by it."""
+    api = DartRay(render=render, overrides=overrides, warn=warn, upsample=upsample)
     api.base = os.path.dirname(os.path.abspath(path))
     PbrtParser(api).parse(path)
     return api
 
 
-def loads(text, base=".", render=False, overrides=None, warn=None):
-    api = DartRay(render=render, overrides=overrides, warn=warn)
+def loads(text, base=".", render=False, overrides=None, warn=None, upsample=None):
+    api = DartRay(render=render, overrides=overrides, warn=warn, upsample=upsample)
     api.base = base
     PbrtParser(api).parseString(text, "<string>", base)
     return api
@@ -1075,8 +1087,11 @@ def _write_pfm(path, rgb):
 
 
 def main(argv=None):
-    """python -m dartray_amd.pbrt scene.pbrt [-o out.pfm|out.npy|out.png|out.ppm] [--spp N] [--xres W --yres H]
+    """python -m dartray_amd.pbrt scene.pbrt [-o out.pfm|out.npy|out.png|out.ppm] [--spp N] [--xres W --yres H] [--upsample 2|4]
     [--exposure auto|SCALE] [--tonemap clamp|reinhard|filmic] [--encode srgb|gamma22|reference]
+
+    --upsample F traces the beauty image at 1/F of the film's resolution per axis and brings it to the full resolution under full-resolution
+    normal and depth images (denoise.render_upsampled).
 
     .png and .ppm go through the display transform (dartray_amd/display.py), which the three last flags choose; .npy and
     every other suffix hold the linear f32 radiance."""
@@ -1088,6 +1103,7 @@ def main(argv=None):
     ap.add_argument("--spp", type=int)
     ap.add_argument("--xres", type=int)
     ap.add_argument("--yres", type=int)
+    ap.add_argument("--upsample", type=int, choices=[2, 4], help="trace 1/2 or 1/4 of the resolution per axis and upsample under full-resolution guides")
     ap.add_argument("--exposure", default="auto", help=".png / .ppm: auto (the median luminance goes to 0.18), or the scale as a number")
     ap.add_argument("--tonemap", default="reinhard", choices=["clamp", "reinhard", "filmic"])
     ap.add_argument("--encode", default="srgb", choices=["srgb", "gamma22", "reference"])
@@ -1100,11 +1116,21 @@ def main(argv=None):
             ap.error("--exposure must be auto or a number (got %r)" % (a.exposure,))
     ov = {k: v for k, v in (("pixelsamples", a.spp), ("xresolution", a.xres), ("yresolution", a.yres)) if v}
     t0 = time.time()
-    api = load(a.scene, render=False, overrides=ov, warn=lambda m: print("warning:", m))
+    try:
+        api = load(a.scene, render=False, overrides=ov, warn=lambda m: print("warning:", m), upsample=a.upsample)
+    except ValueError as e:
+        if not a.upsample or "upsample" not in str(e):
+            raise
+        ap.error(str(e))
     t1 = time.time()
-    out = api.rendererObject.render(api.scene)
+    if a.upsample:
+        from . import denoise
+        out = denoise.render_upsampled(api.lowRendererObject, api.rendererObject, api.scene)
+        st = api.lowRendererObject.last_stats
+    else:
+        out = api.rendererObject.render(api.scene)
+        st = api.rendererObject.last_stats
     t2 = time.time()
-    st = api.rendererObject.last_stats
     print(f"parsed + built BVH in {t1 - t0:.2f} s; rendered {out.width}x{out.height} in {t2 - t1:.2f} s "
           f"({st['camera_samples'] / max(t2 - t1, 1e-9) / 1e6:.1f} Msamples/s)")
     if a.output:

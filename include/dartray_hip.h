@@ -547,6 +547,37 @@ int dr_denoise_pair_device(const void* a_dev, const void* b_dev, const void* nor
                            const DrDenoisePairParams* params, void* out_dev, void* out_var_dev, void* scratch_dev, uint64_t* scratch_bytes,
                            void* hip_stream);
 
+/* The joint bilateral upsampler (Kopf et al. 2007 with the denoiser's rational edge-stopping weights): a beauty image
+ * rendered at 1/factor of the resolution per axis, rgb_lo[hl][wl][3], with guides aligned with it, normal_lo[hl][wl][3] and depth_lo[hl][wl],
+ * becomes out[h][w][3], w = factor * wl, h = factor * hl, under the full-resolution guides normal[h][w][3] and depth[h][w].  Pixel (x, y) is
+ * the weighted mean of the taps x taps low-resolution pixels around (u, v) = ((x + 0.5) / factor - 0.5, (y + 0.5) / factor - 0.5) that lie
+ * inside the image and are valid (colour, normal and depth finite); a tap's weight is the tent (1 - |u - i| / r) * (1 - |v - j| / r),
+ * r = taps / 2, divided by (1 + k * d) for the squared normal and depth distance between the tap's guide and the pixel's own, each only
+ * where its k is not 0 and the pixel's own guide is finite.  No tap, or every weight 0: the colour of low-resolution pixel
+ * (x / factor, y / factor), bit for bit.  f32 arithmetic, one rounding per operator: the three entry points below write the same bytes. */
+typedef struct DrUpsampleParams {
+  int32_t factor;  /* 2 or 4 */
+  int32_t taps;    /* 2 or 4: the footprint is taps x taps low-resolution pixels */
+  float k_normal;  /* finite, >= 0; 0: the term is off.  As in DrDenoiseParams */
+  float k_depth;
+} DrUpsampleParams; /* 16 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer, a factor or taps other than 2 or 4, wl or hl < 1, w * h >= 2^31, a k that is negative
+ * or not finite, `out` overlapping an input (or the scratch buffer).  dr_upsample_check states them without an image. */
+int dr_upsample_check(const DrUpsampleParams* params, int32_t wl, int32_t hl);
+/* dr_upsample_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_upsample_host(const float* rgb_lo, const float* normal_lo, const float* depth_lo, int32_t wl, int32_t hl, const float* normal,
+                     const float* depth, const DrUpsampleParams* params, float* out);
+/* The same ON THE GPU (dr_upsample_device.hip), host buffers: uploads, upsamples, copies back.  Needs dr_init. */
+int dr_upsample(const float* rgb_lo, const float* normal_lo, const float* depth_lo, int32_t wl, int32_t hl, const float* normal,
+                const float* depth, const DrUpsampleParams* params, float* out);
+/* The same on device buffers, asynchronous on the given hipStream_t.  scratch_dev == NULL: the size query -- writes the bytes of scratch a
+ * low-resolution image of wl x hl needs to *scratch_bytes and does nothing else (the image pointers are not read and may be NULL).
+ * Otherwise *scratch_bytes is the size of scratch_dev (too small is DR_ERR_INVALID), which must be 16-byte aligned and is the call's to
+ * overwrite until the stream has run it. */
+int dr_upsample_device(const void* rgb_lo_dev, const void* normal_lo_dev, const void* depth_lo_dev, int32_t wl, int32_t hl,
+                       const void* normal_dev, const void* depth_dev, const DrUpsampleParams* params, void* out_dev, void* scratch_dev,
+                       uint64_t* scratch_bytes, void* hip_stream);
+
 /* The display transform: rgb[h][w][3], row-major f32 linear radiance, becomes out[h][w][4], bytes R, G, B, A = 255.
  * Per pixel: a non-finite channel makes the pixel invalid (it is no sample of the histogram and comes out as invalid_rgba); a negative channel
  * is taken as 0; the channels are multiplied by the exposure scale, go through the tone curve and are encoded to a byte each.  The scale is
@@ -843,7 +874,8 @@ const char* dr_version(void);
  * three new entry points read -- dr_denoise_pair_host, dr_denoise_pair and dr_denoise_pair_device; and the display transform: one new struct,
  * DrDisplayParams, that only its seven new entry points read -- dr_display_check, dr_display_table, dr_display_host, dr_display,
  * dr_display_device, dr_display_exposure_host and dr_display_exposure; and the NURBS shape: one new struct, DrNurbsPatch, that only its
- * two new entry points read -- dr_nurbs_dice and dr_nurbs_dice_device). */
+ * two new entry points read -- dr_nurbs_dice and dr_nurbs_dice_device; and the upsampler: one new struct, DrUpsampleParams, that only its
+ * four new entry points read -- dr_upsample_check, dr_upsample_host, dr_upsample and dr_upsample_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -975,6 +1007,10 @@ DR_ABI_OFFSET(DrNurbsPatch, uknots, 8);
 DR_ABI_OFFSET(DrNurbsPatch, nv, 24);
 DR_ABI_OFFSET(DrNurbsPatch, cp, 48);
 DR_ABI_OFFSET(DrNurbsPatch, dicev, 64);
+DR_ABI_SIZE(DrUpsampleParams, 16);
+DR_ABI_OFFSET(DrUpsampleParams, taps, 4);
+DR_ABI_OFFSET(DrUpsampleParams, k_normal, 8);
+DR_ABI_OFFSET(DrUpsampleParams, k_depth, 12);
 
 #ifdef __cplusplus
 }

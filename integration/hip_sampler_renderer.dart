@@ -189,6 +189,13 @@ const int OFF_DrDisplayParams_exposure = 16;
 const int OFF_DrDisplayParams_key = 20;
 const int OFF_DrDisplayParams_inv_white2 = 24;
 const int OFF_DrDisplayParams_invalid_rgba = 28;
+// DrUpsampleParams (the joint bilateral upsampler, DESIGN.md 2.22): int32 factor (2 or 4) at 0, int32 taps (2 or 4) at 4, then the two f32
+// sharpness values k = 1 / sigma^2 of the normal and the depth term
+const int SIZEOF_DrUpsampleParams = 16;
+const int OFF_DrUpsampleParams_factor = 0;
+const int OFF_DrUpsampleParams_taps = 4;
+const int OFF_DrUpsampleParams_k_normal = 8;
+const int OFF_DrUpsampleParams_k_depth = 12;
 // DrNurbsPatch (one NURBS patch, DESIGN.md 2.21): per direction int32 n, int32 order, the address of n + order f32 knots and the f32 range;
 // the address of the nu * nv control points (3 floats each, or 4 when homogeneous is 1); uint32 dice rates (0: 30)
 const int SIZEOF_DrNurbsPatch = 72;
@@ -312,6 +319,13 @@ typedef _DenoisePairC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<F
     Pointer<Float>);
 typedef _DenoisePairD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>,
     Pointer<Float>);
+// dr_upsample (the joint bilateral upsampler on the GPU, host buffers; DESIGN.md 2.22): rgb_lo[hl][wl][3], normal_lo[hl][wl][3], depth_lo[hl][wl],
+// wl, hl, normal[h][w][3], depth[h][w] with w = factor * wl and h = factor * hl, DrUpsampleParams (16 bytes, the OFF_DrUpsampleParams_* offsets
+// above), out[h][w][3].  (Signature only, never compiled, like the rest.)
+typedef _UpsampleC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32, Pointer<Float>, Pointer<Float>, Pointer<Uint8>,
+    Pointer<Float>);
+typedef _UpsampleD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Float>, Pointer<Float>, Pointer<Uint8>,
+    Pointer<Float>);
 // dr_display (the display transform on the GPU, host buffers; DESIGN.md 2.20): rgb[h][w][3], w, h, DrDisplayParams (32 bytes, the
 // OFF_DrDisplayParams_* offsets above), out[h][w][4] bytes R, G, B, A.  (Signature only, never compiled, like the rest.)
 typedef _DisplayC = Int32 Function(Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Uint8>);
@@ -383,6 +397,9 @@ class HipSamplerRenderer extends Renderer {
   static final _DenoiseAtrousD denoiseAtrous = _lib.lookupFunction<_DenoiseAtrousC, _DenoiseAtrousD>('dr_denoise_atrous');
   /// The same over two half-sample renders, whose difference estimates the variance that guides the colour term (after dr_init).
   static final _DenoisePairD denoisePair = _lib.lookupFunction<_DenoisePairC, _DenoisePairD>('dr_denoise_pair');
+  /// The joint bilateral upsampler: an image rendered at 1/2 or 1/4 of the resolution per axis, brought to the full resolution under
+  /// full-resolution FeatureIntegrator normal and depth images (after dr_init).
+  static final _UpsampleD upsample = _lib.lookupFunction<_UpsampleC, _UpsampleD>('dr_upsample');
   /// The display transform: linear f32 radiance to RGBA8 through exposure, a tone curve and an 8-bit encode (after dr_init).
   static final _DisplayD displayImage = _lib.lookupFunction<_DisplayC, _DisplayD>('dr_display');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
