@@ -196,6 +196,11 @@ class DrUpsampleParams(C.Structure):
     _fields_ = [("factor", C.c_int32), ("taps", C.c_int32), ("k_normal", C.c_float), ("k_depth", C.c_float)]
 
 
+class DrTemporalParams(C.Structure):
+    _fields_ = [("raster_to_camera", C.c_double * 16), ("cur_to_prev", C.c_double * 16), ("prev_to_raster", C.c_double * 16),
+                ("depth_tol", C.c_float), ("normal_tol", C.c_float), ("max_history", C.c_int32), ("reserved", C.c_uint32)]
+
+
 class DrNurbsPatch(C.Structure):
     """One NURBS patch (dr_nurbs_dice / dr_nurbs_dice_device): include/dartray_hip.h."""
     _fields_ = [("nu", C.c_int32), ("uorder", C.c_int32), ("uknots", C.c_void_p), ("u0", C.c_float), ("u1", C.c_float),
@@ -250,6 +255,10 @@ EXPORTS = {
                               C.c_void_p]),
     "dr_upsample_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(DrUpsampleParams),
                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "dr_temporal_check": (C.c_int, [C.POINTER(DrTemporalParams), C.c_int32, C.c_int32]),
+    "dr_temporal_host": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.POINTER(DrTemporalParams)] + [C.c_void_p] * 3),
+    "dr_temporal": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.POINTER(DrTemporalParams)] + [C.c_void_p] * 3),
+    "dr_temporal_device": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.POINTER(DrTemporalParams)] + [C.c_void_p] * 4),
     "dr_scene_create": (C.c_int, [C.POINTER(DrSceneDesc), C.POINTER(C.c_void_p)]),
     "dr_scene_destroy": (None, [C.c_void_p]),
     "dr_scene_get_trace_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 2)]),

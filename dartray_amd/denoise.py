@@ -14,6 +14,12 @@ and the joint bilateral upsampler that lets a render trace 1/4 or 1/16 of the ca
     upsample(rgb_lo, normal_lo, depth_lo, normal, depth, ...)    a low-resolution image becomes a full-resolution one under full-resolution guides
     render_upsampled(low_renderer, full_renderer, scene, ...)    renders the low-resolution image and both sets of guides, and upsamples
 
+and temporal accumulation with reprojection for the frames of a camera animation (dr_temporal*):
+
+    temporal_matrices(camera, prev_camera)                       the three f64 matrices that take a pixel to the previous frame's raster
+    temporal(rgb, normal, depth, history, matrices, ...)         blends one frame into the history of the frames before it
+    render_sequence(renderers, scene, ...)                       renders one frame per camera pose and accumulates them
+
 The library takes sharpness values k = 1 / sigma^2 (k = 0: the term is off); this module takes the sigmas.
 """
 import copy
@@ -23,6 +29,7 @@ import math
 import numpy as np
 
 from . import _abi
+from .core.cameras import PerspectiveCamera
 from .core.renderer import FeatureIntegrator, OutputImage, SamplerRenderer
 from .core.samplers import AdaptiveSampler
 
@@ -260,3 +267,152 @@ def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", ta
     out = OutputImage(film.left, film.top, film.width, film.height, atrous(up, normal, depth, **kw) if denoise else up)
     out.low, out.normal_lo, out.depth_lo, out.normal, out.depth, out.upsampled = low.rgb, normal_lo, depth_lo, normal, depth, up
     return out
+
+
+# Temporal accumulation's defaults, set by reasoning and not tuned on any animation.  depth_tol: the reprojected distance and
+# the stored one are two roundings of one length where the surface is the same, and differ by the surface's depth gradient over the one
+# pixel a bilinear tap may lie away: a 35-degree lens at 64 pixels has pixels of 0.01 rad, so 2 % keeps a surface seen at up to 63 degrees
+# from its normal (tan 63 x 0.01), steeper ones at higher resolutions, and drops a step of more than 2 % of the distance.  normal_tol: the
+# guide is 0.5 * (n + 1), so a squared distance of 0.05 is |dn| = 0.45, about 26 degrees: wider than the a-trous filters' 11 degrees because
+# a rejected tap costs the whole history, not a part of one weight.  max_history: a new frame's weight never falls below 1/32; SVGF's fixed
+# alpha = 0.2 forgets within about five frames because it follows moving lights and objects, which are out of scope here, and a static
+# scene gains nothing from forgetting.
+DEPTH_TOL = 0.02
+NORMAL_TOL = 0.05
+MAX_HISTORY = 32
+
+
+def _camera_refusals(who, name, camera):
+    if type(camera) is not PerspectiveCamera:
+        raise ValueError("%s: %s is a %s: only a PerspectiveCamera is supported" % (who, name, type(camera).__name__))
+    if camera.lensRadius != 0.0:
+        raise ValueError("%s: %s has lensRadius %r: a camera with a lens is not supported" % (who, name, camera.lensRadius))
+
+
+def temporal_matrices(camera, prev_camera):
+    """The three row-major f64 4 x 4 matrices dr_temporal* takes -- (raster_to_camera, cur_to_prev, prev_to_raster) -- composed with numpy from
+    the two cameras' rasterToCamera and cameraToWorld: cur_to_prev = inv(prev.cameraToWorld) . cur.cameraToWorld and prev_to_raster =
+    inv(prev.rasterToCamera).  Both must be a PerspectiveCamera with lensRadius 0 over films of one size."""
+    who = "temporal_matrices"
+    _camera_refusals(who, "camera", camera)
+    _camera_refusals(who, "prev_camera", prev_camera)
+    cf, pf = camera.film, prev_camera.film
+    if (cf.xResolution, cf.yResolution) != (pf.xResolution, pf.yResolution):
+        raise ValueError("%s: the two cameras' films differ in size (%d x %d and %d x %d)"
+                         % (who, cf.xResolution, cf.yResolution, pf.xResolution, pf.yResolution))
+    r2c = np.array(camera.rasterToCamera, dtype=np.float64).reshape(4, 4)
+    cur_to_prev = np.linalg.inv(np.array(prev_camera.cameraToWorld, dtype=np.float64).reshape(4, 4)) @ np.array(camera.cameraToWorld, dtype=np.float64).reshape(4, 4)
+    prev_to_raster = np.linalg.inv(np.array(prev_camera.rasterToCamera, dtype=np.float64).reshape(4, 4))
+    return r2c, cur_to_prev, prev_to_raster
+
+
+def temporal_params(matrices, depth_tol=DEPTH_TOL, normal_tol=NORMAL_TOL, max_history=MAX_HISTORY):
+    if len(matrices) != 3:
+        raise ValueError("temporal: matrices must be (raster_to_camera, cur_to_prev, prev_to_raster), got %d of them" % (len(matrices),))
+    p = _abi.DrTemporalParams()
+    for name, m in zip(("raster_to_camera", "cur_to_prev", "prev_to_raster"), matrices):
+        m = np.asarray(m, dtype=np.float64)
+        if m.size != 16:
+            raise ValueError("temporal: %s must be a 4 x 4 matrix (got shape %r)" % (name, m.shape))
+        getattr(p, name)[:] = [float(v) for v in m.reshape(-1)]
+    p.depth_tol, p.normal_tol, p.max_history = float(depth_tol), float(normal_tol), int(max_history)
+    return p
+
+
+class TemporalFrame:
+    """What temporal() returns and takes back as `history`: the accumulated colour `rgb` [h, w, 3], the accumulated second moment of the
+    luminance `m2` [h, w], the history length `len` [h, w] (f32; 0: none), and the frame's own guides `normal` and `depth`."""
+
+    def __init__(self, rgb, m2, len, normal, depth):
+        self.rgb, self.m2, self.len, self.normal, self.depth = rgb, m2, len, normal, depth
+
+    @property
+    def variance(self):
+        """max(0, m2 - lum(rgb)^2) [h, w]: the luminance variance the accumulated moments estimate (0 after one frame)."""
+        rgb = self.rgb
+        with np.errstate(all="ignore"):
+            lum = (np.float32(0.212671) * rgb[..., 0] + np.float32(0.715160) * rgb[..., 1]) + np.float32(0.072169) * rgb[..., 2]
+            return np.maximum(np.float32(0), self.m2 - lum * lum)
+
+
+def temporal(rgb, normal, depth, history, matrices, depth_tol=DEPTH_TOL, normal_tol=NORMAL_TOL, max_history=MAX_HISTORY, device=True):
+    """One frame of temporal accumulation.  rgb [h, w, 3], normal [h, w, 3] and depth [h, w] are the current frame and its
+    FeatureIntegrator guides; `history` is None (the first frame) or the TemporalFrame the previous call returned; `matrices` is
+    temporal_matrices(camera, prev_camera) (read only with a history, but always checked).  Returns a TemporalFrame.  device=True:
+    dr_temporal, on the GPU; device=False: dr_temporal_host, which needs none and writes the same bytes."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    normal = np.ascontiguousarray(normal, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or normal.shape != rgb.shape or depth.shape != rgb.shape[:2]:
+        raise ValueError("temporal: rgb and normal must be [h, w, 3] and depth [h, w] (got %r, %r, %r)" % (rgb.shape, normal.shape, depth.shape))
+    h, w = depth.shape
+    hist = [None] * 5
+    if history is not None:
+        hist = [np.ascontiguousarray(a, dtype=np.float32) for a in (history.rgb, history.m2, history.len, history.normal, history.depth)]
+        if hist[0].shape != rgb.shape or hist[3].shape != rgb.shape or any(a.shape != depth.shape for a in (hist[1], hist[2], hist[4])):
+            raise ValueError("temporal: the history is of another size (%r for %r)" % (hist[0].shape, rgb.shape))
+    p = temporal_params(matrices, depth_tol, normal_tol, max_history)
+    out = TemporalFrame(np.zeros_like(rgb), np.zeros_like(depth), np.zeros_like(depth), normal, depth)
+    lib = _abi.lib()
+    if device:
+        _abi.init(_abi._initialised if _abi._initialised is not None else 0)
+    fn = lib.dr_temporal if device else lib.dr_temporal_host
+    _abi.check(fn(rgb.ctypes.data, normal.ctypes.data, depth.ctypes.data, *[a.ctypes.data if a is not None else None for a in hist], w, h,
+                  C.byref(p), out.rgb.ctypes.data, out.m2.ctypes.data, out.len.ctypes.data))
+    return out
+
+
+def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_tol=DEPTH_TOL, normal_tol=NORMAL_TOL, max_history=MAX_HISTORY,
+                    **kw):
+    """Renders one frame per renderer -- one camera pose each, in the order of the animation -- with its beauty image and two
+    FeatureIntegrator images, `normal_channel` ("ns" or "ng") and "depth", as render_denoised does, and accumulates each into the history of
+    the frames before it with temporal().  Returns the list of frames: OutputImages whose rgb is the accumulated colour, or with denoise=True
+    atrous(accumulated, normal, depth, **kw); the parts stay on each as `noisy` (the frame's own render), `accumulated`, `normal`, `depth`,
+    `m2`, `len`, `variance` and `history` (the TemporalFrame).
+
+    Give each renderer's sampler its own seed.  The samplers are keyed by pixel and seed: two frames that share a seed draw the same sample
+    pattern in every pixel, so a surface that stays under one pixel is sampled with the same numbers again, the frames' errors are the same
+    error, and their mean is no better than one of them.  The guides are another matter: they are filtered over the sampler's positions too,
+    so where a pixel straddles a silhouette two seeds give two depths, and a static camera would lose its history there in every frame.
+    Every frame's guides are therefore rendered with a copy of its sampler that carries the first renderer's seed: at one pose the guides are
+    the same bytes whatever the beauty image's seed."""
+    who = "render_sequence"
+    if normal_channel not in ("ns", "ng"):
+        raise ValueError("%s: normal_channel must be ns or ng (got %r)" % (who, normal_channel))
+    renderers = list(renderers)
+    if kw and not denoise:
+        raise ValueError("%s: %s given without denoise=True" % (who, ", ".join(sorted(kw))))
+    for k, r in enumerate(renderers):
+        name = "renderers[%d]" % k
+        if isinstance(r.sampler, AdaptiveSampler):
+            raise ValueError("%s: the adaptive sampler is not supported (%s; the feature integrator refuses it)" % (who, name))
+        if r.tileCount > 1 or r.taskCount > 1:
+            raise ValueError("%s: tileCount > 1 and taskCount > 1 are not supported (%s has %d and %d): sharded accumulation is out of scope"
+                             % (who, name, r.tileCount, r.taskCount))
+        crop = tuple(r.camera.film.cropWindow)
+        if crop != (0.0, 1.0, 0.0, 1.0):
+            raise ValueError("%s: a crop window other than the whole film is not supported (%s has %r)" % (who, name, crop))
+        _camera_refusals(who, name + ".camera", r.camera)
+    mats = [temporal_matrices(r.camera, renderers[max(k - 1, 0)].camera) for k, r in enumerate(renderers)]
+
+    guide_seed = getattr(renderers[0].sampler, "seed", None) if renderers else None
+    frames, history = [], None
+    for r, m in zip(renderers, mats):
+        guide_sampler = r.sampler
+        if guide_seed is not None and getattr(guide_sampler, "seed", None) is not None:
+            guide_sampler = copy.copy(r.sampler)
+            guide_sampler.seed = guide_seed
+
+        def guide(channel):
+            return SamplerRenderer(guide_sampler, r.camera, FeatureIntegrator(channel), r.volumeIntegrator, taskNum=r.taskNum, taskCount=r.taskCount,
+                                   tileRank=r.tileRank, tileCount=r.tileCount, tileSize=r.tileSize).render(scene)
+        beauty = r.render(scene)
+        normal = guide(normal_channel).rgb
+        depth = np.ascontiguousarray(guide("depth").rgb[..., 0])
+        history = temporal(beauty.rgb, normal, depth, history, m, depth_tol=depth_tol, normal_tol=normal_tol, max_history=max_history)
+        rgb = atrous(history.rgb, normal, depth, **kw) if denoise else history.rgb
+        out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, rgb, beauty.film)
+        out.noisy, out.accumulated, out.normal, out.depth = beauty.rgb, history.rgb, normal, depth
+        out.m2, out.len, out.variance, out.history = history.m2, history.len, history.variance, history
+        frames.append(out)
+    return frames

@@ -578,6 +578,47 @@ int dr_upsample_device(const void* rgb_lo_dev, const void* normal_lo_dev, const 
                        const void* normal_dev, const void* depth_dev, const DrUpsampleParams* params, void* out_dev, void* scratch_dev,
                        uint64_t* scratch_bytes, void* hip_stream);
 
+/* Temporal accumulation with reprojection (the temporal half of Schied et al. 2017): the frames of a camera animation
+ * share their samples where a surface stays visible.  A call reads the current frame -- rgb[h][w][3], normal[h][w][3] as the feature integrator
+ * encodes it and depth[h][w], the ray parameter t along the normalised camera ray -- and the history the previous call left: h_rgb[h][w][3],
+ * h_m2[h][w] (the accumulated second moment of the luminance), h_len[h][w] (the history length as f32; 0: none) and the previous frame's
+ * guides h_normal / h_depth.  The five history pointers may be NULL together: the first frame.  It writes out_rgb, out_m2 and out_len, the next
+ * call's h_rgb, h_m2 and h_len; the current normal and depth are the next call's h_normal and h_depth (the caller hands them over, nothing is
+ * copied).  A pixel whose colour, normal and depth are finite and whose depth is > 0 is taken along its camera ray to the point at t (f64),
+ * through cur_to_prev to the previous camera's space and through prev_to_raster to the previous raster; (u, v) is rounded to f32 and snapped to
+ * 1/256 of a pixel; the 2 x 2 previous pixels around it that lie inside the image, have h_len > 0 and finite values, a depth within
+ * depth_tol * tz of the point's distance tz from the previous camera and an encoded normal within normal_tol (squared distance) of the pixel's
+ * give the history as their bilinear mean, and out = hist + (cur - hist) / N with N = min(len + 1, max_history).  Every other pixel restarts:
+ * out_rgb = rgb bit for bit, out_m2 = lum^2, out_len = 1 (m2 = 0 where lum^2 is not finite, len = 0 where the colour is not).  The matrices are
+ * row-major and are not inverted or composed here.  f64 geometry, f32 blending, one rounding per operator: the entry points below write the
+ * same bytes. */
+typedef struct DrTemporalParams {
+  double raster_to_camera[16]; /* the current camera's */
+  double cur_to_prev[16];      /* current camera space -> previous camera space; affine: the last row is not read */
+  double prev_to_raster[16];   /* previous camera space -> previous raster; projective: rows 0, 1 and 3 are read */
+  float depth_tol;             /* relative; finite, >= 0 */
+  float normal_tol;            /* squared distance of the encoded normals; finite, >= 0 */
+  int32_t max_history;         /* 1..4096: the blend weight never falls below 1 / max_history */
+  uint32_t reserved;           /* 0 */
+} DrTemporalParams; /* 400 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer other than the all-NULL history, a history that is only partly NULL, w or h < 1,
+ * w * h >= 2^31, a tolerance that is negative or not finite, max_history outside 1..4096, a matrix element that is not finite, an output
+ * overlapping an input or another output.  dr_temporal_check states those of the parameters and the size without an image. */
+int dr_temporal_check(const DrTemporalParams* params, int32_t w, int32_t h);
+/* dr_temporal_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_temporal_host(const float* rgb, const float* normal, const float* depth, const float* h_rgb, const float* h_m2, const float* h_len,
+                     const float* h_normal, const float* h_depth, int32_t w, int32_t h, const DrTemporalParams* params, float* out_rgb,
+                     float* out_m2, float* out_len);
+/* The same ON THE GPU (dr_temporal_device.hip), host buffers: uploads, one launch, copies back.  Needs dr_init. */
+int dr_temporal(const float* rgb, const float* normal, const float* depth, const float* h_rgb, const float* h_m2, const float* h_len,
+                const float* h_normal, const float* h_depth, int32_t w, int32_t h, const DrTemporalParams* params, float* out_rgb, float* out_m2,
+                float* out_len);
+/* The same on device buffers, asynchronous on the given hipStream_t: one kernel launch.  It needs no scratch buffer, so there is no size
+ * query; the parameters are copied at the call and may change as soon as it returns. */
+int dr_temporal_device(const void* rgb_dev, const void* normal_dev, const void* depth_dev, const void* h_rgb_dev, const void* h_m2_dev,
+                       const void* h_len_dev, const void* h_normal_dev, const void* h_depth_dev, int32_t w, int32_t h,
+                       const DrTemporalParams* params, void* out_rgb_dev, void* out_m2_dev, void* out_len_dev, void* hip_stream);
+
 /* The display transform: rgb[h][w][3], row-major f32 linear radiance, becomes out[h][w][4], bytes R, G, B, A = 255.
  * Per pixel: a non-finite channel makes the pixel invalid (it is no sample of the histogram and comes out as invalid_rgba); a negative channel
  * is taken as 0; the channels are multiplied by the exposure scale, go through the tone curve and are encoded to a byte each.  The scale is
@@ -875,7 +916,9 @@ const char* dr_version(void);
  * DrDisplayParams, that only its seven new entry points read -- dr_display_check, dr_display_table, dr_display_host, dr_display,
  * dr_display_device, dr_display_exposure_host and dr_display_exposure; and the NURBS shape: one new struct, DrNurbsPatch, that only its
  * two new entry points read -- dr_nurbs_dice and dr_nurbs_dice_device; and the upsampler: one new struct, DrUpsampleParams, that only its
- * four new entry points read -- dr_upsample_check, dr_upsample_host, dr_upsample and dr_upsample_device). */
+ * four new entry points read -- dr_upsample_check, dr_upsample_host, dr_upsample and dr_upsample_device; and temporal accumulation: one new
+ * struct, DrTemporalParams, that only its four new entry points read -- dr_temporal_check, dr_temporal_host, dr_temporal and
+ * dr_temporal_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -1011,6 +1054,12 @@ DR_ABI_SIZE(DrUpsampleParams, 16);
 DR_ABI_OFFSET(DrUpsampleParams, taps, 4);
 DR_ABI_OFFSET(DrUpsampleParams, k_normal, 8);
 DR_ABI_OFFSET(DrUpsampleParams, k_depth, 12);
+DR_ABI_SIZE(DrTemporalParams, 400);
+DR_ABI_OFFSET(DrTemporalParams, cur_to_prev, 128);
+DR_ABI_OFFSET(DrTemporalParams, prev_to_raster, 256);
+DR_ABI_OFFSET(DrTemporalParams, depth_tol, 384);
+DR_ABI_OFFSET(DrTemporalParams, normal_tol, 388);
+DR_ABI_OFFSET(DrTemporalParams, max_history, 392);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,16 @@ const int OFF_DrUpsampleParams_factor = 0;
 const int OFF_DrUpsampleParams_taps = 4;
 const int OFF_DrUpsampleParams_k_normal = 8;
 const int OFF_DrUpsampleParams_k_depth = 12;
+// DrTemporalParams (temporal accumulation with reprojection, DESIGN.md 2.23): three row-major f64 4 x 4 matrices -- the current camera's
+// raster-to-camera, current camera space to previous camera space, previous camera space to previous raster --, then f32 depth_tol (relative),
+// f32 normal_tol (squared distance of the encoded normals), int32 max_history (1..4096) and a reserved uint32 that is 0
+const int SIZEOF_DrTemporalParams = 400;
+const int OFF_DrTemporalParams_raster_to_camera = 0;
+const int OFF_DrTemporalParams_cur_to_prev = 128;
+const int OFF_DrTemporalParams_prev_to_raster = 256;
+const int OFF_DrTemporalParams_depth_tol = 384;
+const int OFF_DrTemporalParams_normal_tol = 388;
+const int OFF_DrTemporalParams_max_history = 392;
 // DrNurbsPatch (one NURBS patch, DESIGN.md 2.21): per direction int32 n, int32 order, the address of n + order f32 knots and the f32 range;
 // the address of the nu * nv control points (3 floats each, or 4 when homogeneous is 1); uint32 dice rates (0: 30)
 const int SIZEOF_DrNurbsPatch = 72;
@@ -326,6 +336,14 @@ typedef _UpsampleC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Floa
     Pointer<Float>);
 typedef _UpsampleD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Float>, Pointer<Float>, Pointer<Uint8>,
     Pointer<Float>);
+// dr_temporal (temporal accumulation on the GPU, host buffers; DESIGN.md 2.23): rgb[h][w][3], normal[h][w][3], depth[h][w], the history
+// h_rgb[h][w][3], h_m2[h][w], h_len[h][w], h_normal[h][w][3], h_depth[h][w] (all five nullptr on the first frame), w, h, DrTemporalParams
+// (400 bytes, the OFF_DrTemporalParams_* offsets above), out_rgb[h][w][3], out_m2[h][w], out_len[h][w].  (Signature only, never compiled,
+// like the rest.)
+typedef _TemporalC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>,
+    Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+typedef _TemporalD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>,
+    Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 // dr_display (the display transform on the GPU, host buffers; DESIGN.md 2.20): rgb[h][w][3], w, h, DrDisplayParams (32 bytes, the
 // OFF_DrDisplayParams_* offsets above), out[h][w][4] bytes R, G, B, A.  (Signature only, never compiled, like the rest.)
 typedef _DisplayC = Int32 Function(Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Uint8>);
@@ -400,6 +418,9 @@ class HipSamplerRenderer extends Renderer {
   /// The joint bilateral upsampler: an image rendered at 1/2 or 1/4 of the resolution per axis, brought to the full resolution under
   /// full-resolution FeatureIntegrator normal and depth images (after dr_init).
   static final _UpsampleD upsample = _lib.lookupFunction<_UpsampleC, _UpsampleD>('dr_upsample');
+  /// Temporal accumulation: one frame of a camera animation blended into the history of the frames before it, where the previous frame
+  /// saw the same surface (after dr_init).  The host composes the three matrices of DrTemporalParams from the two cameras.
+  static final _TemporalD temporal = _lib.lookupFunction<_TemporalC, _TemporalD>('dr_temporal');
   /// The display transform: linear f32 radiance to RGBA8 through exposure, a tone curve and an 8-bit encode (after dr_init).
   static final _DisplayD displayImage = _lib.lookupFunction<_DisplayC, _DisplayD>('dr_display');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
