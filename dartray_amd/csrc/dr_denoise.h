@@ -11,23 +11,12 @@
 #ifndef DR_DENOISE_H
 #define DR_DENOISE_H
 
-#include <stddef.h>
-#include <stdint.h>
+#include <utility>
+#include <vector>
 
-#include "../../include/dartray_hip.h"
-
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define DR_DN_HD __host__ __device__ inline
-#else
-#define DR_DN_HD inline
-#endif
+#include "dr_image.h"
 
 #define DR_DN_MAX_ITERATIONS 8
-
-struct alignas(16) DnTexel {
-  float x, y, z, w;
-};
 
 // h[a] * h[b] of h = [1/16, 1/4, 3/8, 1/4, 1/16], row dy + 2, column dx + 2: multiples of 1/256, exact in f32
 DR_DN_HD float dn_tap(int row, int col) {
@@ -37,28 +26,6 @@ DR_DN_HD float dn_tap(int row, int col) {
                                     {4 / 256.f, 16 / 256.f, 24 / 256.f, 16 / 256.f, 4 / 256.f},
                                     {1 / 256.f, 4 / 256.f, 6 / 256.f, 4 / 256.f, 1 / 256.f}};
   return H[row][col];
-}
-
-DR_DN_HD bool dn_finite(float v) {
-  uint32_t u;
-  __builtin_memcpy(&u, &v, sizeof(u));
-  return (u & 0x7f800000u) != 0x7f800000u;
-}
-
-// (a - b)^2 summed over three components, left to right
-DR_DN_HD float dn_dist2(const DnTexel& a, const DnTexel& b) {
-  const float dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
-  return ((dx * dx) + (dy * dy)) + (dz * dz);
-}
-
-DR_DN_HD DnTexel dn_pack_colour(const float* rgb, const float* normal, const float* depth, size_t p) {
-  const float r = rgb[3 * p], g = rgb[3 * p + 1], b = rgb[3 * p + 2];
-  const bool valid = dn_finite(r) && dn_finite(g) && dn_finite(b) && dn_finite(normal[3 * p]) && dn_finite(normal[3 * p + 1]) &&
-                     dn_finite(normal[3 * p + 2]) && dn_finite(depth[p]);
-  return DnTexel{r, g, b, valid ? 1.0f : 0.0f};
-}
-DR_DN_HD DnTexel dn_pack_guide(const float* normal, const float* depth, size_t p) {
-  return DnTexel{normal[3 * p], normal[3 * p + 1], normal[3 * p + 2], depth[p]};
 }
 
 // One pixel of one level: step s, sharpness kc (this level's), kn, kz.  Every tap's coordinates are checked against the image
@@ -102,8 +69,7 @@ inline float dn_level_kc(float k_color, int i) { return (float)((double)k_color 
 // The arguments every entry point checks the same way: NULL, or the refusal's text
 inline const char* dn_check(int32_t w, int32_t h, const DrDenoiseParams* p) {
   if (!p) return "a null pointer";
-  if (w < 1 || h < 1) return "w and h must be at least 1";
-  if ((int64_t)w * (int64_t)h >= ((int64_t)1 << 31)) return "the image has 2^31 or more pixels";
+  if (const char* why = img_check_dims(w, h)) return why;
   if (p->iterations < 1 || p->iterations > DR_DN_MAX_ITERATIONS) return "iterations must be in 1..8";
   const float k[3] = {p->k_color, p->k_normal, p->k_depth};
   for (int i = 0; i < 3; ++i)
@@ -112,17 +78,54 @@ inline const char* dn_check(int32_t w, int32_t h, const DrDenoiseParams* p) {
   return nullptr;
 }
 
-// [a, a + na) and [b, b + nb) share a byte
-inline bool dn_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
 // dn_check, the null pointers and the overlap of `out` with an input, as a refusal (`who` prefixes the message).  dr_denoise_host.cpp.
 int dn_check_images(const char* who, const void* rgb, const void* normal, const void* depth, int32_t w, int32_t h,
                     const DrDenoiseParams* params, const void* out);
 
-#include <string>
-int dr_fail(int code, const std::string& msg);  // dr_api.hip: sets dr_last_error()
+// What sets the a-trous filter and its pair form (dr_denoise_pair.h) apart, as the level loop of the host (dn_levels_host) and of the
+// device (dr_denoise_device.hip) takes it: the images a call packs, one level's scalars, the per-pixel function, and whether the last
+// level's w goes to a variance image.  Here w is the validity flag and no output.
+struct DnRule {
+  typedef DrDenoiseParams Params;
+  typedef DnInputs Inputs;
+  static constexpr bool kVariance = false;
+  float kc, kn, kz;
+  static DnRule level(const Params& p, int i) { return DnRule{dn_level_kc(p.k_color, i), p.k_normal, p.k_depth}; }
+  DR_DN_HD DnTexel pixel(const DnTexel* colour, const DnTexel* guide, int32_t w, int32_t h, int32_t x, int32_t y, int32_t s) const {
+    return dn_pixel(colour, guide, w, h, x, y, s, kc, kn, kz);
+  }
+};
+
+// The levels of one call on the host, on images that the caller has checked: a serial loop over Rule's per-pixel function.  The levels
+// take turns between two colour planes; the last one writes out [h][w][3] and, where the rule has one and out_var is set, [h][w].
+template <class Rule>
+void dn_levels_host(const typename Rule::Inputs& in, int32_t w, int32_t h, const typename Rule::Params& prm, float* out, float* out_var) {
+  const size_t n = (size_t)w * (size_t)h;
+  std::vector<DnTexel> guide(n), a(n), b(prm.iterations > 1 ? n : 0);
+  for (size_t p = 0; p < n; ++p) {
+    a[p] = in.colour(p);
+    guide[p] = in.guide(p);
+  }
+  DnTexel* src = a.data();
+  DnTexel* dst = b.data();
+  for (int i = 0; i < prm.iterations; ++i) {
+    const bool last = i == prm.iterations - 1;
+    const Rule rule = Rule::level(prm, i);
+    for (int32_t y = 0; y < h; ++y)
+      for (int32_t x = 0; x < w; ++x) {
+        const DnTexel t = rule.pixel(src, guide.data(), w, h, x, y, (int32_t)(1 << i));
+        const size_t p = (size_t)y * (size_t)w + (size_t)x;
+        if (last) {
+          out[3 * p] = t.x;
+          out[3 * p + 1] = t.y;
+          out[3 * p + 2] = t.z;
+          if (Rule::kVariance && out_var) out_var[p] = t.w;
+        } else {
+          dst[p] = t;
+        }
+      }
+    std::swap(src, dst);
+  }
+}
 
 #endif

@@ -1,91 +1,62 @@
-// dr_denoise_device.hip -- the edge-avoiding a-trous filter ON THE GPU: dr_denoise_atrous (host buffers) and
-// dr_denoise_atrous_device (device buffers, asynchronous on a stream).
-//   k_denoise_pack     lane = pixel: the three input images become two planes of 16-byte texels, colour = (r, g, b, valid) and
-//                      guide = (nx, ny, nz, z), so that a tap is two 16-byte loads
-//   k_denoise_atrous   lane = pixel, one launch per level: 64 x 4 tiles whose rows are contiguous in x -- a wave is 64 neighbours of
-//                      one image row, and its tap at dx * s is the same 1 KiB run shifted, so every tap load stays coalesced at every
-//                      step.  The levels take turns between two colour planes; the last one writes [h][w][3].
-// The per-pixel rule is dr_denoise.h's, the one the host loop runs (dr_denoise_host.cpp): the outputs are byte-identical
-// (tests/test_gpu_denoise.py).  Every tap's coordinates are checked against w and h before its loads (dn_pixel); a workgroup walks the
-// tiles t = blockIdx.x, + gridDim.x, ... so that no image shape needs more workgroups than a launch may have, and a lane whose pixel
-// lies outside the image skips the tile before any access.  No LDS: a level's 25 taps per pixel hit lines its neighbours in the tile and
-// the tiles around it have just brought into L2, and the traffic that reaches HBM is the 32 B read + 16 B written per pixel.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <string>
-
-#include "../../include/dartray_hip.h"
-
-#include "dr_denoise.h"
+// dr_denoise_device.hip -- the two a-trous filters ON THE GPU: the edge-avoiding one, dr_denoise_atrous (host buffers)
+// and dr_denoise_atrous_device (device buffers, asynchronous on a stream), and the variance-guided one over two half renders (DESIGN.md
+// 2.19), dr_denoise_pair and dr_denoise_pair_device.  One pack kernel and one level kernel, each compiled once per rule (DnRule of
+// dr_denoise.h, DnpRule of dr_denoise_pair.h):
+//   k_image_pack<Inputs>     dr_image_device.h.  The pair filter's colour is (mean r, g, b, variance or -1)
+//   k_denoise_level<Rule>    lane = pixel, one launch per level: 64 x 4 tiles whose rows are contiguous in x -- a wave is 64 neighbours of
+//                            one image row, and its tap at dx * s is the same 1 KiB run shifted, so every tap load stays coalesced at every
+//                            step; the nine loads of the pair filter's variance prefilter are the same run shifted by one pixel and one
+//                            row.  The levels take turns between two colour planes; the last one writes [h][w][3] and, for the pair filter
+//                            when asked, [h][w].
+// The per-pixel rules are the ones the host loop runs (dn_levels_host): the outputs are byte-identical (tests/test_gpu_denoise.py,
+// tests/test_gpu_denoise_pair.py).  Every tap's coordinates are checked against w and h before its loads (dn_pixel, dnp_pixel); the tile
+// walk is dr_image_device.h's.  No LDS: a level's 25 taps per pixel hit lines its neighbours in the tile and the tiles around it have just
+// brought into L2, and the traffic that reaches HBM is the 32 B read + 16 B written per pixel.
+#include "dr_denoise_pair.h"
+#include "dr_image_device.h"
 
 namespace {
 
-#define DR_DN_TILE_X 64  // one wave = one row of the tile
-#define DR_DN_TILE_Y 4
-#define DR_DN_MAX_GRID (1u << 20)
-
-__global__ void __launch_bounds__(256) k_denoise_pack(const float* rgb, const float* normal, const float* depth, uint64_t n, DnTexel* colour,
-                                                     DnTexel* guide) {
-  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < n; p += (uint64_t)gridDim.x * 256u) {
-    colour[p] = dn_pack_colour(rgb, normal, depth, (size_t)p);
-    guide[p] = dn_pack_guide(normal, depth, (size_t)p);
-  }
-}
-
-// dst: the next level's colour plane, or out3: the image (the last level); exactly one is set
-__global__ void __launch_bounds__(DR_DN_TILE_X* DR_DN_TILE_Y) k_denoise_atrous(const DnTexel* colour, const DnTexel* guide, int32_t w, int32_t h,
-                                                                              int32_t s, float kc, float kn, float kz, uint64_t tilesX,
-                                                                              uint64_t ntiles, DnTexel* dst, float* out3) {
+// dst: the next level's colour plane; or out3: the image, with outv: the variance image or NULL (the last level)
+template <class Rule>
+__global__ void __launch_bounds__(DR_IMG_TILE_X* DR_IMG_TILE_Y) k_denoise_level(const DnTexel* colour, const DnTexel* guide, int32_t w, int32_t h,
+                                                                               int32_t s, Rule rule, uint64_t tilesX, uint64_t ntiles,
+                                                                               DnTexel* dst, float* out3, float* outv) {
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const uint64_t x = (t % tilesX) * DR_DN_TILE_X + threadIdx.x, y = (t / tilesX) * DR_DN_TILE_Y + threadIdx.y;
-    if (x >= (uint64_t)w || y >= (uint64_t)h) continue;
-    const DnTexel r = dn_pixel(colour, guide, w, h, (int32_t)x, (int32_t)y, s, kc, kn, kz);
+    uint64_t x, y;
+    if (!img_tile_pixel(t, tilesX, w, h, &x, &y)) continue;
+    const DnTexel r = rule.pixel(colour, guide, w, h, (int32_t)x, (int32_t)y, s);
     const size_t p = (size_t)y * (size_t)w + (size_t)x;
     if (out3) {
       out3[3 * p] = r.x;
       out3[3 * p + 1] = r.y;
       out3[3 * p + 2] = r.z;
+      if (Rule::kVariance && outv) outv[p] = r.w;
     } else {
       dst[p] = r;
     }
   }
 }
 
-template <class T>
-struct Buf {
-  T* p = nullptr;
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-};
-#define ST(x)                                                                                                  \
-  do {                                                                                                         \
-    hipError_t e_ = (x);                                                                                       \
-    if (e_ != hipSuccess) return dr_fail(DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
+// the guide plane and the two colour planes the levels take turns between
 uint64_t scratch_need(int32_t w, int32_t h) { return 3ull * sizeof(DnTexel) * (uint64_t)w * (uint64_t)h; }
 
 // The launches of one call, on device buffers that the caller has checked
-int run(const char* who, const float* rgb, const float* normal, const float* depth, int32_t w, int32_t h, const DrDenoiseParams& prm, float* out,
+template <class Rule>
+int run(const char* who, const typename Rule::Inputs& in, int32_t w, int32_t h, const typename Rule::Params& prm, float* out, float* out_var,
         void* scratch, hipStream_t s) {
   const uint64_t n = (uint64_t)w * (uint64_t)h;
   DnTexel* guide = (DnTexel*)scratch;
   DnTexel* src = guide + n;
   DnTexel* dst = src + n;
-  const unsigned packGrid = (unsigned)std::min<uint64_t>((n + 255u) / 256u, DR_DN_MAX_GRID);
-  hipLaunchKernelGGL(k_denoise_pack, dim3(packGrid), dim3(256), 0, s, rgb, normal, depth, n, src, guide);
-  ST(hipGetLastError());
-  const uint64_t tilesX = ((uint64_t)w + DR_DN_TILE_X - 1) / DR_DN_TILE_X, tilesY = ((uint64_t)h + DR_DN_TILE_Y - 1) / DR_DN_TILE_Y;
-  const uint64_t ntiles = tilesX * tilesY;
-  const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, DR_DN_MAX_GRID);
+  const int rc = img_pack(who, in, n, src, guide, s);
+  if (rc != DR_OK) return rc;
+  const ImgTiles tl = img_tiles(w, h);
   for (int i = 0; i < prm.iterations; ++i) {
     const bool last = i == prm.iterations - 1;
-    hipLaunchKernelGGL(k_denoise_atrous, dim3(grid), dim3(DR_DN_TILE_X, DR_DN_TILE_Y), 0, s, (const DnTexel*)src, (const DnTexel*)guide, w, h,
-                       (int32_t)(1 << i), dn_level_kc(prm.k_color, i), prm.k_normal, prm.k_depth, tilesX, ntiles, last ? (DnTexel*)nullptr : dst,
-                       last ? out : (float*)nullptr);
+    hipLaunchKernelGGL(k_denoise_level<Rule>, dim3(tl.grid), dim3(DR_IMG_TILE_X, DR_IMG_TILE_Y), 0, s, (const DnTexel*)src, (const DnTexel*)guide, w,
+                       h, (int32_t)(1 << i), Rule::level(prm, i), tl.tilesX, tl.ntiles, last ? (DnTexel*)nullptr : dst,
+                       last ? out : (float*)nullptr, last ? out_var : (float*)nullptr);
     ST(hipGetLastError());
     std::swap(src, dst);
   }
@@ -98,33 +69,23 @@ extern "C" int dr_denoise_atrous_device(const void* rgb_dev, const void* normal_
                                         const DrDenoiseParams* params, void* out_dev, void* scratch_dev, uint64_t* scratch_bytes,
                                         void* hip_stream) {
   const char* who = "dr_denoise_atrous_device";
-  const std::string pre = std::string(who) + ": ";
-  if (!scratch_bytes || !params) return dr_fail(DR_ERR_INVALID, pre + "a null pointer");
-  if (!scratch_dev) {  // the size query
-    if (const char* why = dn_check(w, h, params)) return dr_fail(DR_ERR_INVALID, pre + why);
-    *scratch_bytes = scratch_need(w, h);
-    return DR_OK;
-  }
-  const int rc = dn_check_images(who, rgb_dev, normal_dev, depth_dev, w, h, params, out_dev);
+  if (!scratch_bytes || !params) return img_refuse(who, "a null pointer");
+  int rc = scratch_dev ? dn_check_images(who, rgb_dev, normal_dev, depth_dev, w, h, params, out_dev) : img_refuse(who, dn_check(w, h, params));
   if (rc != DR_OK) return rc;
   const uint64_t need = scratch_need(w, h);
-  if (*scratch_bytes < need) return dr_fail(DR_ERR_INVALID, pre + "the scratch buffer is too small");
-  if ((uintptr_t)scratch_dev % sizeof(DnTexel) != 0) return dr_fail(DR_ERR_INVALID, pre + "the scratch buffer is not 16-byte aligned");
+  if (img_scratch(who, scratch_dev, scratch_bytes, need, &rc)) return rc;
   const size_t n = (size_t)w * (size_t)h, f = sizeof(float);
-  if (dn_overlap(out_dev, 3 * n * f, scratch_dev, (size_t)need)) return dr_fail(DR_ERR_INVALID, pre + "out overlaps the scratch buffer");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return dr_fail(DR_ERR_NO_DEVICE, pre + "called before dr_init");
-  return run(who, (const float*)rgb_dev, (const float*)normal_dev, (const float*)depth_dev, w, h, *params, (float*)out_dev, scratch_dev,
-             (hipStream_t)hip_stream);
+  if (dn_overlap(out_dev, 3 * n * f, scratch_dev, (size_t)need)) return img_refuse(who, "out overlaps the scratch buffer");
+  if ((rc = img_device_ready(who)) != DR_OK) return rc;
+  return run<DnRule>(who, DnInputs{(const float*)rgb_dev, (const float*)normal_dev, (const float*)depth_dev}, w, h, *params, (float*)out_dev,
+                     nullptr, scratch_dev, (hipStream_t)hip_stream);
 }
 
 extern "C" int dr_denoise_atrous(const float* rgb, const float* normal, const float* depth, int32_t w, int32_t h, const DrDenoiseParams* params,
                                  float* out) {
   const char* who = "dr_denoise_atrous";
-  const int rc = dn_check_images(who, rgb, normal, depth, w, h, params, out);
-  if (rc != DR_OK) return rc;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return dr_fail(DR_ERR_NO_DEVICE, std::string(who) + ": called before dr_init");
+  int rc = dn_check_images(who, rgb, normal, depth, w, h, params, out);
+  if (rc != DR_OK || (rc = img_device_ready(who)) != DR_OK) return rc;
   const size_t n = (size_t)w * (size_t)h;
   Buf<float> dRgb, dNormal, dDepth, dOut;
   Buf<DnTexel> scratch;
@@ -134,12 +95,56 @@ extern "C" int dr_denoise_atrous(const float* rgb, const float* normal, const fl
   ST(dOut.alloc(3 * n));
   ST(scratch.alloc(3 * n));
   hipStream_t s = 0;
-  ST(hipMemcpyAsync(dRgb.p, rgb, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
-  ST(hipMemcpyAsync(dNormal.p, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
-  ST(hipMemcpyAsync(dDepth.p, depth, n * sizeof(float), hipMemcpyHostToDevice, s));
-  const int rc2 = run(who, dRgb.p, dNormal.p, dDepth.p, w, h, *params, dOut.p, scratch.p, s);
-  if (rc2 != DR_OK) return rc2;
-  ST(hipMemcpyAsync(out, dOut.p, 3 * n * sizeof(float), hipMemcpyDeviceToHost, s));
+  ST(dRgb.upload(rgb, 3 * n, s));
+  ST(dNormal.upload(normal, 3 * n, s));
+  ST(dDepth.upload(depth, n, s));
+  if ((rc = run<DnRule>(who, DnInputs{dRgb.p, dNormal.p, dDepth.p}, w, h, *params, dOut.p, nullptr, scratch.p, s)) != DR_OK) return rc;
+  ST(dOut.download(out, 3 * n, s));
+  ST(hipStreamSynchronize(s));
+  return DR_OK;
+}
+
+extern "C" int dr_denoise_pair_device(const void* a_dev, const void* b_dev, const void* normal_dev, const void* depth_dev, int32_t w, int32_t h,
+                                      const DrDenoisePairParams* params, void* out_dev, void* out_var_dev, void* scratch_dev,
+                                      uint64_t* scratch_bytes, void* hip_stream) {
+  const char* who = "dr_denoise_pair_device";
+  if (!scratch_bytes || !params) return img_refuse(who, "a null pointer");
+  int rc = scratch_dev ? dnp_check_images(who, a_dev, b_dev, normal_dev, depth_dev, w, h, params, out_dev, out_var_dev)
+                       : img_refuse(who, dnp_check(w, h, params));
+  if (rc != DR_OK) return rc;
+  const uint64_t need = scratch_need(w, h);
+  if (img_scratch(who, scratch_dev, scratch_bytes, need, &rc)) return rc;
+  const size_t n = (size_t)w * (size_t)h, f = sizeof(float);
+  if (dn_overlap(out_dev, 3 * n * f, scratch_dev, (size_t)need)) return img_refuse(who, "out overlaps the scratch buffer");
+  if (out_var_dev && dn_overlap(out_var_dev, n * f, scratch_dev, (size_t)need)) return img_refuse(who, "out_var overlaps the scratch buffer");
+  if ((rc = img_device_ready(who)) != DR_OK) return rc;
+  return run<DnpRule>(who, DnpInputs{(const float*)a_dev, (const float*)b_dev, (const float*)normal_dev, (const float*)depth_dev}, w, h, *params,
+                      (float*)out_dev, (float*)out_var_dev, scratch_dev, (hipStream_t)hip_stream);
+}
+
+extern "C" int dr_denoise_pair(const float* a, const float* b, const float* normal, const float* depth, int32_t w, int32_t h,
+                               const DrDenoisePairParams* params, float* out, float* out_var) {
+  const char* who = "dr_denoise_pair";
+  int rc = dnp_check_images(who, a, b, normal, depth, w, h, params, out, out_var);
+  if (rc != DR_OK || (rc = img_device_ready(who)) != DR_OK) return rc;
+  const size_t n = (size_t)w * (size_t)h;
+  Buf<float> dA, dB, dNormal, dDepth, dOut, dVar;
+  Buf<DnTexel> scratch;
+  ST(dA.alloc(3 * n));
+  ST(dB.alloc(3 * n));
+  ST(dNormal.alloc(3 * n));
+  ST(dDepth.alloc(n));
+  ST(dOut.alloc(3 * n));
+  if (out_var) ST(dVar.alloc(n));
+  ST(scratch.alloc(3 * n));
+  hipStream_t s = 0;
+  ST(dA.upload(a, 3 * n, s));
+  ST(dB.upload(b, 3 * n, s));
+  ST(dNormal.upload(normal, 3 * n, s));
+  ST(dDepth.upload(depth, n, s));
+  if ((rc = run<DnpRule>(who, DnpInputs{dA.p, dB.p, dNormal.p, dDepth.p}, w, h, *params, dOut.p, dVar.p, scratch.p, s)) != DR_OK) return rc;
+  ST(dOut.download(out, 3 * n, s));
+  if (out_var) ST(dVar.download(out_var, n, s));
   ST(hipStreamSynchronize(s));
   return DR_OK;
 }

@@ -4,13 +4,13 @@
 // film/image_film.dart:53-58 and :174-177).  The per-pixel rules, the histogram bin, the exposure pick and the parameter check, written once
 // for the host loop (dr_display_host.cpp) and the device kernels (dr_display_device.hip).
 //
-// Arithmetic: dr_denoise.h's -- + - * / and comparisons in f32, one operation and one rounding per operator, in the order DESIGN.md 2.20
+// Arithmetic: dr_image.h's -- + - * / and comparisons in f32, one operation and one rounding per operator, in the order DESIGN.md 2.20
 // writes them (the reference encode alone widens to f64 for one product and its floor, as the reference does).  Nothing transcendental runs
 // per pixel: every pow is spent on the host, once, in the 256-word table of dsp_fill_table (dr_display_host.cpp).
 #ifndef DR_DISPLAY_H
 #define DR_DISPLAY_H
 
-#include "dr_denoise.h"
+#include "dr_image.h"
 
 #define DR_DISPLAY_TABLE 256  // words of an encode table
 
@@ -29,9 +29,6 @@ DR_DN_HD uint32_t dsp_bits(float f) {
   return u;
 }
 
-// the pair denoiser's luminance (dnp_lum): the same weights in the same order
-DR_DN_HD float dsp_lum(float r, float g, float b) { return (0.212671f * r + 0.715160f * g) + 0.072169f * b; }
-
 DR_DN_HD bool dsp_valid(float r, float g, float b) { return dn_finite(r) && dn_finite(g) && dn_finite(b); }
 
 DR_DN_HD float dsp_floor0(float c) { return c < 0.0f ? 0.0f : c; }
@@ -41,7 +38,7 @@ DR_DN_HD float dsp_floor0(float c) { return c < 0.0f ? 0.0f : c; }
 // the three leading bits of the mantissa.
 DR_DN_HD uint32_t dsp_bin(float r, float g, float b) {
   if (!dsp_valid(r, g, b)) return DR_DISPLAY_BINS;
-  const uint32_t u = dsp_bits(dsp_lum(dsp_floor0(r), dsp_floor0(g), dsp_floor0(b)));
+  const uint32_t u = dsp_bits(img_lum(dsp_floor0(r), dsp_floor0(g), dsp_floor0(b)));
   return (u >= 0x00800000u && u < 0x7f800000u) ? (u >> 20) : DR_DISPLAY_BINS;
 }
 
@@ -88,7 +85,7 @@ DR_DN_HD uint32_t dsp_pixel(const uint32_t* table, const DrDisplayParams& p, flo
   g = dsp_floor0(g) * scale;
   b = dsp_floor0(b) * scale;
   if (p.curve == DR_TONE_REINHARD) {
-    const float y = dsp_lum(r, g, b);
+    const float y = img_lum(r, g, b);
     if (y == 0.0f) {
       r = g = b = 0.0f;
     } else {
@@ -115,9 +112,7 @@ inline const char* dsp_check(const DrDisplayParams* p, int32_t w, int32_t h) {
   if (!dn_finite(p->exposure) || !(p->exposure > 0.0f)) return "exposure must be finite and positive";
   if (!dn_finite(p->key) || !(p->key > 0.0f)) return "key must be finite and positive";
   if (!dn_finite(p->inv_white2) || p->inv_white2 < 0.0f) return "inv_white2 must be finite and not negative";
-  if (w < 1 || h < 1) return "w and h must be at least 1";
-  if ((int64_t)w * (int64_t)h >= ((int64_t)1 << 31)) return "the image has 2^31 or more pixels";
-  return nullptr;
+  return img_check_dims(w, h);
 }
 
 // dr_display_host.cpp.  The table of an encode (valid for the process's life; filled once), and the checks of the entry points that take

@@ -12,14 +12,8 @@
 //                      is an argument (manual exposure, where the two kernels above do not run)
 // The per-pixel rules are dr_display.h's, the ones the host loop runs (dr_display_host.cpp): the outputs are byte-identical
 // (tests/test_gpu_display.py).  Every pixel index is checked against n before its loads.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <string>
-
-#include "../../include/dartray_hip.h"
-
 #include "dr_display.h"
+#include "dr_image_device.h"
 
 #ifndef DR_DISPLAY_HIST_COMBINE
 #define DR_DISPLAY_HIST_COMBINE 1  // 0: every lane its own LDS atomic (tools/measure_display.py builds that variant beside this one)
@@ -105,20 +99,6 @@ __global__ void __launch_bounds__(DR_DSP_BLOCK) k_display_encode(const float* rg
     out[p] = dsp_pixel(lut, prm, scale, rgb[3 * p], rgb[3 * p + 1], rgb[3 * p + 2]);
 }
 
-template <class T>
-struct Buf {
-  T* p = nullptr;
-  hipError_t alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)); }
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-};
-#define ST(x)                                                                                          \
-  do {                                                                                                 \
-    hipError_t e_ = (x);                                                                               \
-    if (e_ != hipSuccess) return dr_fail(DR_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
 unsigned grid_for(uint64_t n, unsigned cap) { return (unsigned)std::min<uint64_t>((n + DR_DSP_BLOCK - 1) / DR_DSP_BLOCK, cap); }
 
 // The counts and the scale of auto-exposure into the scratch buffer: a memset and two launches
@@ -153,33 +133,22 @@ int run(const char* who, const float* rgb, int32_t w, int32_t h, const DrDisplay
 extern "C" int dr_display_device(const void* rgb_dev, int32_t w, int32_t h, const DrDisplayParams* params, void* out_dev, void* scratch_dev,
                                  uint64_t* scratch_bytes, void* hip_stream) {
   const char* who = "dr_display_device";
-  const std::string pre = std::string(who) + ": ";
-  if (!scratch_bytes || !params) return dr_fail(DR_ERR_INVALID, pre + "a null pointer");
-  if (!scratch_dev) {  // the size query
-    if (const char* why = dsp_check(params, w, h)) return dr_fail(DR_ERR_INVALID, pre + why);
-    *scratch_bytes = DR_DSP_SCRATCH;
-    return DR_OK;
-  }
-  const int rc = dsp_check_images(who, rgb_dev, w, h, params, out_dev, true);
+  if (!scratch_bytes || !params) return img_refuse(who, "a null pointer");
+  int rc = scratch_dev ? dsp_check_images(who, rgb_dev, w, h, params, out_dev, true) : img_refuse(who, dsp_check(params, w, h));
   if (rc != DR_OK) return rc;
-  if (*scratch_bytes < DR_DSP_SCRATCH) return dr_fail(DR_ERR_INVALID, pre + "the scratch buffer is too small");
-  if ((uintptr_t)scratch_dev % 16u != 0) return dr_fail(DR_ERR_INVALID, pre + "the scratch buffer is not 16-byte aligned");
-  if ((uintptr_t)out_dev % 4u != 0) return dr_fail(DR_ERR_INVALID, pre + "out is not 4-byte aligned");
+  if (img_scratch(who, scratch_dev, scratch_bytes, DR_DSP_SCRATCH, &rc)) return rc;
+  if ((uintptr_t)out_dev % 4u != 0) return img_refuse(who, "out is not 4-byte aligned");
   const size_t n = (size_t)w * (size_t)h;
-  if (dn_overlap(out_dev, 4 * n, scratch_dev, (size_t)DR_DSP_SCRATCH)) return dr_fail(DR_ERR_INVALID, pre + "out overlaps the scratch buffer");
-  if (dn_overlap(rgb_dev, 3 * n * sizeof(float), scratch_dev, (size_t)DR_DSP_SCRATCH))
-    return dr_fail(DR_ERR_INVALID, pre + "rgb overlaps the scratch buffer");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return dr_fail(DR_ERR_NO_DEVICE, pre + "called before dr_init");
+  if (dn_overlap(out_dev, 4 * n, scratch_dev, (size_t)DR_DSP_SCRATCH)) return img_refuse(who, "out overlaps the scratch buffer");
+  if (dn_overlap(rgb_dev, 3 * n * sizeof(float), scratch_dev, (size_t)DR_DSP_SCRATCH)) return img_refuse(who, "rgb overlaps the scratch buffer");
+  if ((rc = img_device_ready(who)) != DR_OK) return rc;
   return run(who, (const float*)rgb_dev, w, h, *params, out_dev, scratch_dev, (hipStream_t)hip_stream);
 }
 
 extern "C" int dr_display(const float* rgb, int32_t w, int32_t h, const DrDisplayParams* params, uint8_t* out) {
   const char* who = "dr_display";
-  const int rc = dsp_check_images(who, rgb, w, h, params, out, true);
-  if (rc != DR_OK) return rc;
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return dr_fail(DR_ERR_NO_DEVICE, std::string(who) + ": called before dr_init");
+  int rc = dsp_check_images(who, rgb, w, h, params, out, true);
+  if (rc != DR_OK || (rc = img_device_ready(who)) != DR_OK) return rc;
   const size_t n = (size_t)w * (size_t)h;
   Buf<float> dRgb;
   Buf<uint32_t> dOut, scratch;
@@ -187,32 +156,29 @@ extern "C" int dr_display(const float* rgb, int32_t w, int32_t h, const DrDispla
   ST(dOut.alloc(n));
   ST(scratch.alloc((size_t)DR_DSP_SCRATCH / sizeof(uint32_t)));
   hipStream_t s = 0;
-  ST(hipMemcpyAsync(dRgb.p, rgb, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
-  const int rc2 = run(who, dRgb.p, w, h, *params, dOut.p, scratch.p, s);
-  if (rc2 != DR_OK) return rc2;
-  ST(hipMemcpyAsync(out, dOut.p, 4 * n, hipMemcpyDeviceToHost, s));
+  ST(dRgb.upload(rgb, 3 * n, s));
+  if ((rc = run(who, dRgb.p, w, h, *params, dOut.p, scratch.p, s)) != DR_OK) return rc;
+  ST(dOut.download((uint32_t*)out, n, s));
   ST(hipStreamSynchronize(s));
   return DR_OK;
 }
 
 extern "C" int dr_display_exposure(const float* rgb, int32_t w, int32_t h, const DrDisplayParams* params, float* scale, uint32_t* hist) {
   const char* who = "dr_display_exposure";
-  const int rc = dsp_check_images(who, rgb, w, h, params, nullptr, false);
+  int rc = dsp_check_images(who, rgb, w, h, params, nullptr, false);
   if (rc != DR_OK) return rc;
-  if (!scale) return dr_fail(DR_ERR_INVALID, std::string(who) + ": a null pointer");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return dr_fail(DR_ERR_NO_DEVICE, std::string(who) + ": called before dr_init");
+  if (!scale) return img_refuse(who, "a null pointer");
+  if ((rc = img_device_ready(who)) != DR_OK) return rc;
   const size_t n = (size_t)w * (size_t)h;
   Buf<float> dRgb;
   Buf<uint32_t> scratch;
   ST(dRgb.alloc(3 * n));
   ST(scratch.alloc((size_t)DR_DSP_SCRATCH / sizeof(uint32_t)));
   hipStream_t s = 0;
-  ST(hipMemcpyAsync(dRgb.p, rgb, 3 * n * sizeof(float), hipMemcpyHostToDevice, s));
-  const int rc2 = run_exposure(who, dRgb.p, n, *params, scratch.p, s);
-  if (rc2 != DR_OK) return rc2;
+  ST(dRgb.upload(rgb, 3 * n, s));
+  if ((rc = run_exposure(who, dRgb.p, n, *params, scratch.p, s)) != DR_OK) return rc;
   ST(hipMemcpyAsync(scale, scratch.p + DR_DISPLAY_BINS, sizeof(float), hipMemcpyDeviceToHost, s));
-  if (hist) ST(hipMemcpyAsync(hist, scratch.p, DR_DISPLAY_BINS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (hist) ST(scratch.download(hist, DR_DISPLAY_BINS, s));
   ST(hipStreamSynchronize(s));
   return DR_OK;
 }

@@ -40,18 +40,14 @@ const DspTable& dsp_table(uint32_t encode) {
 }
 
 int dsp_check_images(const char* who, const void* rgb, int32_t w, int32_t h, const DrDisplayParams* params, const void* out, bool has_out) {
-  const std::string pre = std::string(who) + ": ";
-  if (!rgb || !params || (has_out && !out)) return dr_fail(DR_ERR_INVALID, pre + "a null pointer");
-  if (const char* why = dsp_check(params, w, h)) return dr_fail(DR_ERR_INVALID, pre + why);
+  if (!rgb || !params || (has_out && !out)) return img_refuse(who, "a null pointer");
+  if (const char* why = dsp_check(params, w, h)) return img_refuse(who, why);
   const size_t n = (size_t)w * (size_t)h;
-  if (has_out && dn_overlap(out, 4 * n, rgb, 3 * n * sizeof(float))) return dr_fail(DR_ERR_INVALID, pre + "out overlaps an input");
+  if (has_out && dn_overlap(out, 4 * n, rgb, 3 * n * sizeof(float))) return img_refuse(who, "out overlaps an input");
   return DR_OK;
 }
 
-extern "C" int dr_display_check(const DrDisplayParams* params, int32_t w, int32_t h) {
-  if (const char* why = dsp_check(params, w, h)) return dr_fail(DR_ERR_INVALID, std::string("dr_display_check: ") + why);
-  return DR_OK;
-}
+extern "C" int dr_display_check(const DrDisplayParams* params, int32_t w, int32_t h) { return img_refuse("dr_display_check", dsp_check(params, w, h)); }
 
 extern "C" int dr_display_table(uint32_t encode, uint32_t* out, uint32_t n) {
   const std::string pre = "dr_display_table: ";

@@ -15,7 +15,7 @@
 
 #include <math.h>
 
-#include "dr_denoise_pair.h"
+#include "dr_image.h"
 
 #define DR_TP_MAX_HISTORY 4096
 
@@ -116,7 +116,7 @@ DR_DN_HD void tp_pixel(const TpImages& im, int32_t w, int32_t h, const DrTempora
   const float nx = im.normal[3 * p], ny = im.normal[3 * p + 1], nz = im.normal[3 * p + 2], depth = im.depth[p];
   const bool colour = dn_finite(r) && dn_finite(g) && dn_finite(b);
   const bool valid = colour && dn_finite(nx) && dn_finite(ny) && dn_finite(nz) && dn_finite(depth) && depth > 0.0f;
-  const float l = dnp_lum(r, g, b), m2 = l * l;
+  const float l = img_lum(r, g, b), m2 = l * l;
   float hist[5];
   if (!valid || !tp_history(im, w, h, prm, x, y, nx, ny, nz, depth, hist)) {  // the current sample, bit for bit
     im.out_rgb[3 * p] = r;
@@ -139,8 +139,7 @@ DR_DN_HD void tp_pixel(const TpImages& im, int32_t w, int32_t h, const DrTempora
 // The arguments every entry point checks the same way: NULL, or the refusal's text
 inline const char* tp_check(int32_t w, int32_t h, const DrTemporalParams* p) {
   if (!p) return "a null pointer";
-  if (w < 1 || h < 1) return "w and h must be at least 1";
-  if ((int64_t)w * (int64_t)h >= ((int64_t)1 << 31)) return "the image has 2^31 or more pixels";
+  if (const char* why = img_check_dims(w, h)) return why;
   if (!dn_finite(p->depth_tol) || p->depth_tol < 0.0f || !dn_finite(p->normal_tol) || p->normal_tol < 0.0f)
     return "depth_tol and normal_tol must be finite and not negative";
   if (p->max_history < 1 || p->max_history > DR_TP_MAX_HISTORY) return "max_history must be in 1..4096";

@@ -11,7 +11,7 @@
 #ifndef DR_UPSAMPLE_H
 #define DR_UPSAMPLE_H
 
-#include "dr_denoise.h"
+#include "dr_image.h"
 
 // One full-resolution pixel (x, y) of an image w = f * wl wide: its three colour values to out3.  Every tap's coordinates are checked
 // against the low-resolution image before its two loads.

@@ -29,8 +29,9 @@ import math
 import numpy as np
 
 from . import _abi
+from ._image import _check_channel, _entry, _guides, _images, _rerender, _whole_film_refusals
 from .core.cameras import PerspectiveCamera
-from .core.renderer import FeatureIntegrator, OutputImage, SamplerRenderer
+from .core.renderer import FeatureIntegrator, OutputImage, SamplerRenderer  # noqa: F401  (the first and last: read from here by tools/)
 from .core.samplers import AdaptiveSampler
 
 # The defaults: five levels reach 2 * 16 pixels to either side; the colour sigma is one unit of radiance at the first
@@ -65,19 +66,11 @@ def atrous(rgb, normal, depth, iterations=ITERATIONS, sigma_color=SIGMA_COLOR, s
            device=True):
     """rgb [h, w, 3], normal [h, w, 3], depth [h, w] -> the filtered [h, w, 3] f32.  device=True: dr_denoise_atrous, on the GPU;
     device=False: dr_denoise_atrous_host, which needs none and writes the same bytes."""
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    normal = np.ascontiguousarray(normal, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    if rgb.ndim != 3 or rgb.shape[2] != 3 or normal.shape != rgb.shape or depth.shape != rgb.shape[:2]:
-        raise ValueError("denoise: rgb and normal must be [h, w, 3] and depth [h, w] (got %r, %r, %r)" % (rgb.shape, normal.shape, depth.shape))
+    rgb, normal, depth = _images("denoise", "rgb and normal must be [h, w, 3] and depth [h, w]", (rgb, normal), depth)
     h, w = depth.shape
     p = params(iterations, sigma_color, sigma_normal, sigma_depth)
     out = np.zeros_like(rgb)
-    lib = _abi.lib()
-    if device:
-        _abi.init(_abi._initialised if _abi._initialised is not None else 0)
-    fn = lib.dr_denoise_atrous if device else lib.dr_denoise_atrous_host
-    _abi.check(fn(rgb.ctypes.data, normal.ctypes.data, depth.ctypes.data, w, h, C.byref(p), out.ctypes.data))
+    _abi.check(_entry("dr_denoise_atrous", device)(rgb.ctypes.data, normal.ctypes.data, depth.ctypes.data, w, h, C.byref(p), out.ctypes.data))
     return out
 
 
@@ -85,18 +78,11 @@ def render_denoised(renderer, scene, normal_channel="ns", **filter_kw):
     """Renders the beauty image with `renderer` as given and two FeatureIntegrator images -- `normal_channel` ("ns" or "ng") and "depth" --
     with the same camera, film, sampler and work split, filters, and returns an OutputImage whose rgb is the result; the three unfiltered
     images stay on it as `noisy` [h, w, 3], `normal` [h, w, 3] and `depth` [h, w].  filter_kw: atrous()'s keywords."""
-    if normal_channel not in ("ns", "ng"):
-        raise ValueError("render_denoised: normal_channel must be ns or ng (got %r)" % (normal_channel,))
+    _check_channel("render_denoised", normal_channel)
     if isinstance(renderer.sampler, AdaptiveSampler):
         raise ValueError("render_denoised: the adaptive sampler is not supported (the feature integrator refuses it)")
-
-    def guide(channel):
-        return SamplerRenderer(renderer.sampler, renderer.camera, FeatureIntegrator(channel), renderer.volumeIntegrator,
-                               taskNum=renderer.taskNum, taskCount=renderer.taskCount, tileRank=renderer.tileRank,
-                               tileCount=renderer.tileCount, tileSize=renderer.tileSize).render(scene)
     beauty = renderer.render(scene)
-    normal = guide(normal_channel).rgb
-    depth = np.ascontiguousarray(guide("depth").rgb[..., 0])
+    normal, depth = _guides(renderer, scene, normal_channel)
     out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, atrous(beauty.rgb, normal, depth, **filter_kw), beauty.film)
     out.noisy, out.normal, out.depth = beauty.rgb, normal, depth
     return out
@@ -112,22 +98,12 @@ def atrous_pair(a, b, normal, depth, iterations=ITERATIONS, sigma_color=SIGMA_CO
     mean, filtered, [h, w, 3] f32; with return_variance=True also the variance [h, w] the last level leaves (-1: the pixel is not valid).
     sigma_color is in standard deviations of the local noise.  device=True: dr_denoise_pair, on the GPU; device=False:
     dr_denoise_pair_host, which needs none and writes the same bytes."""
-    a = np.ascontiguousarray(a, dtype=np.float32)
-    b = np.ascontiguousarray(b, dtype=np.float32)
-    normal = np.ascontiguousarray(normal, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    if a.ndim != 3 or a.shape[2] != 3 or b.shape != a.shape or normal.shape != a.shape or depth.shape != a.shape[:2]:
-        raise ValueError("denoise: a, b and normal must be [h, w, 3] and depth [h, w] (got %r, %r, %r, %r)"
-                         % (a.shape, b.shape, normal.shape, depth.shape))
+    a, b, normal, depth = _images("denoise", "a, b and normal must be [h, w, 3] and depth [h, w]", (a, b, normal), depth)
     h, w = depth.shape
     p = pair_params(iterations, sigma_color, sigma_normal, sigma_depth, var_floor)
     out = np.zeros_like(a)
     var = np.zeros_like(depth) if return_variance else None
-    lib = _abi.lib()
-    if device:
-        _abi.init(_abi._initialised if _abi._initialised is not None else 0)
-    fn = lib.dr_denoise_pair if device else lib.dr_denoise_pair_host
-    _abi.check(fn(a.ctypes.data, b.ctypes.data, normal.ctypes.data, depth.ctypes.data, w, h, C.byref(p), out.ctypes.data,
+    _abi.check(_entry("dr_denoise_pair", device)(a.ctypes.data, b.ctypes.data, normal.ctypes.data, depth.ctypes.data, w, h, C.byref(p), out.ctypes.data,
                   var.ctypes.data if return_variance else None))
     return (out, var) if return_variance else out
 
@@ -145,8 +121,7 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", **fi
 
     Each half costs a full render at the sampler's spp: the fair comparison with render_denoised at N samples per pixel is this function
     with a sampler of N / 2."""
-    if normal_channel not in ("ns", "ng"):
-        raise ValueError("render_denoised_pair: normal_channel must be ns or ng (got %r)" % (normal_channel,))
+    _check_channel("render_denoised_pair", normal_channel)
     sampler = renderer.sampler
     if isinstance(sampler, AdaptiveSampler):
         raise ValueError("render_denoised_pair: the adaptive sampler is not supported (the feature integrator refuses it)")
@@ -157,14 +132,9 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", **fi
         raise ValueError("render_denoised_pair: seed_b equals the sampler's seed (%d): the two halves would be one render" % (seed_b,))
     sampler_b = copy.copy(sampler)
     sampler_b.seed = seed_b
-
-    def with_(smp, surface):
-        return SamplerRenderer(smp, renderer.camera, surface, renderer.volumeIntegrator, taskNum=renderer.taskNum, taskCount=renderer.taskCount,
-                               tileRank=renderer.tileRank, tileCount=renderer.tileCount, tileSize=renderer.tileSize).render(scene)
     half_a = renderer.render(scene)
-    half_b = with_(sampler_b, renderer.surfaceIntegrator)
-    normal = with_(sampler, FeatureIntegrator(normal_channel)).rgb
-    depth = np.ascontiguousarray(with_(sampler, FeatureIntegrator("depth")).rgb[..., 0])
+    half_b = _rerender(renderer, scene, renderer.surfaceIntegrator, sampler_b)
+    normal, depth = _guides(renderer, scene, normal_channel)
     filter_kw = dict(filter_kw, return_variance=True)
     rgb, variance = atrous_pair(half_a.rgb, half_b.rgb, normal, depth, **filter_kw)
     out = OutputImage(half_a.xOffset, half_a.yOffset, half_a.width, half_a.height, rgb, half_a.film)
@@ -183,16 +153,8 @@ def upsample(rgb_lo, normal_lo, depth_lo, normal, depth, factor=None, taps=2, si
     aligned with it -- and the full-resolution guides normal [h, w, 3], depth [h, w], h = factor * hl, w = factor * wl -> the upsampled
     [h, w, 3] f32.  factor: 2 or 4; None derives it from the shapes.  taps: 2 or 4, the footprint's side in low-resolution pixels.
     device=True: dr_upsample, on the GPU; device=False: dr_upsample_host, which needs none and writes the same bytes."""
-    rgb_lo = np.ascontiguousarray(rgb_lo, dtype=np.float32)
-    normal_lo = np.ascontiguousarray(normal_lo, dtype=np.float32)
-    depth_lo = np.ascontiguousarray(depth_lo, dtype=np.float32)
-    normal = np.ascontiguousarray(normal, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    if rgb_lo.ndim != 3 or rgb_lo.shape[2] != 3 or normal_lo.shape != rgb_lo.shape or depth_lo.shape != rgb_lo.shape[:2]:
-        raise ValueError("upsample: rgb_lo and normal_lo must be [hl, wl, 3] and depth_lo [hl, wl] (got %r, %r, %r)"
-                         % (rgb_lo.shape, normal_lo.shape, depth_lo.shape))
-    if normal.ndim != 3 or normal.shape[2] != 3 or depth.shape != normal.shape[:2]:
-        raise ValueError("upsample: normal must be [h, w, 3] and depth [h, w] (got %r, %r)" % (normal.shape, depth.shape))
+    rgb_lo, normal_lo, depth_lo = _images("upsample", "rgb_lo and normal_lo must be [hl, wl, 3] and depth_lo [hl, wl]", (rgb_lo, normal_lo), depth_lo)
+    normal, depth = _images("upsample", "normal must be [h, w, 3] and depth [h, w]", (normal,), depth)
     hl, wl = depth_lo.shape
     h, w = depth.shape
     if factor is None:
@@ -206,11 +168,7 @@ def upsample(rgb_lo, normal_lo, depth_lo, normal, depth, factor=None, taps=2, si
                          % (factor, depth.shape, depth_lo.shape))
     p = upsample_params(factor, taps, sigma_normal, sigma_depth)
     out = np.zeros_like(normal)
-    lib = _abi.lib()
-    if device:
-        _abi.init(_abi._initialised if _abi._initialised is not None else 0)
-    fn = lib.dr_upsample if device else lib.dr_upsample_host
-    _abi.check(fn(rgb_lo.ctypes.data, normal_lo.ctypes.data, depth_lo.ctypes.data, wl, hl, normal.ctypes.data, depth.ctypes.data, C.byref(p),
+    _abi.check(_entry("dr_upsample", device)(rgb_lo.ctypes.data, normal_lo.ctypes.data, depth_lo.ctypes.data, wl, hl, normal.ctypes.data, depth.ctypes.data, C.byref(p),
                   out.ctypes.data))
     return out
 
@@ -218,15 +176,7 @@ def upsample(rgb_lo, normal_lo, depth_lo, normal, depth, factor=None, taps=2, si
 def _upsample_refusals(who, low, full):
     """What render_upsampled asks of its two renderers, each refusal by name; returns the factor."""
     for name, r in (("low_renderer", low), ("full_renderer", full)):
-        if isinstance(r.sampler, AdaptiveSampler):
-            raise ValueError("%s: the adaptive sampler is not supported (%s; the feature integrator refuses it)" % (who, name))
-        if r.tileCount > 1:
-            raise ValueError("%s: tileCount > 1 is not supported (%s has tileCount %d): sharded upsampling is out of scope" % (who, name, r.tileCount))
-        if r.taskCount > 1:
-            raise ValueError("%s: taskCount > 1 is not supported (%s has taskCount %d): sharded upsampling is out of scope" % (who, name, r.taskCount))
-        crop = tuple(r.camera.film.cropWindow)
-        if crop != (0.0, 1.0, 0.0, 1.0):
-            raise ValueError("%s: a crop window other than the whole film is not supported (%s has %r)" % (who, name, crop))
+        _whole_film_refusals(who, name, r, "upsampling")
     lf, ff = low.camera.film, full.camera.film
     lo, hi = (lf.xResolution, lf.yResolution), (ff.xResolution, ff.yResolution)
     factor = next((f for f in (2, 4) if hi == (f * lo[0], f * lo[1])), None)
@@ -247,21 +197,14 @@ def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", ta
     `normal` and `depth`, and `upsampled` [h, w, 3].  kw: sigma_normal and sigma_depth go to both stages; atrous()'s other keywords need
     denoise=True."""
     who = "render_upsampled"
-    if normal_channel not in ("ns", "ng"):
-        raise ValueError("%s: normal_channel must be ns or ng (got %r)" % (who, normal_channel))
+    _check_channel(who, normal_channel)
     factor = _upsample_refusals(who, low_renderer, full_renderer)
     guide_kw = {k: kw[k] for k in ("sigma_normal", "sigma_depth") if k in kw}
     if not denoise and len(guide_kw) != len(kw):
         raise ValueError("%s: %s given without denoise=True" % (who, ", ".join(sorted(set(kw) - set(guide_kw)))))
-
-    def guides(r):
-        def one(channel):
-            return SamplerRenderer(r.sampler, r.camera, FeatureIntegrator(channel), r.volumeIntegrator, taskNum=r.taskNum, taskCount=r.taskCount,
-                                   tileRank=r.tileRank, tileCount=r.tileCount, tileSize=r.tileSize).render(scene)
-        return one(normal_channel).rgb, np.ascontiguousarray(one("depth").rgb[..., 0])
     low = low_renderer.render(scene)
-    normal_lo, depth_lo = guides(low_renderer)
-    normal, depth = guides(full_renderer)
+    normal_lo, depth_lo = _guides(low_renderer, scene, normal_channel)
+    normal, depth = _guides(full_renderer, scene, normal_channel)
     up = upsample(low.rgb, normal_lo, depth_lo, normal, depth, factor=factor, taps=taps, **guide_kw)
     film = full_renderer.camera.film
     out = OutputImage(film.left, film.top, film.width, film.height, atrous(up, normal, depth, **kw) if denoise else up)
@@ -340,11 +283,7 @@ def temporal(rgb, normal, depth, history, matrices, depth_tol=DEPTH_TOL, normal_
     FeatureIntegrator guides; `history` is None (the first frame) or the TemporalFrame the previous call returned; `matrices` is
     temporal_matrices(camera, prev_camera) (read only with a history, but always checked).  Returns a TemporalFrame.  device=True:
     dr_temporal, on the GPU; device=False: dr_temporal_host, which needs none and writes the same bytes."""
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    normal = np.ascontiguousarray(normal, dtype=np.float32)
-    depth = np.ascontiguousarray(depth, dtype=np.float32)
-    if rgb.ndim != 3 or rgb.shape[2] != 3 or normal.shape != rgb.shape or depth.shape != rgb.shape[:2]:
-        raise ValueError("temporal: rgb and normal must be [h, w, 3] and depth [h, w] (got %r, %r, %r)" % (rgb.shape, normal.shape, depth.shape))
+    rgb, normal, depth = _images("temporal", "rgb and normal must be [h, w, 3] and depth [h, w]", (rgb, normal), depth)
     h, w = depth.shape
     hist = [None] * 5
     if history is not None:
@@ -353,11 +292,7 @@ def temporal(rgb, normal, depth, history, matrices, depth_tol=DEPTH_TOL, normal_
             raise ValueError("temporal: the history is of another size (%r for %r)" % (hist[0].shape, rgb.shape))
     p = temporal_params(matrices, depth_tol, normal_tol, max_history)
     out = TemporalFrame(np.zeros_like(rgb), np.zeros_like(depth), np.zeros_like(depth), normal, depth)
-    lib = _abi.lib()
-    if device:
-        _abi.init(_abi._initialised if _abi._initialised is not None else 0)
-    fn = lib.dr_temporal if device else lib.dr_temporal_host
-    _abi.check(fn(rgb.ctypes.data, normal.ctypes.data, depth.ctypes.data, *[a.ctypes.data if a is not None else None for a in hist], w, h,
+    _abi.check(_entry("dr_temporal", device)(rgb.ctypes.data, normal.ctypes.data, depth.ctypes.data, *[a.ctypes.data if a is not None else None for a in hist], w, h,
                   C.byref(p), out.rgb.ctypes.data, out.m2.ctypes.data, out.len.ctypes.data))
     return out
 
@@ -377,21 +312,13 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
     Every frame's guides are therefore rendered with a copy of its sampler that carries the first renderer's seed: at one pose the guides are
     the same bytes whatever the beauty image's seed."""
     who = "render_sequence"
-    if normal_channel not in ("ns", "ng"):
-        raise ValueError("%s: normal_channel must be ns or ng (got %r)" % (who, normal_channel))
+    _check_channel(who, normal_channel)
     renderers = list(renderers)
     if kw and not denoise:
         raise ValueError("%s: %s given without denoise=True" % (who, ", ".join(sorted(kw))))
     for k, r in enumerate(renderers):
         name = "renderers[%d]" % k
-        if isinstance(r.sampler, AdaptiveSampler):
-            raise ValueError("%s: the adaptive sampler is not supported (%s; the feature integrator refuses it)" % (who, name))
-        if r.tileCount > 1 or r.taskCount > 1:
-            raise ValueError("%s: tileCount > 1 and taskCount > 1 are not supported (%s has %d and %d): sharded accumulation is out of scope"
-                             % (who, name, r.tileCount, r.taskCount))
-        crop = tuple(r.camera.film.cropWindow)
-        if crop != (0.0, 1.0, 0.0, 1.0):
-            raise ValueError("%s: a crop window other than the whole film is not supported (%s has %r)" % (who, name, crop))
+        _whole_film_refusals(who, name, r, "accumulation", each=False)
         _camera_refusals(who, name + ".camera", r.camera)
     mats = [temporal_matrices(r.camera, renderers[max(k - 1, 0)].camera) for k, r in enumerate(renderers)]
 
@@ -402,13 +329,8 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
         if guide_seed is not None and getattr(guide_sampler, "seed", None) is not None:
             guide_sampler = copy.copy(r.sampler)
             guide_sampler.seed = guide_seed
-
-        def guide(channel):
-            return SamplerRenderer(guide_sampler, r.camera, FeatureIntegrator(channel), r.volumeIntegrator, taskNum=r.taskNum, taskCount=r.taskCount,
-                                   tileRank=r.tileRank, tileCount=r.tileCount, tileSize=r.tileSize).render(scene)
         beauty = r.render(scene)
-        normal = guide(normal_channel).rgb
-        depth = np.ascontiguousarray(guide("depth").rgb[..., 0])
+        normal, depth = _guides(r, scene, normal_channel, guide_sampler)
         history = temporal(beauty.rgb, normal, depth, history, m, depth_tol=depth_tol, normal_tol=normal_tol, max_history=max_history)
         rgb = atrous(history.rgb, normal, depth, **kw) if denoise else history.rgb
         out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, rgb, beauty.film)

@@ -17,6 +17,7 @@ import zlib
 import numpy as np
 
 from . import _abi
+from ._image import _entry, _images
 
 CURVES = {"clamp": _abi.DR_TONE_CLAMP, "reinhard": _abi.DR_TONE_REINHARD, "filmic": _abi.DR_TONE_FILMIC}
 ENCODES = {"srgb": _abi.DR_ENCODE_SRGB, "gamma22": _abi.DR_ENCODE_GAMMA22, "reference": _abi.DR_ENCODE_REFERENCE}
@@ -57,17 +58,7 @@ def params(exposure=None, key=KEY, percentile=PERCENTILE, curve=CURVE, white=flo
 
 
 def _image(rgb):
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
-    if rgb.ndim != 3 or rgb.shape[2] != 3:
-        raise ValueError("display: rgb must be [h, w, 3] (got %r)" % (rgb.shape,))
-    return rgb
-
-
-def _lib(device):
-    lib = _abi.lib()
-    if device:
-        _abi.init(_abi._initialised if _abi._initialised is not None else 0)
-    return lib
+    return _images("display", "rgb must be [h, w, 3]", (rgb,))[0]
 
 
 def tonemap(rgb, exposure=None, key=KEY, percentile=PERCENTILE, curve=CURVE, white=float("inf"), encode=ENCODE, invalid=INVALID, device=True):
@@ -78,9 +69,7 @@ def tonemap(rgb, exposure=None, key=KEY, percentile=PERCENTILE, curve=CURVE, whi
     h, w = rgb.shape[:2]
     p = params(exposure, key, percentile, curve, white, encode, invalid)
     out = np.zeros((h, w, 4), np.uint8)
-    lib = _lib(device)
-    fn = lib.dr_display if device else lib.dr_display_host
-    _abi.check(fn(rgb.ctypes.data, w, h, C.byref(p), out.ctypes.data))
+    _abi.check(_entry("dr_display", device)(rgb.ctypes.data, w, h, C.byref(p), out.ctypes.data))
     return out
 
 
@@ -91,9 +80,7 @@ def exposure_of(rgb, key=KEY, percentile=PERCENTILE, device=True):
     p = params(None, key, percentile)
     scale = C.c_float(0.0)
     hist = np.zeros(_abi.DR_DISPLAY_BINS, np.uint32)
-    lib = _lib(device)
-    fn = lib.dr_display_exposure if device else lib.dr_display_exposure_host
-    _abi.check(fn(rgb.ctypes.data, w, h, C.byref(p), C.byref(scale), hist.ctypes.data))
+    _abi.check(_entry("dr_display_exposure", device)(rgb.ctypes.data, w, h, C.byref(p), C.byref(scale), hist.ctypes.data))
     return float(scale.value), hist
 
 

@@ -538,7 +538,7 @@ typedef struct DrDenoisePairParams {
  * dr_denoise_pair_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
 int dr_denoise_pair_host(const float* a, const float* b, const float* normal, const float* depth, int32_t w, int32_t h,
                          const DrDenoisePairParams* params, float* out, float* out_var);
-/* The same ON THE GPU (dr_denoise_pair_device.hip), host buffers: uploads, filters, copies back.  Needs dr_init. */
+/* The same ON THE GPU (dr_denoise_device.hip), host buffers: uploads, filters, copies back.  Needs dr_init. */
 int dr_denoise_pair(const float* a, const float* b, const float* normal, const float* depth, int32_t w, int32_t h,
                     const DrDenoisePairParams* params, float* out, float* out_var);
 /* The same on device buffers, asynchronous on the given hipStream_t; the scratch buffer and its size query as for

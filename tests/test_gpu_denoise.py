@@ -1,4 +1,4 @@
-"""The edge-avoiding a-trous denoiser on the GPU (k_denoise_pack / k_denoise_atrous): dr_denoise_atrous (host buffers) and
+"""The edge-avoiding a-trous denoiser on the GPU (k_image_pack<DnInputs> / k_denoise_level<DnRule>): dr_denoise_atrous (host buffers) and
 dr_denoise_atrous_device (torch tensors, a stream of its own) against dr_denoise_atrous_host bit for bit -- the host entry is itself held to
 the numpy restatement by tests/test_denoise.py -- and render_denoised on a small Cornell scene against the restatement.  The host result of a
 case is computed once and shared.  Nothing is started after a failed call: every call's return code raises."""

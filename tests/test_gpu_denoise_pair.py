@@ -1,4 +1,4 @@
-"""The variance-guided a-trous denoiser on the GPU (k_denoise_pair_pack / k_denoise_pair_level): dr_denoise_pair (host buffers)
+"""The variance-guided a-trous denoiser on the GPU (k_image_pack<DnpInputs> / k_denoise_level<DnpRule>): dr_denoise_pair (host buffers)
 and dr_denoise_pair_device (torch tensors, a stream of its own) against dr_denoise_pair_host bit for bit, in colour and variance -- the host
 entry is itself held to the numpy restatement by tests/test_denoise_pair.py -- and render_denoised_pair on a small Cornell scene against the
 restatement.  The host result of a case is computed once and shared.  Nothing is started after a failed call: every call's return code raises."""

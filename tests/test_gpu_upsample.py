@@ -1,4 +1,4 @@
-"""The joint bilateral upsampler on the GPU (k_upsample_pack / k_upsample): dr_upsample (host buffers) and dr_upsample_device
+"""The joint bilateral upsampler on the GPU (k_image_pack<DnInputs> / k_upsample): dr_upsample (host buffers) and dr_upsample_device
 (torch tensors, a stream of its own) against dr_upsample_host bit for bit -- the host entry is itself held to the numpy restatement by
 tests/test_upsample.py -- and render_upsampled on the small Cornell scene against upsample() and atrous() of its own parts.  The host result
 of a case is computed once and shared.  One process; nothing is started after a failed call: every call's return code raises."""

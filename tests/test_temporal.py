@@ -211,7 +211,10 @@ def test_every_refusal_by_code_and_text(hip):
     lib = hip.lib()
     fr = tc.frame(3, 2, "identity")
     m = tc.matrices("identity", 3, 2)
-    outs = dict(out_rgb=np.zeros((2, 3, 3), np.float32), out_m2=np.zeros((2, 3), np.float32), out_len=np.zeros((2, 3), np.float32))
+    # the outputs lie in one allocation with room behind them: a pointer moved past an output's end stays clear of the inputs wherever the
+    # heap has put those
+    room = np.zeros(64, np.float32)
+    outs = dict(out_rgb=room[:18].reshape(2, 3, 3), out_m2=room[18:24].reshape(2, 3), out_len=room[24:30].reshape(2, 3))
     arrays = dict(fr, **outs)
     ptr = {k: v.ctypes.data for k, v in arrays.items()}
     order = tc.CURRENT_PLANES + tc.HISTORY_PLANES
