@@ -187,6 +187,11 @@ class DrDenoisePairParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float), ("var_floor", C.c_float)]
 
 
+class DrDenoiseMomentsParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("k_color", C.c_float), ("k_normal", C.c_float), ("k_depth", C.c_float), ("var_floor", C.c_float),
+                ("min_history", C.c_int32), ("radius", C.c_int32)]
+
+
 class DrDisplayParams(C.Structure):
     _fields_ = [("curve", C.c_uint32), ("encode", C.c_uint32), ("auto_exposure", C.c_uint32), ("permille", C.c_uint32), ("exposure", C.c_float),
                 ("key", C.c_float), ("inv_white2", C.c_float), ("invalid_rgba", C.c_uint32)]
@@ -240,6 +245,11 @@ EXPORTS = {
                                   C.c_void_p, C.c_void_p]),
     "dr_denoise_pair_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDenoisePairParams),
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p]),
+    "dr_denoise_moments_check": (C.c_int, [C.POINTER(DrDenoiseMomentsParams), C.c_int32, C.c_int32]),
+    "dr_denoise_moments_host": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.POINTER(DrDenoiseMomentsParams)] + [C.c_void_p] * 3),
+    "dr_denoise_moments": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.POINTER(DrDenoiseMomentsParams)] + [C.c_void_p] * 3),
+    "dr_denoise_moments_device": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.POINTER(DrDenoiseMomentsParams)] + [C.c_void_p] * 4
+                                  + [C.POINTER(C.c_uint64), C.c_void_p]),
     "dr_display_check": (C.c_int, [C.POINTER(DrDisplayParams), C.c_int32, C.c_int32]),
     "dr_display_table": (C.c_int, [C.c_uint32, C.c_void_p, C.c_uint32]),
     "dr_display_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(DrDisplayParams), C.c_void_p]),

@@ -96,24 +96,28 @@ struct DnRule {
   }
 };
 
-// The levels of one call on the host, on images that the caller has checked: a serial loop over Rule's per-pixel function.  The levels
-// take turns between two colour planes; the last one writes out [h][w][3] and, where the rule has one and out_var is set, [h][w].
-template <class Rule>
-void dn_levels_host(const typename Rule::Inputs& in, int32_t w, int32_t h, const typename Rule::Params& prm, float* out, float* out_var) {
-  const size_t n = (size_t)w * (size_t)h;
-  std::vector<DnTexel> guide(n), a(n), b(prm.iterations > 1 ? n : 0);
+// A call on the host is two halves, as on the device (dr_denoise_device.hip): make the two planes, run the levels.  The first half of
+// the a-trous filter and of its pair form is the pack; the moments form (dr_denoise_moments.h) has a variance estimate behind it.
+template <class Inputs>
+void dn_pack_host(const Inputs& in, size_t n, DnTexel* colour, DnTexel* guide) {
   for (size_t p = 0; p < n; ++p) {
-    a[p] = in.colour(p);
+    colour[p] = in.colour(p);
     guide[p] = in.guide(p);
   }
-  DnTexel* src = a.data();
-  DnTexel* dst = b.data();
+}
+
+// The levels of one call on the host: a serial loop over Rule's per-pixel function.  The levels take turns between two colour planes,
+// `src` first (`dst` is not touched by a single level); the last one writes out [h][w][3] and, where the rule has one and out_var is
+// set, [h][w].
+template <class Rule>
+void dn_run_levels_host(DnTexel* src, DnTexel* dst, const DnTexel* guide, int32_t w, int32_t h, const typename Rule::Params& prm, float* out,
+                        float* out_var) {
   for (int i = 0; i < prm.iterations; ++i) {
     const bool last = i == prm.iterations - 1;
     const Rule rule = Rule::level(prm, i);
     for (int32_t y = 0; y < h; ++y)
       for (int32_t x = 0; x < w; ++x) {
-        const DnTexel t = rule.pixel(src, guide.data(), w, h, x, y, (int32_t)(1 << i));
+        const DnTexel t = rule.pixel(src, guide, w, h, x, y, (int32_t)(1 << i));
         const size_t p = (size_t)y * (size_t)w + (size_t)x;
         if (last) {
           out[3 * p] = t.x;
@@ -126,6 +130,15 @@ void dn_levels_host(const typename Rule::Inputs& in, int32_t w, int32_t h, const
       }
     std::swap(src, dst);
   }
+}
+
+// Both halves, on images that the caller has checked: the pack, then the levels
+template <class Rule>
+void dn_levels_host(const typename Rule::Inputs& in, int32_t w, int32_t h, const typename Rule::Params& prm, float* out, float* out_var) {
+  const size_t n = (size_t)w * (size_t)h;
+  std::vector<DnTexel> guide(n), a(n), b(prm.iterations > 1 ? n : 0);
+  dn_pack_host(in, n, a.data(), guide.data());
+  dn_run_levels_host<Rule>(a.data(), b.data(), guide.data(), w, h, prm, out, out_var);
 }
 
 #endif

@@ -20,6 +20,11 @@ and temporal accumulation with reprojection for the frames of a camera animation
     temporal(rgb, normal, depth, history, matrices, ...)         blends one frame into the history of the frames before it
     render_sequence(renderers, scene, ...)                       renders one frame per camera pose and accumulates them
 
+and the variance-guided filter fed by that history's luminance moments (dr_denoise_moments*):
+
+    atrous_moments(frame, ...)                                   filters a TemporalFrame's colour, guided by the variance its moments estimate
+    render_sequence(renderers, scene, denoise="moments", ...)    ... on every frame of a sequence
+
 The library takes sharpness values k = 1 / sigma^2 (k = 0: the term is off); this module takes the sigmas.
 """
 import copy
@@ -297,13 +302,53 @@ def temporal(rgb, normal, depth, history, matrices, depth_tol=DEPTH_TOL, normal_
     return out
 
 
+# The moments filter's own two, SVGF's and reasoned, not tuned on any animation.  min_history: below four frames the sample
+# variance of the per-frame luminance has two degrees of freedom or fewer and is mostly noise itself, so the neighbours are asked instead.
+# radius: a 7 x 7 window is 49 accumulated values, the fewest at which a spatial estimate is steadier than a four-frame temporal one.
+MIN_HISTORY = 4
+RADIUS = 3
+
+
+def moments_params(iterations=ITERATIONS, sigma_color=SIGMA_COLOR_PAIR, sigma_normal=SIGMA_NORMAL, sigma_depth=SIGMA_DEPTH, var_floor=VAR_FLOOR,
+                   min_history=MIN_HISTORY, radius=RADIUS):
+    return _abi.DrDenoiseMomentsParams(int(iterations), sharpness(sigma_color), sharpness(sigma_normal), sharpness(sigma_depth), float(var_floor),
+                                       int(min_history), int(radius))
+
+
+def atrous_moments(frame, iterations=ITERATIONS, sigma_color=SIGMA_COLOR_PAIR, sigma_normal=SIGMA_NORMAL, sigma_depth=SIGMA_DEPTH,
+                   var_floor=VAR_FLOOR, min_history=MIN_HISTORY, radius=RADIUS, device=True, return_variance=False, return_estimate=False):
+    """frame: a TemporalFrame, or anything with rgb [h, w, 3], m2 [h, w], len [h, w], normal [h, w, 3] and depth [h, w] -> its colour, filtered,
+    [h, w, 3] f32, guided by the per-pixel variance its moments estimate: the temporal one where len >= min_history, else the spatial one over
+    the (2 radius + 1)^2 window.  return_variance=True adds the variance [h, w] the last level leaves, return_estimate=True the estimate
+    [h, w] before any level (-1: the pixel is not valid), in that order.  sigma_color is in standard deviations of the local noise.
+    device=True: dr_denoise_moments, on the GPU; device=False: dr_denoise_moments_host, which needs none and writes the same bytes."""
+    for name in ("rgb", "m2", "len", "normal", "depth"):
+        if not hasattr(frame, name):
+            raise ValueError("denoise: frame has no %s (a TemporalFrame, or anything with rgb, m2, len, normal and depth)" % (name,))
+    rgb, normal, depth = _images("denoise", "rgb and normal must be [h, w, 3] and depth [h, w]", (frame.rgb, frame.normal), frame.depth)
+    m2, length = (np.ascontiguousarray(a, dtype=np.float32) for a in (frame.m2, frame.len))
+    if m2.shape != depth.shape or length.shape != depth.shape:
+        raise ValueError("denoise: m2 and len must be [h, w] like depth (got %r and %r for %r)" % (m2.shape, length.shape, depth.shape))
+    h, w = depth.shape
+    p = moments_params(iterations, sigma_color, sigma_normal, sigma_depth, var_floor, min_history, radius)
+    out = np.zeros_like(rgb)
+    var = np.zeros_like(depth) if return_variance else None
+    var0 = np.zeros_like(depth) if return_estimate else None
+    _abi.check(_entry("dr_denoise_moments", device)(rgb.ctypes.data, m2.ctypes.data, length.ctypes.data, normal.ctypes.data, depth.ctypes.data, w, h,
+                  C.byref(p), out.ctypes.data, var.ctypes.data if return_variance else None, var0.ctypes.data if return_estimate else None))
+    extra = [a for a in (var, var0) if a is not None]
+    return (out, *extra) if extra else out
+
+
 def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_tol=DEPTH_TOL, normal_tol=NORMAL_TOL, max_history=MAX_HISTORY,
                     **kw):
     """Renders one frame per renderer -- one camera pose each, in the order of the animation -- with its beauty image and two
     FeatureIntegrator images, `normal_channel` ("ns" or "ng") and "depth", as render_denoised does, and accumulates each into the history of
     the frames before it with temporal().  Returns the list of frames: OutputImages whose rgb is the accumulated colour, or with denoise=True
-    atrous(accumulated, normal, depth, **kw); the parts stay on each as `noisy` (the frame's own render), `accumulated`, `normal`, `depth`,
-    `m2`, `len`, `variance` and `history` (the TemporalFrame).
+    atrous(accumulated, normal, depth, **kw), or with denoise="moments" atrous_moments(history, **kw), whose last level's variance then stays
+    on the frame as `filtered_variance`; the parts stay on each as `noisy` (the frame's own render), `accumulated`, `normal`, `depth`,
+    `m2`, `len`, `variance` and `history` (the TemporalFrame).  The history itself is never filtered: the next frame accumulates onto the
+    unfiltered colour.
 
     Give each renderer's sampler its own seed.  The samplers are keyed by pixel and seed: two frames that share a seed draw the same sample
     pattern in every pixel, so a surface that stays under one pixel is sampled with the same numbers again, the frames' errors are the same
@@ -314,6 +359,8 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
     who = "render_sequence"
     _check_channel(who, normal_channel)
     renderers = list(renderers)
+    if not any(denoise is v for v in (False, True)) and denoise != "moments":
+        raise ValueError("%s: denoise must be False, True or \"moments\", got %r" % (who, denoise))
     if kw and not denoise:
         raise ValueError("%s: %s given without denoise=True" % (who, ", ".join(sorted(kw))))
     for k, r in enumerate(renderers):
@@ -332,8 +379,14 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
         beauty = r.render(scene)
         normal, depth = _guides(r, scene, normal_channel, guide_sampler)
         history = temporal(beauty.rgb, normal, depth, history, m, depth_tol=depth_tol, normal_tol=normal_tol, max_history=max_history)
-        rgb = atrous(history.rgb, normal, depth, **kw) if denoise else history.rgb
+        filtered_variance = None
+        if denoise == "moments":
+            rgb, filtered_variance = atrous_moments(history, **dict(kw, return_variance=True, return_estimate=False))
+        else:
+            rgb = atrous(history.rgb, normal, depth, **kw) if denoise else history.rgb
         out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, rgb, beauty.film)
+        if filtered_variance is not None:
+            out.filtered_variance = filtered_variance
         out.noisy, out.accumulated, out.normal, out.depth = beauty.rgb, history.rgb, normal, depth
         out.m2, out.len, out.variance, out.history = history.m2, history.len, history.variance, history
         frames.append(out)

@@ -619,6 +619,43 @@ int dr_temporal_device(const void* rgb_dev, const void* normal_dev, const void* 
                        const void* h_len_dev, const void* h_normal_dev, const void* h_depth_dev, int32_t w, int32_t h,
                        const DrTemporalParams* params, void* out_rgb_dev, void* out_m2_dev, void* out_len_dev, void* hip_stream);
 
+/* The variance-guided a-trous denoiser over a temporal history (the variance estimate of Schied et al. 2017,
+ * section 4.2, in front of the levels of section 2.19): rgb[h][w][3], m2[h][w] and len[h][w] are what dr_temporal* wrote last -- the
+ * accumulated colour, the accumulated second moment of its luminance and the history length -- and normal and depth that frame's guides.
+ * A pixel is valid where all nine values are finite and len > 0.  Its first variance is, with l = lum(rgb): where len >= min_history,
+ * max(0, m2 - l * l) / (len - 1), the sample variance of the per-frame luminance taken as the variance of the accumulated mean; where
+ * the history is shorter, max(0, s2 / sw - (s1 / sw)^2) over the valid pixels q of the (2 radius + 1)^2 window inside the image, with
+ * s1, s2 and sw the sums of wt * lum(q), wt * lum(q)^2 and wt, and wt = 1 divided by the normal and depth terms of DrDenoiseParams.  A
+ * first variance that is not finite makes the pixel invalid.  The levels are those of dr_denoise_pair* on (rgb, first variance).
+ * out[h][w][3]: the filtered colour; out_var[h][w], which may be NULL: its variance after the last level; out_var0[h][w], which may be
+ * NULL: the first variance, before any level; both -1 where the pixel is not valid -- such a pixel is copied through and is no tap of
+ * any other pixel.  f32 arithmetic, one rounding per operator: the three entry points below write the same bytes. */
+typedef struct DrDenoiseMomentsParams {
+  int32_t iterations;  /* 1 .. 8 */
+  float k_color;       /* as in DrDenoisePairParams */
+  float k_normal;      /* as in DrDenoiseParams; also the spatial estimate's */
+  float k_depth;
+  float var_floor;     /* as in DrDenoisePairParams */
+  int32_t min_history; /* 2 .. 4096: a history of at least this many frames gives the temporal estimate */
+  int32_t radius;      /* 0 .. 3: the spatial estimate's window is (2 radius + 1)^2 pixels */
+} DrDenoiseMomentsParams; /* 28 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer (out_var and out_var0 excepted), w or h < 1, w * h >= 2^31, iterations outside
+ * 1 .. 8, a k that is negative or not finite, a var_floor that is not finite or not positive, min_history outside 2 .. 4096, radius
+ * outside 0 .. 3, an output overlapping an input, another output (or the scratch buffer).  dr_denoise_moments_check states those of
+ * the parameters and the size without an image. */
+int dr_denoise_moments_check(const DrDenoiseMomentsParams* params, int32_t w, int32_t h);
+/* dr_denoise_moments_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_denoise_moments_host(const float* rgb, const float* m2, const float* len, const float* normal, const float* depth, int32_t w,
+                            int32_t h, const DrDenoiseMomentsParams* params, float* out, float* out_var, float* out_var0);
+/* The same ON THE GPU (dr_denoise_device.hip), host buffers: uploads, filters, copies back.  Needs dr_init. */
+int dr_denoise_moments(const float* rgb, const float* m2, const float* len, const float* normal, const float* depth, int32_t w, int32_t h,
+                       const DrDenoiseMomentsParams* params, float* out, float* out_var, float* out_var0);
+/* The same on device buffers, asynchronous on the given hipStream_t; the scratch buffer and its size query as for
+ * dr_denoise_pair_device (the same size). */
+int dr_denoise_moments_device(const void* rgb_dev, const void* m2_dev, const void* len_dev, const void* normal_dev, const void* depth_dev,
+                              int32_t w, int32_t h, const DrDenoiseMomentsParams* params, void* out_dev, void* out_var_dev,
+                              void* out_var0_dev, void* scratch_dev, uint64_t* scratch_bytes, void* hip_stream);
+
 /* The display transform: rgb[h][w][3], row-major f32 linear radiance, becomes out[h][w][4], bytes R, G, B, A = 255.
  * Per pixel: a non-finite channel makes the pixel invalid (it is no sample of the histogram and comes out as invalid_rgba); a negative channel
  * is taken as 0; the channels are multiplied by the exposure scale, go through the tone curve and are encoded to a byte each.  The scale is
@@ -918,7 +955,8 @@ const char* dr_version(void);
  * two new entry points read -- dr_nurbs_dice and dr_nurbs_dice_device; and the upsampler: one new struct, DrUpsampleParams, that only its
  * four new entry points read -- dr_upsample_check, dr_upsample_host, dr_upsample and dr_upsample_device; and temporal accumulation: one new
  * struct, DrTemporalParams, that only its four new entry points read -- dr_temporal_check, dr_temporal_host, dr_temporal and
- * dr_temporal_device). */
+ * dr_temporal_device; and the moments denoiser: one new struct, DrDenoiseMomentsParams, that only its four new entry points read --
+ * dr_denoise_moments_check, dr_denoise_moments_host, dr_denoise_moments and dr_denoise_moments_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -1060,6 +1098,11 @@ DR_ABI_OFFSET(DrTemporalParams, prev_to_raster, 256);
 DR_ABI_OFFSET(DrTemporalParams, depth_tol, 384);
 DR_ABI_OFFSET(DrTemporalParams, normal_tol, 388);
 DR_ABI_OFFSET(DrTemporalParams, max_history, 392);
+DR_ABI_SIZE(DrDenoiseMomentsParams, 28);
+DR_ABI_OFFSET(DrDenoiseMomentsParams, k_color, 4);
+DR_ABI_OFFSET(DrDenoiseMomentsParams, var_floor, 16);
+DR_ABI_OFFSET(DrDenoiseMomentsParams, min_history, 20);
+DR_ABI_OFFSET(DrDenoiseMomentsParams, radius, 24);
 
 #ifdef __cplusplus
 }

@@ -206,6 +206,16 @@ const int OFF_DrTemporalParams_prev_to_raster = 256;
 const int OFF_DrTemporalParams_depth_tol = 384;
 const int OFF_DrTemporalParams_normal_tol = 388;
 const int OFF_DrTemporalParams_max_history = 392;
+// DrDenoiseMomentsParams (the variance-guided a-trous denoiser over a temporal history, DESIGN.md 2.24): DrDenoisePairParams' five fields, then
+// int32 min_history (2..4096: a history at least this long gives the temporal variance estimate) and int32 radius (0..3: the spatial one's window)
+const int SIZEOF_DrDenoiseMomentsParams = 28;
+const int OFF_DrDenoiseMomentsParams_iterations = 0;
+const int OFF_DrDenoiseMomentsParams_k_color = 4;
+const int OFF_DrDenoiseMomentsParams_k_normal = 8;
+const int OFF_DrDenoiseMomentsParams_k_depth = 12;
+const int OFF_DrDenoiseMomentsParams_var_floor = 16;
+const int OFF_DrDenoiseMomentsParams_min_history = 20;
+const int OFF_DrDenoiseMomentsParams_radius = 24;
 // DrNurbsPatch (one NURBS patch, DESIGN.md 2.21): per direction int32 n, int32 order, the address of n + order f32 knots and the f32 range;
 // the address of the nu * nv control points (3 floats each, or 4 when homogeneous is 1); uint32 dice rates (0: 30)
 const int SIZEOF_DrNurbsPatch = 72;
@@ -344,6 +354,14 @@ typedef _TemporalC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Floa
     Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _TemporalD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>,
     Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+// dr_denoise_moments (the variance-guided filter over a temporal history on the GPU, host buffers; DESIGN.md 2.24): what dr_temporal wrote last --
+// rgb[h][w][3], m2[h][w], len[h][w] -- and that frame's normal[h][w][3] and depth[h][w], w, h, DrDenoiseMomentsParams (28 bytes, the
+// OFF_DrDenoiseMomentsParams_* offsets above), out[h][w][3], out_var[h][w] or null, out_var0[h][w] or null.  (Signature only, never compiled,
+// like the rest.)
+typedef _DenoiseMomentsC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32,
+    Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
+typedef _DenoiseMomentsD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>,
+    Pointer<Float>, Pointer<Float>, Pointer<Float>);
 // dr_display (the display transform on the GPU, host buffers; DESIGN.md 2.20): rgb[h][w][3], w, h, DrDisplayParams (32 bytes, the
 // OFF_DrDisplayParams_* offsets above), out[h][w][4] bytes R, G, B, A.  (Signature only, never compiled, like the rest.)
 typedef _DisplayC = Int32 Function(Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Uint8>);
@@ -421,6 +439,9 @@ class HipSamplerRenderer extends Renderer {
   /// Temporal accumulation: one frame of a camera animation blended into the history of the frames before it, where the previous frame
   /// saw the same surface (after dr_init).  The host composes the three matrices of DrTemporalParams from the two cameras.
   static final _TemporalD temporal = _lib.lookupFunction<_TemporalC, _TemporalD>('dr_temporal');
+  /// The variance-guided a-trous denoiser over what `temporal` wrote last: the history's luminance moments give the per-pixel variance
+  /// that guides the colour term (after dr_init).
+  static final _DenoiseMomentsD denoiseMoments = _lib.lookupFunction<_DenoiseMomentsC, _DenoiseMomentsD>('dr_denoise_moments');
   /// The display transform: linear f32 radiance to RGBA8 through exposure, a tone curve and an 8-bit encode (after dr_init).
   static final _DisplayD displayImage = _lib.lookupFunction<_DisplayC, _DisplayD>('dr_display');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
