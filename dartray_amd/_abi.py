@@ -206,6 +206,11 @@ class DrTemporalParams(C.Structure):
                 ("depth_tol", C.c_float), ("normal_tol", C.c_float), ("max_history", C.c_int32), ("reserved", C.c_uint32)]
 
 
+class DrFireflyParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float), ("depth_tol", C.c_float),
+                ("normal_tol", C.c_float)]
+
+
 class DrNurbsPatch(C.Structure):
     """One NURBS patch (dr_nurbs_dice / dr_nurbs_dice_device): include/dartray_hip.h."""
     _fields_ = [("nu", C.c_int32), ("uorder", C.c_int32), ("uknots", C.c_void_p), ("u0", C.c_float), ("u1", C.c_float),
@@ -269,6 +274,10 @@ EXPORTS = {
     "dr_temporal_host": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.POINTER(DrTemporalParams)] + [C.c_void_p] * 3),
     "dr_temporal": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.POINTER(DrTemporalParams)] + [C.c_void_p] * 3),
     "dr_temporal_device": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32, C.POINTER(DrTemporalParams)] + [C.c_void_p] * 4),
+    "dr_firefly_check": (C.c_int, [C.POINTER(DrFireflyParams), C.c_int32, C.c_int32]),
+    "dr_firefly_host": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrFireflyParams)] + [C.c_void_p] * 2),
+    "dr_firefly": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrFireflyParams)] + [C.c_void_p] * 2),
+    "dr_firefly_device": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrFireflyParams)] + [C.c_void_p] * 3),
     "dr_scene_create": (C.c_int, [C.POINTER(DrSceneDesc), C.POINTER(C.c_void_p)]),
     "dr_scene_destroy": (None, [C.c_void_p]),
     "dr_scene_get_trace_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 2)]),

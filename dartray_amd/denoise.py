@@ -25,6 +25,12 @@ and the variance-guided filter fed by that history's luminance moments (DESIGN.m
     atrous_moments(frame, ...)                                   filters a TemporalFrame's colour, guided by the variance its moments estimate
     render_sequence(renderers, scene, denoise="moments", ...)    ... on every frame of a sequence
 
+and firefly suppression, the outlier clamp that runs ahead of all of them (dr_firefly*):
+
+    firefly(rgb, normal, depth, ...)                             scales a pixel far brighter than its same-surface neighbours down to their level
+    render_firefly(renderer, scene, ...)                         renders the beauty image and its two guides, and clamps
+    render_denoised / _pair / render_upsampled / render_sequence(..., firefly=True)    ... ahead of the filter, the upsampler, the history
+
 The library takes sharpness values k = 1 / sigma^2 (k = 0: the term is off); this module takes the sigmas.
 """
 import copy
@@ -79,17 +85,23 @@ def atrous(rgb, normal, depth, iterations=ITERATIONS, sigma_color=SIGMA_COLOR, s
     return out
 
 
-def render_denoised(renderer, scene, normal_channel="ns", **filter_kw):
+def render_denoised(renderer, scene, normal_channel="ns", firefly=False, **filter_kw):
     """Renders the beauty image with `renderer` as given and two FeatureIntegrator images -- `normal_channel` ("ns" or "ng") and "depth" --
     with the same camera, film, sampler and work split, filters, and returns an OutputImage whose rgb is the result; the three unfiltered
-    images stay on it as `noisy` [h, w, 3], `normal` [h, w, 3] and `depth` [h, w].  filter_kw: atrous()'s keywords."""
+    images stay on it as `noisy` [h, w, 3], `normal` [h, w, 3] and `depth` [h, w].  filter_kw: atrous()'s keywords.  firefly: True, or a
+    dict of firefly()'s parameters, clamps the beauty image's outliers before the filter; `noisy` stays the unclamped
+    render and the luminance taken away stays on the result as `removed`."""
     _check_channel("render_denoised", normal_channel)
+    fkw = _firefly_kw("render_denoised", firefly)
     if isinstance(renderer.sampler, AdaptiveSampler):
         raise ValueError("render_denoised: the adaptive sampler is not supported (the feature integrator refuses it)")
     beauty = renderer.render(scene)
     normal, depth = _guides(renderer, scene, normal_channel)
-    out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, atrous(beauty.rgb, normal, depth, **filter_kw), beauty.film)
+    clamped, removed = _clamped(fkw, beauty.rgb, normal, depth)
+    out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, atrous(clamped, normal, depth, **filter_kw), beauty.film)
     out.noisy, out.normal, out.depth = beauty.rgb, normal, depth
+    if fkw is not None:
+        out.removed = removed
     return out
 
 
@@ -118,15 +130,20 @@ def pair_seed(seed):
     return int(seed) ^ SEED_B_XOR
 
 
-def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", **filter_kw):
+def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", firefly=False, **filter_kw):
     """Renders the scene twice -- half A with `renderer` as given, half B with a shallow copy of its sampler whose seed is `seed_b` (default:
     pair_seed of the sampler's seed) -- and the two guides as render_denoised does, all four with the same camera, integrators and work
     split, and filters the halves' mean with atrous_pair.  Returns an OutputImage whose rgb is the result; `a`, `b`, `noisy` (the mean),
     `normal`, `depth` and `variance` (the last level's, -1 where a pixel is not valid) stay on it.  filter_kw: atrous_pair()'s keywords.
 
     Each half costs a full render at the sampler's spp: the fair comparison with render_denoised at N samples per pixel is this function
-    with a sampler of N / 2."""
+    with a sampler of N / 2.
+
+    firefly: True, or a dict of firefly()'s parameters, clamps each half's outliers before the filter, so that a bright
+    pixel of one half no longer inflates the variance estimate its neighbours share; `a`, `b` and `noisy` stay the unclamped renders, and
+    the luminance taken from the halves stays on the result as `removed` = (removed_a, removed_b)."""
     _check_channel("render_denoised_pair", normal_channel)
+    fkw = _firefly_kw("render_denoised_pair", firefly)
     sampler = renderer.sampler
     if isinstance(sampler, AdaptiveSampler):
         raise ValueError("render_denoised_pair: the adaptive sampler is not supported (the feature integrator refuses it)")
@@ -141,9 +158,12 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", **fi
     half_b = _rerender(renderer, scene, renderer.surfaceIntegrator, sampler_b)
     normal, depth = _guides(renderer, scene, normal_channel)
     filter_kw = dict(filter_kw, return_variance=True)
-    rgb, variance = atrous_pair(half_a.rgb, half_b.rgb, normal, depth, **filter_kw)
+    (a, removed_a), (b, removed_b) = _clamped(fkw, half_a.rgb, normal, depth), _clamped(fkw, half_b.rgb, normal, depth)
+    rgb, variance = atrous_pair(a, b, normal, depth, **filter_kw)
     out = OutputImage(half_a.xOffset, half_a.yOffset, half_a.width, half_a.height, rgb, half_a.film)
     out.a, out.b, out.normal, out.depth, out.variance = half_a.rgb, half_b.rgb, normal, depth, variance
+    if fkw is not None:
+        out.removed = (removed_a, removed_b)
     with np.errstate(all="ignore"):
         out.noisy = np.float32(0.5) * (out.a + out.b)
     return out
@@ -194,15 +214,18 @@ def _upsample_refusals(who, low, full):
     return factor
 
 
-def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", taps=2, denoise=False, **kw):
+def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", taps=2, denoise=False, firefly=False, **kw):
     """Renders the beauty image and two FeatureIntegrator images -- `normal_channel` ("ns" or "ng") and "depth" -- with `low_renderer`, whose
     film is 1/2 or 1/4 of `full_renderer`'s in both axes over the same camera pose, the same two guides with `full_renderer`'s sampler and
     camera -- its own surface integrator is never run -- and upsamples.  Returns an OutputImage of the full size whose rgb is the result;
     with denoise=True it is atrous(upsampled, normal, depth, **kw).  The parts stay on it as `low` [hl, wl, 3], `normal_lo`, `depth_lo`,
     `normal` and `depth`, and `upsampled` [h, w, 3].  kw: sigma_normal and sigma_depth go to both stages; atrous()'s other keywords need
-    denoise=True."""
+    denoise=True.  firefly: True, or a dict of firefly()'s parameters, clamps the low-resolution beauty image's outliers under the
+    low-resolution guides before it is upsampled; `low` stays the unclamped render, and the luminance taken away stays on
+    the result as `removed` [hl, wl]."""
     who = "render_upsampled"
     _check_channel(who, normal_channel)
+    fkw = _firefly_kw(who, firefly)
     factor = _upsample_refusals(who, low_renderer, full_renderer)
     guide_kw = {k: kw[k] for k in ("sigma_normal", "sigma_depth") if k in kw}
     if not denoise and len(guide_kw) != len(kw):
@@ -210,10 +233,13 @@ def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", ta
     low = low_renderer.render(scene)
     normal_lo, depth_lo = _guides(low_renderer, scene, normal_channel)
     normal, depth = _guides(full_renderer, scene, normal_channel)
-    up = upsample(low.rgb, normal_lo, depth_lo, normal, depth, factor=factor, taps=taps, **guide_kw)
+    low_rgb, removed = _clamped(fkw, low.rgb, normal_lo, depth_lo)
+    up = upsample(low_rgb, normal_lo, depth_lo, normal, depth, factor=factor, taps=taps, **guide_kw)
     film = full_renderer.camera.film
     out = OutputImage(film.left, film.top, film.width, film.height, atrous(up, normal, depth, **kw) if denoise else up)
     out.low, out.normal_lo, out.depth_lo, out.normal, out.depth, out.upsampled = low.rgb, normal_lo, depth_lo, normal, depth, up
+    if fkw is not None:
+        out.removed = removed
     return out
 
 
@@ -302,6 +328,72 @@ def temporal(rgb, normal, depth, history, matrices, depth_tol=DEPTH_TOL, normal_
     return out
 
 
+# Firefly suppression's defaults, reasoned and not tuned on any scene.  radius 1: the eight nearest pixels are the ones most
+# likely to show the same surface under the same light.  rank 2: the limit comes from the second brightest member, so two fireflies side by
+# side do not shield each other, while a bright line one pixel wide and the corner of an emitter survive -- each of their pixels has two
+# equally bright neighbours on the same surface.  threshold 4: a pixel may be four times as bright as that neighbour before it is taken for
+# an outlier.  floor 0: nothing is added, so in a neighbourhood whose members are black any lit pixel is clamped to black.  The two
+# tolerances are temporal accumulation's: the same question -- is this the same surface? -- asked of the same guides.
+FIREFLY_RADIUS = 1
+FIREFLY_RANK = 2
+FIREFLY_THRESHOLD = 4.0
+FIREFLY_FLOOR = 0.0
+
+
+def firefly_params(radius=FIREFLY_RADIUS, rank=FIREFLY_RANK, threshold=FIREFLY_THRESHOLD, floor=FIREFLY_FLOOR, depth_tol=DEPTH_TOL,
+                   normal_tol=NORMAL_TOL):
+    return _abi.DrFireflyParams(int(radius), int(rank), float(threshold), float(floor), float(depth_tol), float(normal_tol))
+
+
+def firefly(rgb, normal, depth, radius=FIREFLY_RADIUS, rank=FIREFLY_RANK, threshold=FIREFLY_THRESHOLD, floor=FIREFLY_FLOOR, depth_tol=DEPTH_TOL,
+            normal_tol=NORMAL_TOL, device=True, return_removed=False):
+    """rgb [h, w, 3], normal [h, w, 3], depth [h, w] -> the clamped [h, w, 3] f32: a pixel whose luminance exceeds
+    threshold * m + floor, m the rank-th largest luminance among the pixels of its (2 radius + 1)^2 window that show the same surface, is
+    scaled down to that limit; every other pixel keeps its bits.  return_removed=True adds the luminance taken away [h, w] (0 where the
+    pixel is unchanged).  device=True: dr_firefly, on the GPU; device=False: dr_firefly_host, which needs none and writes the same bytes."""
+    rgb, normal, depth = _images("firefly", "rgb and normal must be [h, w, 3] and depth [h, w]", (rgb, normal), depth)
+    h, w = depth.shape
+    p = firefly_params(radius, rank, threshold, floor, depth_tol, normal_tol)
+    out = np.zeros_like(rgb)
+    removed = np.zeros_like(depth) if return_removed else None
+    _abi.check(_entry("dr_firefly", device)(rgb.ctypes.data, normal.ctypes.data, depth.ctypes.data, w, h, C.byref(p), out.ctypes.data,
+                  removed.ctypes.data if return_removed else None))
+    return (out, removed) if return_removed else out
+
+
+def _firefly_kw(who, firefly):
+    """The `firefly` keyword of a render_* function as firefly()'s keywords, or None where the stage is off."""
+    if firefly is False or firefly is None:
+        return None
+    if firefly is True:
+        return {}
+    if isinstance(firefly, dict):
+        unknown = sorted(set(firefly) - {"radius", "rank", "threshold", "floor", "depth_tol", "normal_tol", "device"})
+        if unknown:
+            raise ValueError("%s: firefly has no parameter %s" % (who, ", ".join(unknown)))
+        return dict(firefly)
+    raise ValueError("%s: firefly must be False, True or a dict of firefly()'s parameters, got %r" % (who, firefly))
+
+
+def _clamped(kw, rgb, normal, depth):
+    """(rgb after the stage, removed) -- or (rgb, None) where the stage is off (kw None)."""
+    return (rgb, None) if kw is None else firefly(rgb, normal, depth, **dict(kw, return_removed=True))
+
+
+def render_firefly(renderer, scene, normal_channel="ns", **firefly_kw):
+    """Renders the beauty image and the two guides as render_denoised does and clamps its fireflies.  Returns an OutputImage whose rgb is
+    the result; `noisy` (the unclamped render), `normal`, `depth` and `removed` stay on it.  firefly_kw: firefly()'s keywords."""
+    _check_channel("render_firefly", normal_channel)
+    if isinstance(renderer.sampler, AdaptiveSampler):
+        raise ValueError("render_firefly: the adaptive sampler is not supported (the feature integrator refuses it)")
+    beauty = renderer.render(scene)
+    normal, depth = _guides(renderer, scene, normal_channel)
+    rgb, removed = firefly(beauty.rgb, normal, depth, **dict(firefly_kw, return_removed=True))
+    out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, rgb, beauty.film)
+    out.noisy, out.normal, out.depth, out.removed = beauty.rgb, normal, depth, removed
+    return out
+
+
 # The moments filter's own two (DESIGN.md 2.24), SVGF's and reasoned, not tuned on any animation.  min_history: below four frames the sample
 # variance of the per-frame luminance has two degrees of freedom or fewer and is mostly noise itself, so the neighbours are asked instead.
 # radius: a 7 x 7 window is 49 accumulated values, the fewest at which a spatial estimate is steadier than a four-frame temporal one.
@@ -341,14 +433,16 @@ def atrous_moments(frame, iterations=ITERATIONS, sigma_color=SIGMA_COLOR_PAIR, s
 
 
 def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_tol=DEPTH_TOL, normal_tol=NORMAL_TOL, max_history=MAX_HISTORY,
-                    **kw):
+                    firefly=False, **kw):
     """Renders one frame per renderer -- one camera pose each, in the order of the animation -- with its beauty image and two
     FeatureIntegrator images, `normal_channel` ("ns" or "ng") and "depth", as render_denoised does, and accumulates each into the history of
     the frames before it with temporal().  Returns the list of frames: OutputImages whose rgb is the accumulated colour, or with denoise=True
     atrous(accumulated, normal, depth, **kw), or with denoise="moments" atrous_moments(history, **kw), whose last level's variance then stays
     on the frame as `filtered_variance`; the parts stay on each as `noisy` (the frame's own render), `accumulated`, `normal`, `depth`,
     `m2`, `len`, `variance` and `history` (the TemporalFrame).  The history itself is never filtered: the next frame accumulates onto the
-    unfiltered colour.
+    unfiltered colour.  firefly: True, or a dict of firefly()'s parameters, clamps each frame's beauty image before temporal() (DESIGN.md
+    2.25), so that an outlier never enters `rgb`, `m2` or the history; `noisy` stays the unclamped render, and the luminance taken away
+    stays on each frame as `removed`.
 
     Give each renderer's sampler its own seed.  The samplers are keyed by pixel and seed: two frames that share a seed draw the same sample
     pattern in every pixel, so a surface that stays under one pixel is sampled with the same numbers again, the frames' errors are the same
@@ -359,6 +453,7 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
     who = "render_sequence"
     _check_channel(who, normal_channel)
     renderers = list(renderers)
+    fkw = _firefly_kw(who, firefly)
     if not any(denoise is v for v in (False, True)) and denoise != "moments":
         raise ValueError("%s: denoise must be False, True or \"moments\", got %r" % (who, denoise))
     if kw and not denoise:
@@ -378,7 +473,8 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
             guide_sampler.seed = guide_seed
         beauty = r.render(scene)
         normal, depth = _guides(r, scene, normal_channel, guide_sampler)
-        history = temporal(beauty.rgb, normal, depth, history, m, depth_tol=depth_tol, normal_tol=normal_tol, max_history=max_history)
+        clamped, removed = _clamped(fkw, beauty.rgb, normal, depth)
+        history = temporal(clamped, normal, depth, history, m, depth_tol=depth_tol, normal_tol=normal_tol, max_history=max_history)
         filtered_variance = None
         if denoise == "moments":
             rgb, filtered_variance = atrous_moments(history, **dict(kw, return_variance=True, return_estimate=False))
@@ -389,5 +485,7 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
             out.filtered_variance = filtered_variance
         out.noisy, out.accumulated, out.normal, out.depth = beauty.rgb, history.rgb, normal, depth
         out.m2, out.len, out.variance, out.history = history.m2, history.len, history.variance, history
+        if fkw is not None:
+            out.removed = removed
         frames.append(out)
     return frames

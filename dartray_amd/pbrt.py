@@ -1088,10 +1088,13 @@ def _write_pfm(path, rgb):
 
 def main(argv=None):
     """python -m dartray_amd.pbrt scene.pbrt [-o out.pfm|out.npy|out.png|out.ppm] [--spp N] [--xres W --yres H] [--upsample 2|4]
-    [--exposure auto|SCALE] [--tonemap clamp|reinhard|filmic] [--encode srgb|gamma22|reference]
+    [--firefly] [--exposure auto|SCALE] [--tonemap clamp|reinhard|filmic] [--encode srgb|gamma22|reference]
 
     --upsample F traces the beauty image at 1/F of the film's resolution per axis and brings it to the full resolution under full-resolution
     normal and depth images (denoise.render_upsampled).
+
+    --firefly clamps the beauty image's outliers under its normal and depth images with the default parameters (denoise.render_firefly;
+    DESIGN.md 2.25); with --upsample, the low-resolution image's before it is upsampled.
 
     .png and .ppm go through the display transform (dartray_amd/display.py), which the three last flags choose; .npy and
     every other suffix hold the linear f32 radiance."""
@@ -1104,6 +1107,7 @@ def main(argv=None):
     ap.add_argument("--xres", type=int)
     ap.add_argument("--yres", type=int)
     ap.add_argument("--upsample", type=int, choices=[2, 4], help="trace 1/2 or 1/4 of the resolution per axis and upsample under full-resolution guides")
+    ap.add_argument("--firefly", action="store_true", help="clamp pixels far brighter than their same-surface neighbours (two more feature renders)")
     ap.add_argument("--exposure", default="auto", help=".png / .ppm: auto (the median luminance goes to 0.18), or the scale as a number")
     ap.add_argument("--tonemap", default="reinhard", choices=["clamp", "reinhard", "filmic"])
     ap.add_argument("--encode", default="srgb", choices=["srgb", "gamma22", "reference"])
@@ -1125,8 +1129,12 @@ def main(argv=None):
     t1 = time.time()
     if a.upsample:
         from . import denoise
-        out = denoise.render_upsampled(api.lowRendererObject, api.rendererObject, api.scene)
+        out = denoise.render_upsampled(api.lowRendererObject, api.rendererObject, api.scene, firefly=a.firefly)
         st = api.lowRendererObject.last_stats
+    elif a.firefly:
+        from . import denoise
+        out = denoise.render_firefly(api.rendererObject, api.scene)
+        st = api.rendererObject.last_stats
     else:
         out = api.rendererObject.render(api.scene)
         st = api.rendererObject.last_stats

@@ -619,6 +619,38 @@ int dr_temporal_device(const void* rgb_dev, const void* normal_dev, const void* 
                        const void* h_len_dev, const void* h_normal_dev, const void* h_depth_dev, int32_t w, int32_t h,
                        const DrTemporalParams* params, void* out_rgb_dev, void* out_m2_dev, void* out_len_dev, void* hip_stream);
 
+/* Firefly suppression: a guide-aware outlier clamp that runs ahead of the filters and of the temporal history.
+ * rgb[h][w][3], normal[h][w][3] and depth[h][w] are the images of dr_temporal*.  A pixel is valid where its three colour values, three normal
+ * values and depth are finite and its luminance L is finite.  The members of a valid pixel p are the valid pixels q != p of its
+ * (2 radius + 1)^2 window inside the image with |z_q - z_p| <= depth_tol * z_p and a squared distance of the encoded normals <= normal_tol
+ * (dr_temporal*'s agreement test).  With n members, n >= rank, m the rank-th largest member luminance, T = threshold * m + floor and
+ * T0 = T > 0 ? T : 0: where L > T0 the colour is scaled by T0 / L; every other pixel -- invalid, n < rank, or not brighter -- is copied bit
+ * for bit.  out[h][w][3]: the result; removed[h][w], which may be NULL: L - T0 where the pixel was scaled and 0 elsewhere.  The taps read
+ * the original image, so the stage cannot run in place.  f32 arithmetic, one rounding per operator: the entry points below write the same
+ * bytes. */
+typedef struct DrFireflyParams {
+  int32_t radius;   /* 1 or 2: the window is (2 radius + 1)^2 pixels */
+  int32_t rank;     /* 1..4: the member luminance the limit is taken from, counted from the largest */
+  float threshold;  /* finite, >= 0 */
+  float floor;      /* finite, not < 0: added to the limit, in radiance */
+  float depth_tol;  /* as in DrTemporalParams */
+  float normal_tol; /* as in DrTemporalParams */
+} DrFireflyParams; /* 24 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer (removed excepted), w or h < 1, w * h >= 2^31, radius other than 1 or 2, rank outside
+ * 1..4, a threshold, floor or tolerance that is negative or not finite, out or removed overlapping an input or each other.
+ * dr_firefly_check states those of the parameters and the size without an image. */
+int dr_firefly_check(const DrFireflyParams* params, int32_t w, int32_t h);
+/* dr_firefly_host: host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_firefly_host(const float* rgb, const float* normal, const float* depth, int32_t w, int32_t h, const DrFireflyParams* params, float* out,
+                    float* removed);
+/* The same ON THE GPU (dr_firefly_device.hip), host buffers: uploads, one launch, copies back.  Needs dr_init. */
+int dr_firefly(const float* rgb, const float* normal, const float* depth, int32_t w, int32_t h, const DrFireflyParams* params, float* out,
+               float* removed);
+/* The same on device buffers, asynchronous on the given hipStream_t: one kernel launch.  It needs no scratch buffer, so there is no size
+ * query; the parameters are copied at the call and may change as soon as it returns. */
+int dr_firefly_device(const void* rgb_dev, const void* normal_dev, const void* depth_dev, int32_t w, int32_t h, const DrFireflyParams* params,
+                      void* out_dev, void* removed_dev, void* hip_stream);
+
 /* The variance-guided a-trous denoiser over a temporal history (the variance estimate of Schied et al. 2017,
  * section 4.2, in front of the levels of section 2.19): rgb[h][w][3], m2[h][w] and len[h][w] are what dr_temporal* wrote last -- the
  * accumulated colour, the accumulated second moment of its luminance and the history length -- and normal and depth that frame's guides.
@@ -956,7 +988,9 @@ const char* dr_version(void);
  * four new entry points read -- dr_upsample_check, dr_upsample_host, dr_upsample and dr_upsample_device; and temporal accumulation: one new
  * struct, DrTemporalParams, that only its four new entry points read -- dr_temporal_check, dr_temporal_host, dr_temporal and
  * dr_temporal_device; and the moments denoiser: one new struct, DrDenoiseMomentsParams, that only its four new entry points read --
- * dr_denoise_moments_check, dr_denoise_moments_host, dr_denoise_moments and dr_denoise_moments_device). */
+ * dr_denoise_moments_check, dr_denoise_moments_host, dr_denoise_moments and dr_denoise_moments_device; and firefly suppression: one new
+ * struct, DrFireflyParams, that only its four new entry points read -- dr_firefly_check, dr_firefly_host, dr_firefly and
+ * dr_firefly_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -1103,6 +1137,12 @@ DR_ABI_OFFSET(DrDenoiseMomentsParams, k_color, 4);
 DR_ABI_OFFSET(DrDenoiseMomentsParams, var_floor, 16);
 DR_ABI_OFFSET(DrDenoiseMomentsParams, min_history, 20);
 DR_ABI_OFFSET(DrDenoiseMomentsParams, radius, 24);
+DR_ABI_SIZE(DrFireflyParams, 24);
+DR_ABI_OFFSET(DrFireflyParams, rank, 4);
+DR_ABI_OFFSET(DrFireflyParams, threshold, 8);
+DR_ABI_OFFSET(DrFireflyParams, floor, 12);
+DR_ABI_OFFSET(DrFireflyParams, depth_tol, 16);
+DR_ABI_OFFSET(DrFireflyParams, normal_tol, 20);
 
 #ifdef __cplusplus
 }

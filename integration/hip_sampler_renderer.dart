@@ -216,6 +216,16 @@ const int OFF_DrDenoiseMomentsParams_k_depth = 12;
 const int OFF_DrDenoiseMomentsParams_var_floor = 16;
 const int OFF_DrDenoiseMomentsParams_min_history = 20;
 const int OFF_DrDenoiseMomentsParams_radius = 24;
+// DrFireflyParams (firefly suppression, the outlier clamp ahead of the filters, DESIGN.md 2.25): int32 radius (1 or 2: the window is
+// (2 radius + 1)^2 pixels), int32 rank (1..4: the member luminance the limit is taken from), f32 threshold and f32 floor (the limit is
+// threshold * m + floor), then DrTemporalParams' f32 depth_tol and f32 normal_tol
+const int SIZEOF_DrFireflyParams = 24;
+const int OFF_DrFireflyParams_radius = 0;
+const int OFF_DrFireflyParams_rank = 4;
+const int OFF_DrFireflyParams_threshold = 8;
+const int OFF_DrFireflyParams_floor = 12;
+const int OFF_DrFireflyParams_depth_tol = 16;
+const int OFF_DrFireflyParams_normal_tol = 20;
 // DrNurbsPatch (one NURBS patch, DESIGN.md 2.21): per direction int32 n, int32 order, the address of n + order f32 knots and the f32 range;
 // the address of the nu * nv control points (3 floats each, or 4 when homogeneous is 1); uint32 dice rates (0: 30)
 const int SIZEOF_DrNurbsPatch = 72;
@@ -362,6 +372,18 @@ typedef _DenoiseMomentsC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointe
     Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Float>);
 typedef _DenoiseMomentsD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>,
     Pointer<Float>, Pointer<Float>, Pointer<Float>);
+// dr_firefly_check (the refusals of the parameters and the size, without an image) and dr_firefly / dr_firefly_host (firefly suppression on
+// the GPU and on the host, host buffers; DESIGN.md 2.25): rgb[h][w][3], normal[h][w][3], depth[h][w], w, h, DrFireflyParams (24 bytes, the
+// OFF_DrFireflyParams_* offsets above), out[h][w][3], removed[h][w] or null.  dr_firefly_device takes device addresses and a hipStream_t
+// last.  (Signatures only, never compiled, like the rest.)
+typedef _FireflyCheckC = Int32 Function(Pointer<Uint8>, Int32, Int32);
+typedef _FireflyCheckD = int Function(Pointer<Uint8>, int, int);
+typedef _FireflyC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>, Pointer<Float>);
+typedef _FireflyD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>, Pointer<Float>);
+typedef _FireflyDeviceC = Int32 Function(Pointer<Void>, Pointer<Void>, Pointer<Void>, Int32, Int32, Pointer<Uint8>, Pointer<Void>, Pointer<Void>,
+    Pointer<Void>);
+typedef _FireflyDeviceD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Void>, int, int, Pointer<Uint8>, Pointer<Void>, Pointer<Void>,
+    Pointer<Void>);
 // dr_display (the display transform on the GPU, host buffers; DESIGN.md 2.20): rgb[h][w][3], w, h, DrDisplayParams (32 bytes, the
 // OFF_DrDisplayParams_* offsets above), out[h][w][4] bytes R, G, B, A.  (Signature only, never compiled, like the rest.)
 typedef _DisplayC = Int32 Function(Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Uint8>);
@@ -442,6 +464,12 @@ class HipSamplerRenderer extends Renderer {
   /// The variance-guided a-trous denoiser over what `temporal` wrote last: the history's luminance moments give the per-pixel variance
   /// that guides the colour term (after dr_init).
   static final _DenoiseMomentsD denoiseMoments = _lib.lookupFunction<_DenoiseMomentsC, _DenoiseMomentsD>('dr_denoise_moments');
+  /// Firefly suppression: a pixel far brighter than its same-surface neighbours is scaled down to their level, ahead of `temporal` and
+  /// the denoisers (`firefly` and `fireflyDevice` after dr_init; `fireflyHost` and `fireflyCheck` need no GPU).
+  static final _FireflyCheckD fireflyCheck = _lib.lookupFunction<_FireflyCheckC, _FireflyCheckD>('dr_firefly_check');
+  static final _FireflyD fireflyHost = _lib.lookupFunction<_FireflyC, _FireflyD>('dr_firefly_host');
+  static final _FireflyD firefly = _lib.lookupFunction<_FireflyC, _FireflyD>('dr_firefly');
+  static final _FireflyDeviceD fireflyDevice = _lib.lookupFunction<_FireflyDeviceC, _FireflyDeviceD>('dr_firefly_device');
   /// The display transform: linear f32 radiance to RGBA8 through exposure, a tone curve and an 8-bit encode (after dr_init).
   static final _DisplayD displayImage = _lib.lookupFunction<_DisplayC, _DisplayD>('dr_display');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
