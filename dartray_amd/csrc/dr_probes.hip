@@ -24,6 +24,7 @@
 
 #include "dr_host.h"
 #include "dr_rng.h"
+#include "dr_shade_hit.h"  // hit_rec, hit_dg, ray_epsilon
 #include "dr_li_sampling.h"
 
 using namespace dr_host;
@@ -85,11 +86,9 @@ __global__ void __launch_bounds__(256) k_walk_step(DScene sc, DQuadric sph, Walk
   DGeo dg;
   if (h.prim >= 0) {  // scene.intersect(ray, isect)
     t = h.t;
-    const Tri tr = load_tri(sc, (uint32_t)h.prim);
-    if (tr.kind != 0) quadric_dg_at(sc.quads[tr.quad], o, d, t, &dg);
-    else if (sc.srec && __float_as_uint(sc.srec[7 * (size_t)h.prim + 6].x) != 0u) tri_dg_srec(tr, load_srec(sc, (uint32_t)h.prim), o, d, t, &dg);
-    else tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
-    eps = (tr.kind != 0 ? 5.0e-4 : 1.0e-3) * t;
+    const HitRec rec = hit_rec(sc, (uint32_t)h.prim);
+    hit_dg(sc, rec, hit_srec(sc, rec), o, d, t, &dg);
+    eps = ray_epsilon(rec.isQuad, t);
   } else {            // sphere.intersect(ray, isect): the bounding sphere of scene.worldBound
     F3 phit;
     if (!quadric_hit(sph, o, d, w.eps[i], DR_INF, &t, &phit)) {

@@ -14,11 +14,12 @@
 // last stage of a round has no traversal behind it and queues nothing, so the next round's first stage queues without folding.
 //
 // Draws: the two randomUint() are draws 0 and 1 of the sample's keyed in-Li stream (kind 2), in every sampler mode.
-// Per-slot state, in words no other kernel of an AO render touches (no MIS ray, no throughput): W_SCR0, W_SCR1, W_NCLEAR, W_N below.
+// Per-slot state, in words no other kernel of an AO render touches (no MIS ray, no throughput): W_SCR0, W_SCR1 (dr_li_sampling.h), W_NCLEAR, W_N below.
 // F_RO = p, F_RTMIN = minDist and F_SHTMAX = maxDist are written once at the camera hit: every ray of the slot shares them.
 //
 // Launch geometry is k_shade_whitted's (one 512-thread workgroup per CU for the ~64 KB of queue staging); the kernel needs no light or
-// material table.  Compiled with -ffp-contract=off, like every unit.
+// material table; the stage loop, the hit's geometry and the scramble words are the units' shared ones (dr_shade_loop.h, dr_shade_hit.h,
+// dr_li_sampling.h).  Compiled with -ffp-contract=off, like every unit.
 #include "dr_kernels.h"
 #include "dr_rng.h"
 #include "dr_wave.h"
@@ -28,27 +29,22 @@ namespace DR_NS {
 #endif
 
 #include "dr_shade_common.h"
+#include "dr_shade_hit.h"
+#include "dr_shade_loop.h"
 #include "dr_li_sampling.h"
 
-// per-slot words: the scramble (u32 x 2), the clear rays counted so far (i32), n (3 x f32)
-enum { W_SCR0 = F_MISD, W_SCR1 = F_MISD + 1, W_NCLEAR = F_MISPRIM, W_N = F_BETA };
+// per-slot words besides the scramble (dr_li_sampling.h): the clear rays counted so far (i32), n (3 x f32)
+enum { W_NCLEAR = F_MISPRIM, W_N = F_BETA };
 
 __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
     k_shade_ao(DScene sc, RenderParams rp, BatchState st, StageQueues q, int nSamples, int fold, int emit, double minDist, double maxDist) {
   extern __shared__ __align__(16) unsigned char s_dyn[];
   PushStage& s_push = *(PushStage*)s_dyn;
-  PushCtx pctx = {{0, 0, 0, 0}, 0, 0};
-  const uint32_t nIn = q.nActiveIn ? *q.nActiveIn : st.nslots;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const uint32_t nIter = (nIn + stride - 1) / stride;
-  stage_init(s_push);
-  for (uint32_t it = 0; it < nIter; ++it) {
-    const uint32_t idx = it * stride + blockIdx.x * blockDim.x + threadIdx.x;
-    const bool valid = idx < nIn;
+  StageLoop loop = stage_loop_begin(s_push, st, q);
+  for (uint32_t it = 0; it < loop.nIter; ++it) {
     uint32_t slot = 0, pf = 0;
     bool again = false, vert = false;  // again: the slot has another stage; vert: a camera hit was set up here (statistics)
-    if (valid) {
-      slot = q.activeIn ? q.activeIn[idx] : idx;
+    if (stage_loop_slot(loop, q, it, &slot)) {
       const SlotRef sr = SlotRef::of(st, slot);
       bool live = emit != 0;  // (behind the camera hit's stage the lists only hold slots that hit)
       F3 n;
@@ -57,44 +53,25 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
       if (emit == 0) {
         const int prim = sr.i32<F_HPRIM>();
         if (prim >= 0) {
-          const Tri tr = load_tri(sc, (uint32_t)prim);
           const F3 o = ld3f<F_RO>(sr), d = ld3f<F_RD>(sr);
-          const double t = sr.f64<F_HT>();
           DGeo dg, dgs;
-          if (tr.kind != 0) {
-            quadric_dg_at(sc.quads[tr.quad], o, d, t, &dg);
-            dgs = dg;
-          } else if (sc.srec && __float_as_uint(sc.srec[7 * (size_t)prim + 6].x) != 0u) {
-            const ShadeRec srec = load_srec(sc, (uint32_t)prim);
-            tri_dg_srec(tr, srec, o, d, t, &dg);
-            if (srec.flags & (DR_SHADING_N | DR_SHADING_S)) shading_geometry(sc, srec, tr.reverse, dg, &dgs);
-            else dgs = dg;
-          } else {
-            tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
-            dgs = dg;
-          }
+          hit_geometry(sc, hit_rec(sc, (uint32_t)prim), o, d, sr.f64<F_HT>(), &dg, &dgs);
           const F3 p = dgs.p;                                           // bsdf.dgShading.p
           n = vdot(dg.nn, vneg(d)) < 0.0 ? vneg(dg.nn) : dg.nn;         // Normal.FaceForward(isect.dg.nn, -ray.direction) (normal.dart:59-61)
-          DartRandom rng = li_stream(rp, st, slot);
-          scramble[0] = rng.randomUint();
-          scramble[1] = rng.randomUint();
+          new_scramble(rp, st, slot, sr, scramble);
           st3f<F_RO>(sr, p);  // Ray(p, w, minDist, maxDist): minT is minDist, not the intersection's ray epsilon
           sr.f64<F_RTMIN>() = minDist;
           sr.f64<F_SHTMAX>() = maxDist;
           st3f<W_N>(sr, n);
-          sr.u32<W_SCR0>() = scramble[0];
-          sr.u32<W_SCR1>() = scramble[1];
           live = vert = true;
         } else {
-          // the ray left the scene: Li = sum of light.Le(ray) (sampler_renderer.dart:87-92) -- the infinite light's map, else 0
-          stcf<F_L>(sr, sc.hasEnv ? env_Le(sc.env, ld3f<F_RD>(sr)) : C3{0.f, 0.f, 0.f});
+          store_escaped_Le(sc, sr);
         }
       } else {
         nClear = sr.i32<W_NCLEAR>();
         if (emit > 0) {
           n = ld3f<W_N>(sr);
-          scramble[0] = sr.u32<W_SCR0>();
-          scramble[1] = sr.u32<W_SCR1>();
+          load_scramble(sr, scramble);
         }
       }
       if (live) {
@@ -117,12 +94,9 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
       }
       sr.u32<F_FLAGS>() = pf;
     }
-    stage_push(s_push, pctx, false, false, (pf & PF_HAS_SH) != 0, again, slot, Q_MIS_BIT, vert);
-    if (pctx.iters == DR_PUSH_ITERS || it + 1 == nIter)
-      stage_flush(s_push, pctx, q.closestQ, q.nClosest, q.anyQ, q.nAny, q.activeOut, q.nActiveOut, &q.ctr->shade_cont);
+    stage_loop_push(s_push, loop, q, it, false, false, (pf & PF_HAS_SH) != 0, again, slot, Q_MIS_BIT, vert);
   }
-  stage_finish(s_push, pctx, q.closestQ, q.anyQ, q.activeOut, &q.ctr->shade_cont);
-  shade_count(s_push, q.ctr, nIn);
+  stage_loop_end(s_push, loop, q);
 }
 
 void launch_shade_ao(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int nSamples, int fold, int emit,

@@ -2,7 +2,11 @@
 // the light tables, the vertex statistics and the launcher.  RESTATED from dr_kernels.hip word for word (shade_count, the DR_SHADE_* /
 // DR_LDS_* macros, light_table_bytes, mat_table_bytes, stage_lights, launch_shade, lightsInLds), not moved: the committed round-6
 // profiles carry the hash of dr_kernels.hip (tests/test_bench_line.py), so that file changes only together with new profiling passes.
-// When it next does, it should include this header and drop its copies.  Used by dr_shade_whitted.hip.
+// When it next does, it should include this header and drop its copies, and take the helpers that the units share among themselves --
+// dr_shade_hit.h (the hit's geometry, isect.Le, the ray epsilon, the escaped ray, Spectrum.clamp), dr_shade_loop.h (the queue-fed stage
+// loop, the one-lane-per-slot epilogue and launcher) and the scramble words of dr_li_sampling.h -- in place of the copies it holds inline
+// in k_shade_path, k_shade_direct and k_shade_spec.  Only restated text belongs here (tests/test_whitted_integrator.py holds every block
+// against dr_kernels.hip).  Used by the six dr_shade_*.hip units.
 // Included INSIDE the unit's layout namespace (DR_NS), behind dr_kernels.h and dr_wave.h: includes nothing itself.
 #ifndef DR_SHADE_COMMON_H
 #define DR_SHADE_COMMON_H

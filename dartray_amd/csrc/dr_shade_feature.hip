@@ -13,13 +13,18 @@
 // One lane per slot, slots in order (the camera stage has no list), so a wave's reads of the hit record and the camera ray and its store of
 // the radiance are each one run of the tile the state layout was designed around.  The channel is a template parameter: no wave branches on
 // it.  Nothing is queued: the render has one stage and traces nothing but the camera rays.  The geometry comes from dr_device.h's own
-// helpers, as in k_shade_ao's camera-hit part; only (u, v) of a quadric, which quadric_dg does not keep, is restated here (feature_quadric_uv).
+// helpers, through dr_shade_hit.h's pieces; only (u, v) of a quadric, which quadric_dg does not keep, is restated here (feature_quadric_uv).
 // f64 arithmetic, one rounding to the f32 radiance; compiled with -ffp-contract=off, like every unit.
 #include "dr_kernels.h"
+#include "dr_wave.h"
 
 #ifdef DR_NS  // the second state layout (-DDR_SUB=4 -DDR_NS=sp4): every symbol in its own namespace
 namespace DR_NS {
 #endif
+
+#include "dr_shade_common.h"
+#include "dr_shade_hit.h"
+#include "dr_shade_loop.h"
 
 #define DR_FEATURE_BLOCK 256
 
@@ -49,8 +54,7 @@ DR_DEV C3 feature_normal(F3 nn) {  // 0.5 * (n + 1), per component
 template <int CHANNEL>
 __global__ void __launch_bounds__(DR_FEATURE_BLOCK) k_shade_feature(DScene sc, BatchState st, TraceCounters* ctr) {
   __shared__ uint32_t s_hits;
-  if (threadIdx.x == 0) s_hits = 0u;
-  __syncthreads();
+  per_slot_begin(s_hits);
   const uint32_t stride = gridDim.x * blockDim.x;
   uint32_t hits = 0u;
   for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < st.nslots; slot += stride) {
@@ -63,62 +67,50 @@ __global__ void __launch_bounds__(DR_FEATURE_BLOCK) k_shade_feature(DScene sc, B
       if (CHANNEL == DR_FEATURE_DEPTH) {
         L = C3{(float)t, (float)t, (float)t};
       } else {
-        const Tri tr = load_tri(sc, (uint32_t)prim);
         if (CHANNEL == DR_FEATURE_ID) {
-          L = C3{(float)((double)prim + 1.0), (float)((double)tr.mat + 1.0), 1.0f};
+          L = C3{(float)((double)prim + 1.0), (float)((double)load_tri(sc, (uint32_t)prim).mat + 1.0), 1.0f};
         } else {
+          const HitRec h = hit_rec(sc, (uint32_t)prim);
+          const Tri& tr = h.tr;
+          const ShadeRec srec = hit_srec(sc, h);
           const F3 o = ld3f<F_RO>(sr), d = ld3f<F_RD>(sr);
           DGeo dg = {}, dgs = {};
-          if (tr.kind != 0) {
-            const DQuadric q = sc.quads[tr.quad];
-            if (CHANNEL == DR_FEATURE_UV) feature_quadric_uv(q, o, d, t, &dg.u, &dg.v);
-            else quadric_dg_at(q, o, d, t, &dg);
-            dgs = dg;  // Shape.getShadingGeometry: a copy
-          } else if (sc.srec && __float_as_uint(sc.srec[7 * (size_t)prim + 6].x) != 0u) {
-            const ShadeRec srec = load_srec(sc, (uint32_t)prim);
-            tri_dg_srec(tr, srec, o, d, t, &dg);
-            if (CHANNEL == DR_FEATURE_NS && (srec.flags & (DR_SHADING_N | DR_SHADING_S))) shading_geometry(sc, srec, tr.reverse, dg, &dgs);
-            else dgs = dg;
-          } else if (CHANNEL == DR_FEATURE_UV) {
+          if (CHANNEL == DR_FEATURE_UV && h.isQuad) {
+            feature_quadric_uv(sc.quads[tr.quad], o, d, t, &dg.u, &dg.v);
+          } else if (CHANNEL == DR_FEATURE_UV && !h.hasRec) {
             // Triangle.getUVs without a uv array (triangle.dart:255-262) and the interpolation of :134-137, on the accepting test's barycentrics
             double tt, b1 = 0.0, b2 = 0.0;
             (void)tri_hit(tr.p1, tr.p2, tr.p3, o, d, -DR_INF, DR_INF, &tt, &b1, &b2);
             const double b0 = 1.0 - b1 - b2;
             dg.u = b0 * 0.0 + b1 * 1.0 + b2 * 1.0;
             dg.v = b0 * 0.0 + b1 * 0.0 + b2 * 1.0;
-            dgs = dg;
           } else {
-            tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
-            dgs = dg;
+            hit_dg(sc, h, srec, o, d, t, &dg);
           }
-          if (CHANNEL == DR_FEATURE_NG) L = feature_normal(dg.nn);
-          else if (CHANNEL == DR_FEATURE_NS) L = feature_normal(dgs.nn);
-          else L = C3{(float)dg.u, (float)dg.v, 0.f};
+          if (CHANNEL == DR_FEATURE_NG) {
+            L = feature_normal(dg.nn);
+          } else if (CHANNEL == DR_FEATURE_NS) {
+            hit_dgs(sc, h, srec, dg, &dgs);  // (a quadric's Shape.getShadingGeometry: a copy)
+            L = feature_normal(dgs.nn);
+          } else {
+            L = C3{(float)dg.u, (float)dg.v, 0.f};
+          }
         }
       }
     }
     stcf<F_L>(sr, L);
     sr.u32<F_FLAGS>() = 0u;
   }
-  // DrRenderStats.shade_items / shade_vertices, as shade_count keeps them: one atomic per workgroup
-  if (hits) atomicAdd(&s_hits, hits);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_hits) atomicAdd(&ctr->shade_vertices, (unsigned long long)s_hits);
-    if (blockIdx.x == 0) atomicAdd(&ctr->shade_items, (unsigned long long)st.nslots);
-  }
+  per_slot_end(s_hits, hits, ctr, st.nslots);
 }
 
 void launch_shade_feature(const DScene& sc, const BatchState& st, const StageQueues& q, int channel, int grid, hipStream_t s) {
-  if (st.nslots == 0) return;
-  const unsigned need = (st.nslots + DR_FEATURE_BLOCK - 1) / DR_FEATURE_BLOCK, most = (unsigned)grid * 8u;  // (grid: the CUs; 8 workgroups of 256 each)
-  const dim3 g(need < most ? need : most), b(DR_FEATURE_BLOCK);
   switch (channel) {  // (planRender refused every other value)
-    case DR_FEATURE_NG: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_NG>, g, b, 0, s, sc, st, q.ctr); break;
-    case DR_FEATURE_NS: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_NS>, g, b, 0, s, sc, st, q.ctr); break;
-    case DR_FEATURE_DEPTH: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_DEPTH>, g, b, 0, s, sc, st, q.ctr); break;
-    case DR_FEATURE_UV: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_UV>, g, b, 0, s, sc, st, q.ctr); break;
-    case DR_FEATURE_ID: hipLaunchKernelGGL(k_shade_feature<DR_FEATURE_ID>, g, b, 0, s, sc, st, q.ctr); break;
+    case DR_FEATURE_NG: launch_per_slot<k_shade_feature<DR_FEATURE_NG>, DR_FEATURE_BLOCK>(grid, st.nslots, s, sc, st, q.ctr); break;
+    case DR_FEATURE_NS: launch_per_slot<k_shade_feature<DR_FEATURE_NS>, DR_FEATURE_BLOCK>(grid, st.nslots, s, sc, st, q.ctr); break;
+    case DR_FEATURE_DEPTH: launch_per_slot<k_shade_feature<DR_FEATURE_DEPTH>, DR_FEATURE_BLOCK>(grid, st.nslots, s, sc, st, q.ctr); break;
+    case DR_FEATURE_UV: launch_per_slot<k_shade_feature<DR_FEATURE_UV>, DR_FEATURE_BLOCK>(grid, st.nslots, s, sc, st, q.ctr); break;
+    case DR_FEATURE_ID: launch_per_slot<k_shade_feature<DR_FEATURE_ID>, DR_FEATURE_BLOCK>(grid, st.nslots, s, sc, st, q.ctr); break;
   }
 }
 

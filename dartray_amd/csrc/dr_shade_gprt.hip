@@ -25,7 +25,8 @@
 // = bsdf.nn, W_SN = bsdf.sn = Normalize(dgShading.dpdu) (tn = Cross(nn, sn) is recomputed); F_RO = p, F_RTMIN = rayEpsilon, F_SHTMAX = infinity
 // written once at the camera hit; F_RD keeps the camera ray's direction (wo = -F_RD); F_SHD is the ray in flight.
 //
-// Compiled with -ffp-contract=off, like every unit; atan2 / sin / cos of the rotation angles are f64.
+// k_shade_gprt's launch geometry is k_shade_ao's; its stage loop, the hit's geometry and the scramble words are the units' shared ones
+// (dr_shade_loop.h, dr_shade_hit.h, dr_li_sampling.h).  Compiled with -ffp-contract=off, like every unit; atan2 / sin / cos of the rotation angles are f64.
 #include "dr_kernels.h"
 #include "dr_rng.h"
 #include "dr_wave.h"
@@ -37,72 +38,49 @@ namespace DR_NS {
 #endif
 
 #include "dr_shade_common.h"
+#include "dr_shade_hit.h"
+#include "dr_shade_loop.h"
 #include "dr_li_sampling.h"
 
-// per-slot words: the scramble (u32 x 2), nn (3 x f32), sn (3 x f32)
-enum { W_SCR0 = F_MISD, W_SCR1 = F_MISD + 1, W_NN = F_BETA, W_SN = F_BETANEE };
+// per-slot words besides the scramble (dr_li_sampling.h): nn (3 x f32), sn (3 x f32)
+enum { W_NN = F_BETA, W_SN = F_BETANEE };
 
 __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
     k_shade_gprt(DScene sc, RenderParams rp, BatchState st, StageQueues q, GprtArgs a, int fold, int emit) {
   extern __shared__ __align__(16) unsigned char s_dyn[];
   PushStage& s_push = *(PushStage*)s_dyn;
-  PushCtx pctx = {{0, 0, 0, 0}, 0, 0};
-  const uint32_t nIn = q.nActiveIn ? *q.nActiveIn : st.nslots;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const uint32_t nIter = (nIn + stride - 1) / stride;
-  stage_init(s_push);
-  for (uint32_t it = 0; it < nIter; ++it) {
-    const uint32_t idx = it * stride + blockIdx.x * blockDim.x + threadIdx.x;
-    const bool valid = idx < nIn;
+  StageLoop loop = stage_loop_begin(s_push, st, q);
+  for (uint32_t it = 0; it < loop.nIter; ++it) {
     uint32_t slot = 0, pf = 0;
     bool again = false, vert = false;  // again: the slot has another stage; vert: a camera hit was set up here (statistics)
-    if (valid) {
-      slot = q.activeIn ? q.activeIn[idx] : idx;
+    if (stage_loop_slot(loop, q, it, &slot)) {
       const SlotRef sr = SlotRef::of(st, slot);
       bool live = emit != 0;  // (behind the camera hit's stage the lists only hold slots that hit)
       uint32_t scramble[2];
       if (emit == 0) {
         const int prim = sr.i32<F_HPRIM>();
         if (prim >= 0) {
-          const Tri tr = load_tri(sc, (uint32_t)prim);
+          const HitRec h = hit_rec(sc, (uint32_t)prim);
           const F3 o = ld3f<F_RO>(sr), d = ld3f<F_RD>(sr);
           const F3 wo = vneg(d);
           const double t = sr.f64<F_HT>();
           DGeo dg, dgs;
-          if (tr.kind != 0) {
-            quadric_dg_at(sc.quads[tr.quad], o, d, t, &dg);
-            dgs = dg;
-          } else if (sc.srec && __float_as_uint(sc.srec[7 * (size_t)prim + 6].x) != 0u) {
-            const ShadeRec srec = load_srec(sc, (uint32_t)prim);
-            tri_dg_srec(tr, srec, o, d, t, &dg);
-            if (srec.flags & (DR_SHADING_N | DR_SHADING_S)) shading_geometry(sc, srec, tr.reverse, dg, &dgs);
-            else dgs = dg;
-          } else {
-            tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
-            dgs = dg;
-          }
-          const C3 Le = tr.light >= 0 ? light_L(sc.lights[tr.light], dg.nn, wo) : C3{0.f, 0.f, 0.f};  // intersection.dart:60-63
-          stcf<F_L>(sr, cadd(C3{0.f, 0.f, 0.f}, Le));                  // L = Spectrum(0); L += isect.Le(wo)
-          DartRandom rng = li_stream(rp, st, slot);
-          scramble[0] = rng.randomUint();
-          scramble[1] = rng.randomUint();
+          hit_geometry(sc, h, o, d, t, &dg, &dgs);
+          stcf<F_L>(sr, cadd(C3{0.f, 0.f, 0.f}, hit_Le(sc.lights, h.tr, dg.nn, wo)));  // L = Spectrum(0); L += isect.Le(wo)
+          new_scramble(rp, st, slot, sr, scramble);
           st3f<F_RO>(sr, dgs.p);  // Ray(p, w, rayEpsilon), p = bsdf.dgShading.p: infinite extent
-          sr.f64<F_RTMIN>() = (tr.kind != 0 ? 5.0e-4 : 1.0e-3) * t;  // isect.rayEpsilon (triangle.dart:157; sphere.dart:169, disk.dart:98)
+          sr.f64<F_RTMIN>() = ray_epsilon(h.isQuad, t);
           sr.f64<F_SHTMAX>() = DR_INF;
           st3f<W_NN>(sr, dgs.nn);                   // bsdf.dart:45-51: nn = dgShading.nn, sn = Normalize(dgShading.dpdu)
           st3f<W_SN>(sr, vnormalize(dgs.dpdu));
-          sr.u32<W_SCR0>() = scramble[0];
-          sr.u32<W_SCR1>() = scramble[1];
           a.mark[slot] = 1u;
           live = vert = true;
         } else {
-          // the ray left the scene: Li = sum of light.Le(ray) (sampler_renderer.dart:87-92) -- the infinite light's map, else 0
-          stcf<F_L>(sr, sc.hasEnv ? env_Le(sc.env, ld3f<F_RD>(sr)) : C3{0.f, 0.f, 0.f});
+          store_escaped_Le(sc, sr);
           a.mark[slot] = 0u;
         }
       } else {
-        scramble[0] = sr.u32<W_SCR0>();
-        scramble[1] = sr.u32<W_SCR1>();
+        load_scramble(sr, scramble);
       }
       if (live) {
         if (fold >= 0) {  // bit fold & 31 of word fold >> 5: `!scene.intersectP(...)`; the first bit of a word sets the whole word
@@ -121,12 +99,9 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
       }
       sr.u32<F_FLAGS>() = pf;
     }
-    stage_push(s_push, pctx, false, false, (pf & PF_HAS_SH) != 0, again, slot, Q_MIS_BIT, vert);
-    if (pctx.iters == DR_PUSH_ITERS || it + 1 == nIter)
-      stage_flush(s_push, pctx, q.closestQ, q.nClosest, q.anyQ, q.nAny, q.activeOut, q.nActiveOut, &q.ctr->shade_cont);
+    stage_loop_push(s_push, loop, q, it, false, false, (pf & PF_HAS_SH) != 0, again, slot, Q_MIS_BIT, vert);
   }
-  stage_finish(s_push, pctx, q.closestQ, q.anyQ, q.activeOut, &q.ctr->shade_cont);
-  shade_count(s_push, q.ctr, nIn);
+  stage_loop_end(s_push, loop, q);
 }
 
 #define GPRT_WAVES 2
@@ -163,10 +138,7 @@ __global__ void __launch_bounds__(64 * GPRT_WAVES) k_gprt_finish(BatchState st, 
     const bool active = slot < st.nslots && a.mark[slot < st.nslots ? slot : 0u] != 0u;
     const SlotRef sr = SlotRef::of(st, active ? slot : 0u);
     uint32_t scramble[2] = {0u, 0u};
-    if (active) {
-      scramble[0] = sr.u32<W_SCR0>();
-      scramble[1] = sr.u32<W_SCR1>();
-    }
+    if (active) load_scramble(sr, scramble);
     float acc[GPRT_EPL];
 #pragma unroll
     for (int qi = 0; qi < GPRT_EPL; ++qi) acc[qi] = 0.f;  // T[i] = Spectrum(0)
@@ -248,8 +220,7 @@ __global__ void __launch_bounds__(64 * GPRT_WAVES) k_gprt_finish(BatchState st, 
     if (active && lane == 0) {
       C3 Li = C3{0.f, 0.f, 0.f};
       for (int i = 0; i < terms; ++i) Li = cadd(Li, cmulD(C3{sCo[wv][3 * i], sCo[wv][3 * i + 1], sCo[wv][3 * i + 2]}, (double)sYo[wv][i]));  // Li += c_o[i] * Ylm[i]
-      const C3 Lc = C3{Li.r < 0.f || Li.r == 0.f ? 0.f : Li.r, Li.g < 0.f || Li.g == 0.f ? 0.f : Li.g, Li.b < 0.f || Li.b == 0.f ? 0.f : Li.b};  // Li.clamp()
-      stcf<F_L>(sr, cadd(ldcf<F_L>(sr), Lc));  // L += Li.clamp()
+      stcf<F_L>(sr, cadd(ldcf<F_L>(sr), clamp0_poszero(Li)));  // L += Li.clamp()
     }
     __syncthreads();
   }

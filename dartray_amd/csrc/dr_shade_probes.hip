@@ -13,11 +13,16 @@
 // is queued: one launch per batch, one lane per slot, slots in order, as in k_shade_feature.  An escaped camera ray stores the lights' Le(ray).
 // Compiled with -ffp-contract=off, like every unit.
 #include "dr_kernels.h"
+#include "dr_wave.h"
 #include "dr_probes.h"
 
 #ifdef DR_NS  // the second state layout (-DDR_SUB=4 -DDR_NS=sp4): every symbol in its own namespace
 namespace DR_NS {
 #endif
+
+#include "dr_shade_common.h"
+#include "dr_shade_hit.h"
+#include "dr_shade_loop.h"
 
 #define DR_PROBES_BLOCK 256
 
@@ -34,8 +39,7 @@ DR_DEV C3 probes_ld(const float* p) { return C3{p[0], p[1], p[2]}; }
 
 __global__ void __launch_bounds__(DR_PROBES_BLOCK) k_shade_probes(DScene sc, BatchState st, ProbeArgs a, TraceCounters* ctr) {
   __shared__ uint32_t s_hits;
-  if (threadIdx.x == 0) s_hits = 0u;
-  __syncthreads();
+  per_slot_begin(s_hits);
   // SphericalHarmonics.ConvolveCosTheta's table (spherical_harmonics.dart:529-533); lmax <= 8
   const double c_costheta[9] = {0.8862268925, 1.0233267546, 0.4954159260, 0.0000000000, -0.1107783690, 0.0000000000, 0.0499271341, 0.0000000000, -0.0285469331};
   const int terms = sh_terms(a.lmax);
@@ -47,25 +51,13 @@ __global__ void __launch_bounds__(DR_PROBES_BLOCK) k_shade_probes(DScene sc, Bat
     C3 L;
     if (prim >= 0) {
       ++hits;
-      const Tri tr = load_tri(sc, (uint32_t)prim);
+      const HitRec h = hit_rec(sc, (uint32_t)prim);
+      const Tri& tr = h.tr;
       const F3 o = ld3f<F_RO>(sr), d = ld3f<F_RD>(sr);
       const F3 wo = vneg(d);
-      const double t = sr.f64<F_HT>();
       DGeo dg, dgs;
-      if (tr.kind != 0) {
-        quadric_dg_at(sc.quads[tr.quad], o, d, t, &dg);
-        dgs = dg;
-      } else if (sc.srec && __float_as_uint(sc.srec[7 * (size_t)prim + 6].x) != 0u) {
-        const ShadeRec srec = load_srec(sc, (uint32_t)prim);
-        tri_dg_srec(tr, srec, o, d, t, &dg);
-        if (srec.flags & (DR_SHADING_N | DR_SHADING_S)) shading_geometry(sc, srec, tr.reverse, dg, &dgs);
-        else dgs = dg;
-      } else {
-        tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
-        dgs = dg;
-      }
-      const C3 Le = tr.light >= 0 ? light_L(sc.lights[tr.light], dg.nn, wo) : C3{0.f, 0.f, 0.f};  // intersection.dart:60-63
-      L = cadd(C3{0.f, 0.f, 0.f}, Le);                                       // L = Spectrum(0); L += isect.Le(wo)
+      hit_geometry(sc, h, o, d, sr.f64<F_HT>(), &dg, &dgs);
+      L = cadd(C3{0.f, 0.f, 0.f}, hit_Le(sc.lights, tr, dg.nn, wo));       // L = Spectrum(0); L += isect.Le(wo)
       const F3 p = dgs.p, n = dgs.nn;
       // bbox.offset(p) (bbox.dart:193-197)
       const F3 off = f3(((double)p.x - (double)a.bmin[0]) / ((double)a.bmax[0] - (double)a.bmin[0]),
@@ -104,28 +96,18 @@ __global__ void __launch_bounds__(DR_PROBES_BLOCK) k_shade_probes(DScene sc, Bat
       }
       const C3 R = clamp0(sc.mats[4 * (size_t)tr.mat]);            // Kd.evaluate(dgs).clamp() (matte_material.dart:54)
       const C3 rho = cblack(R) ? C3{0.f, 0.f, 0.f} : cadd(C3{0.f, 0.f, 0.f}, R);
-      const C3 Ec = C3{E.r < 0.f || E.r == 0.f ? 0.f : E.r, E.g < 0.f || E.g == 0.f ? 0.f : E.g, E.b < 0.f || E.b == 0.f ? 0.f : E.b};  // E.clamp()
-      L = cadd(L, cmul(cmulD(rho, DR_INV_PI), Ec));                // L += rho * INV_PI * E.clamp()
+      L = cadd(L, cmul(cmulD(rho, DR_INV_PI), clamp0_poszero(E)));  // L += rho * INV_PI * E.clamp()
     } else {
-      // the ray left the scene: Li = sum of light.Le(ray) (sampler_renderer.dart:87-92) -- the infinite light's map, else 0
-      L = sc.hasEnv ? env_Le(sc.env, ld3f<F_RD>(sr)) : C3{0.f, 0.f, 0.f};
+      L = escaped_Le(sc, sr);
     }
     stcf<F_L>(sr, L);
     sr.u32<F_FLAGS>() = 0u;
   }
-  // DrRenderStats.shade_items / shade_vertices, as shade_count keeps them: one atomic per workgroup
-  if (hits) atomicAdd(&s_hits, hits);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_hits) atomicAdd(&ctr->shade_vertices, (unsigned long long)s_hits);
-    if (blockIdx.x == 0) atomicAdd(&ctr->shade_items, (unsigned long long)st.nslots);
-  }
+  per_slot_end(s_hits, hits, ctr, st.nslots);
 }
 
 void launch_shade_probes(const DScene& sc, const BatchState& st, const StageQueues& q, const ProbeArgs& a, int grid, hipStream_t s) {
-  if (st.nslots == 0) return;
-  const unsigned need = (st.nslots + DR_PROBES_BLOCK - 1) / DR_PROBES_BLOCK, most = (unsigned)grid * 8u;  // (grid: the CUs; 8 workgroups of 256 each)
-  hipLaunchKernelGGL(k_shade_probes, dim3(need < most ? need : most), dim3(DR_PROBES_BLOCK), 0, s, sc, st, a, q.ctr);
+  launch_per_slot<k_shade_probes, DR_PROBES_BLOCK>(grid, st.nslots, s, sc, st, a, q.ctr);
 }
 
 #ifdef DR_NS

@@ -23,7 +23,8 @@
 // (a Vector: three f32, exactly what Evaluate is given).  The Terms(lmax) transfer coefficients (the three channels are always equal: one f32
 // per term) do not fit the path state: they live in the render's side buffer c[term][stride] (Workspace::prt; stride: the slots of this render's largest batch), which both state layouts index alike.
 //
-// Launch geometry is k_shade_ao's.  Compiled with -ffp-contract=off, like every unit.
+// Launch geometry is k_shade_ao's; the hit's geometry and the scramble words are the units' shared ones (dr_shade_hit.h,
+// dr_li_sampling.h).  Compiled with -ffp-contract=off, like every unit.
 #include "dr_kernels.h"
 #include "dr_rng.h"
 #include "dr_wave.h"
@@ -34,20 +35,23 @@ namespace DR_NS {
 #endif
 
 #include "dr_shade_common.h"
+#include "dr_shade_hit.h"
 #include "dr_li_sampling.h"
 
-// per-slot words: the scramble (u32 x 2), n (3 x f32), Kd = rho2 * INV_PI (3 x f32)
-enum { W_SCR0 = F_MISD, W_SCR1 = F_MISD + 1, W_N = F_BETA, W_KD = F_BETANEE };
+// per-slot words besides the scramble (dr_li_sampling.h): n (3 x f32), Kd = rho2 * INV_PI (3 x f32)
+enum { W_N = F_BETA, W_KD = F_BETANEE };
 
 __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
     k_shade_prt(DScene sc, RenderParams rp, BatchState st, StageQueues q, PrtArgs a, int fold, int emit) {
   extern __shared__ __align__(16) unsigned char s_dyn[];
   PushStage& s_push = *(PushStage*)s_dyn;
+  const int terms = sh_terms(a.lmax);
+  // The stage loop is written out here, not dr_shade_loop.h's StageLoop: on StageLoop this kernel's 4096 fold stages took 0.4 % longer
+  // (269.0 against 267.9 ms of shading, outside the parent's run-to-run spread; MEASUREMENTS.md) at unchanged registers and scratch.
   PushCtx pctx = {{0, 0, 0, 0}, 0, 0};
   const uint32_t nIn = q.nActiveIn ? *q.nActiveIn : st.nslots;
   const uint32_t stride = gridDim.x * blockDim.x;
   const uint32_t nIter = (nIn + stride - 1) / stride;
-  const int terms = sh_terms(a.lmax);
   stage_init(s_push);
   for (uint32_t it = 0; it < nIter; ++it) {
     const uint32_t idx = it * stride + blockIdx.x * blockDim.x + threadIdx.x;
@@ -64,51 +68,34 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
       if (emit == 0) {
         const int prim = sr.i32<F_HPRIM>();
         if (prim >= 0) {
-          const Tri tr = load_tri(sc, (uint32_t)prim);
+          const HitRec h = hit_rec(sc, (uint32_t)prim);
+          const Tri& tr = h.tr;
           const F3 o = ld3f<F_RO>(sr), d = ld3f<F_RD>(sr);
           const F3 wo = vneg(d);
           const double t = sr.f64<F_HT>();
           DGeo dg, dgs;
-          if (tr.kind != 0) {
-            quadric_dg_at(sc.quads[tr.quad], o, d, t, &dg);
-            dgs = dg;
-          } else if (sc.srec && __float_as_uint(sc.srec[7 * (size_t)prim + 6].x) != 0u) {
-            const ShadeRec srec = load_srec(sc, (uint32_t)prim);
-            tri_dg_srec(tr, srec, o, d, t, &dg);
-            if (srec.flags & (DR_SHADING_N | DR_SHADING_S)) shading_geometry(sc, srec, tr.reverse, dg, &dgs);
-            else dgs = dg;
-          } else {
-            tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
-            dgs = dg;
-          }
-          const C3 Le = tr.light >= 0 ? light_L(sc.lights[tr.light], dg.nn, wo) : C3{0.f, 0.f, 0.f};  // intersection.dart:60-63
-          stcf<F_L>(sr, cadd(C3{0.f, 0.f, 0.f}, Le));                  // L = Spectrum(0); L += isect.Le(wo)
+          hit_geometry(sc, h, o, d, t, &dg, &dgs);
+          stcf<F_L>(sr, cadd(C3{0.f, 0.f, 0.f}, hit_Le(sc.lights, tr, dg.nn, wo)));  // L = Spectrum(0); L += isect.Le(wo)
           const F3 p = dgs.p;                                          // bsdf.dgShading.p
           n = vdot(dgs.nn, wo) < 0.0 ? vneg(dgs.nn) : dgs.nn;          // Normal.FaceForward(bsdf.dgShading.nn, wo) (normal.dart:59-61)
-          DartRandom rng = li_stream(rp, st, slot);
-          scramble[0] = rng.randomUint();
-          scramble[1] = rng.randomUint();
+          new_scramble(rp, st, slot, sr, scramble);
           // bsdf.rho2(wo, rng, BSDF_ALL_REFLECTION) * INV_PI for the one Lambertian lobe of a matte material (none when Kd is black):
           // ret = Spectrum(0) + R (bsdf.dart:232-247, lambertian.dart:39-41)
           const C3 R = clamp0(sc.mats[4 * (size_t)tr.mat]);            // Kd.evaluate(dgs).clamp() (matte_material.dart:54)
           const C3 rho = cblack(R) ? C3{0.f, 0.f, 0.f} : cadd(C3{0.f, 0.f, 0.f}, R);
           stcf<W_KD>(sr, cmulD(rho, DR_INV_PI));
           st3f<F_RO>(sr, p);  // Ray(p, w, rayEpsilon): infinite extent
-          sr.f64<F_RTMIN>() = (tr.kind != 0 ? 5.0e-4 : 1.0e-3) * t;  // isect.rayEpsilon (triangle.dart:157; sphere.dart:169, disk.dart:98)
+          sr.f64<F_RTMIN>() = ray_epsilon(h.isQuad, t);
           sr.f64<F_SHTMAX>() = DR_INF;
           st3f<W_N>(sr, n);
-          sr.u32<W_SCR0>() = scramble[0];
-          sr.u32<W_SCR1>() = scramble[1];
           for (int j = 0; j < terms; ++j) c[(size_t)j * a.stride] = 0.f;  // c_transfer[i] = Spectrum(0)
           live = vert = true;
         } else {
-          // the ray left the scene: Li = sum of light.Le(ray) (sampler_renderer.dart:87-92) -- the infinite light's map, else 0
-          stcf<F_L>(sr, sc.hasEnv ? env_Le(sc.env, ld3f<F_RD>(sr)) : C3{0.f, 0.f, 0.f});
+          store_escaped_Le(sc, sr);
         }
       } else {
         n = ld3f<W_N>(sr);
-        scramble[0] = sr.u32<W_SCR0>();
-        scramble[1] = sr.u32<W_SCR1>();
+        load_scramble(sr, scramble);
       }
       if (live) {
         // ray `fold`, if the previous stage queued it and nothing stopped it: `Dot(w, n) > 0 && !scene.intersectP(...)`
@@ -139,8 +126,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true))
             const float cj = c[(size_t)j * a.stride];
             Lo = cadd(Lo, cmul(C3{a.cin[3 * j], a.cin[3 * j + 1], a.cin[3 * j + 2]}, C3{cj, cj, cj}));  // Lo += c_in[i] * c_transfer[i]
           }
-          const C3 Lc = C3{Lo.r < 0.f || Lo.r == 0.f ? 0.f : Lo.r, Lo.g < 0.f || Lo.g == 0.f ? 0.f : Lo.g, Lo.b < 0.f || Lo.b == 0.f ? 0.f : Lo.b};  // Lo.clamp()
-          stcf<F_L>(sr, cadd(ldcf<F_L>(sr), cmul(ldcf<W_KD>(sr), Lc)));  // L + Kd * Lo.clamp()
+          stcf<F_L>(sr, cadd(ldcf<F_L>(sr), cmul(ldcf<W_KD>(sr), clamp0_poszero(Lo))));  // L + Kd * Lo.clamp()
         } else {
           again = true;
         }

@@ -20,7 +20,8 @@
 // slot words no other kernel of a Whitted render touches (there is no MIS ray): W_LO, W_HI, W_NR, W_CALLS below.
 //
 // Launch geometry and LDS use are k_shade_direct's general form: one 512-thread workgroup per CU, 2 waves per SIMD, the light and
-// material tables in LDS where they fit.  Compiled with -ffp-contract=off, like every unit.
+// material tables in LDS where they fit; the stage loop and the pieces of the hit's geometry are the units' shared ones (dr_shade_loop.h,
+// dr_shade_hit.h).  Compiled with -ffp-contract=off, like every unit.
 #include <type_traits>
 
 #include "dr_kernels.h"
@@ -32,6 +33,8 @@ namespace DR_NS {
 #endif
 
 #include "dr_shade_common.h"
+#include "dr_shade_hit.h"
+#include "dr_shade_loop.h"
 #include "dr_li_sampling.h"  // li_stream
 
 // per-slot words of the draw numbering: the stream's generator state behind the last draw made (u32 lo, hi), the vertices shaded so far
@@ -42,53 +45,37 @@ template <bool LLDS>
 __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true)) k_shade_whitted(DScene sc, RenderParams rp, BatchState st, StageQueues q, int stage) {
   extern __shared__ __align__(16) unsigned char s_dyn[];
   PushStage& s_push = *(PushStage*)s_dyn;
-  PushCtx pctx = {{0, 0, 0, 0}, 0, 0};
   using LV = typename std::conditional<LLDS, LdsLights, GlobalLights>::type;
   LV lv;
   if constexpr (LLDS) lv = stage_lights(sc, s_dyn, push_stage_bytes(SHADE_BLOCK_OF(true)));
   else lv = GlobalLights{sc.lights, sc.ltris, sc.lcdf, sc.mats};
-  const uint32_t nIn = q.nActiveIn ? *q.nActiveIn : st.nslots;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const uint32_t nIter = (nIn + stride - 1) / stride;
   const int nLights = rp.nLights;
-  stage_init(s_push);
-  for (uint32_t it = 0; it < nIter; ++it) {
-    const uint32_t idx = it * stride + blockIdx.x * blockDim.x + threadIdx.x;
-    const bool valid = idx < nIn;
+  StageLoop loop = stage_loop_begin(s_push, st, q);
+  for (uint32_t it = 0; it < loop.nIter; ++it) {
     uint32_t slot = 0, pf = 0;
     bool again = false, vert = false;  // again: the vertex has another stage; vert: a vertex was set up here (statistics)
-    if (valid) {
-      slot = q.activeIn ? q.activeIn[idx] : idx;
+    if (stage_loop_slot(loop, q, it, &slot)) {
       const SlotRef sr = SlotRef::of(st, slot);
       const uint32_t flags = stage == 0 ? 0u : sr.u32<F_FLAGS>();
       const int prim = sr.i32<F_HPRIM>();
       if (prim >= 0) {
-        Tri tr = load_tri(sc, (uint32_t)prim);
+        const HitRec h = hit_rec(sc, (uint32_t)prim);
+        const Tri& tr = h.tr;
         const F3 d = ld3f<F_RD>(sr);
         const F3 wo = vneg(d);
         C3 L;
         DartRandom rng;  // the sample's in-Li stream, at this stage's first draw
         DGeo dg, dgs;
-        const bool isQuad = tr.kind != 0;
-        const bool hasRec = !isQuad && sc.srec && __float_as_uint(sc.srec[7 * (size_t)prim + 6].x) != 0u;
-        ShadeRec srec;
-        if (hasRec) srec = load_srec(sc, (uint32_t)prim);
+        const ShadeRec srec = hit_srec(sc, h);
+        const bool fromRay = h.isQuad || h.hasRec;  // later stages and k_shade_spec rebuild such a hit from the ray: F_RO0 keeps its origin
         if (stage == 0) {
           const F3 o = ld3f<F_RO>(sr);
           const double t = sr.f64<F_HT>();
-          if (isQuad) {
-            quadric_dg_at(sc.quads[tr.quad], o, d, t, &dg);
-            st3f<F_RO0>(sr, o);  // later stages and k_shade_spec rebuild the hit from the ray
-          } else if (hasRec) {
-            tri_dg_srec(tr, srec, o, d, t, &dg);
-            st3f<F_RO0>(sr, o);
-          } else {
-            tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, o, d, t, &dg);
-          }
-          const C3 Le = tr.light >= 0 ? light_L(lv.light(tr.light), dg.nn, wo) : C3{0.f, 0.f, 0.f};  // intersection.dart:60-63
-          L = cadd(C3{0.f, 0.f, 0.f}, Le);  // L = Spectrum(0); L += isect.Le(wo)
+          hit_dg(sc, h, srec, o, d, t, &dg);
+          if (fromRay) st3f<F_RO0>(sr, o);
+          L = cadd(C3{0.f, 0.f, 0.f}, hit_Le(lv, tr, dg.nn, wo));  // L = Spectrum(0); L += isect.Le(wo)
           st3f<F_RO>(sr, dg.p);
-          sr.f64<F_RTMIN>() = (isQuad ? 5.0e-4 : 1.0e-3) * t;  // isect.rayEpsilon (triangle.dart:157; sphere.dart:169, disk.dart:98)
+          sr.f64<F_RTMIN>() = ray_epsilon(h.isQuad, t);
           // Where this vertex's draws start in the sample's stream: behind everything the reference has drawn before it calls Li here.
           // The stored state stands behind the previous vertex's last light draw; since then only Specular* calls have drawn, each a
           // BSDFSample.random(rng) -- 3 randomFloat(), 6 generator steps -- whether or not a lobe exists.  Calls made before this vertex
@@ -111,9 +98,8 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true)) k_
           sr.i32<W_CALLS>() = calls;
           vert = true;
         } else {
-          if (isQuad) quadric_dg_at(sc.quads[tr.quad], ld3f<F_RO0>(sr), d, sr.f64<F_HT>(), &dg);
-          else if (hasRec) tri_dg_srec(tr, srec, ld3f<F_RO0>(sr), d, sr.f64<F_HT>(), &dg);
-          else tri_dg(tr.p1, tr.p2, tr.p3, tr.reverse, F3{0, 0, 0}, d, 0.0, &dg);
+          // (a plain triangle's dpdu, dpdv and nn do not depend on the ray)
+          hit_dg(sc, h, srec, fromRay ? ld3f<F_RO0>(sr) : F3{0, 0, 0}, d, fromRay ? sr.f64<F_HT>() : 0.0, &dg);
           dg.p = ld3f<F_RO>(sr);
           rng.lo = sr.u32<W_LO>();
           rng.hi = sr.u32<W_HI>();
@@ -122,8 +108,7 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true)) k_
           if ((flags & PF_HAS_SH) && sr.i32<F_SHOCC>() == 0) L = cadd(L, ldcf<F_LD1>(sr));
         }
         if (stage < nLights) {
-          if (hasRec && (srec.flags & (DR_SHADING_N | DR_SHADING_S))) shading_geometry(sc, srec, tr.reverse, dg, &dgs);
-          else dgs = dg;
+          hit_dgs(sc, h, srec, dg, &dgs);
           Bsdf bsdf = make_bsdf<true>(lv, dgs, tr.mat);  // isect.getBSDF(ray)
           bsdf.ng = dg.nn;
           const F3 p = bsdf.p, n = bsdf.nn;  // bsdf.dgShading.p / .nn
@@ -204,17 +189,13 @@ __global__ void __launch_bounds__(SHADE_BLOCK_OF(true), SHADE_WAVES_OF(true)) k_
         }
         stcf<F_L>(sr, L);
       } else if (stage == 0) {
-        // the ray left the scene: Li = sum of light.Le(ray) (sampler_renderer.dart:87-92) -- the infinite light's map, else 0
-        stcf<F_L>(sr, sc.hasEnv ? env_Le(sc.env, ld3f<F_RD>(sr)) : C3{0.f, 0.f, 0.f});
+        store_escaped_Le(sc, sr);
       }
       sr.u32<F_FLAGS>() = pf;
     }
-    stage_push(s_push, pctx, false, false, (pf & PF_HAS_SH) != 0, again, slot, Q_MIS_BIT, vert);
-    if (pctx.iters == DR_PUSH_ITERS || it + 1 == nIter)
-      stage_flush(s_push, pctx, q.closestQ, q.nClosest, q.anyQ, q.nAny, q.activeOut, q.nActiveOut, &q.ctr->shade_cont);
+    stage_loop_push(s_push, loop, q, it, false, false, (pf & PF_HAS_SH) != 0, again, slot, Q_MIS_BIT, vert);
   }
-  stage_finish(s_push, pctx, q.closestQ, q.anyQ, q.activeOut, &q.ctr->shade_cont);
-  shade_count(s_push, q.ctr, nIn);
+  stage_loop_end(s_push, loop, q);
 }
 
 void launch_shade_whitted(const DScene& sc, const RenderParams& rp, const BatchState& st, const StageQueues& q, int stage, int grid, hipStream_t s) {

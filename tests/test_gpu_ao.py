@@ -38,14 +38,22 @@ def _prims():
             core.GeometricPrimitive(core.Sphere(at.m, at.mInv, True, 1.0), core.MatteMaterial((0.5, 0.5, 0.5)), None)]
 
 
+def _leaning():
+    """A small tilted quad with per-vertex N that lean away from its plane (a shading record with DR_SHADING_N).  The integrator reads
+    isect.dg.nn and dgShading.p, which Triangle.getShadingGeometry leaves alone, so the restatement's plain triangles stay its reference."""
+    mesh = core.TriangleMesh(np.array([[0, 1, 2], [0, 2, 3]], np.uint32), np.array([(0.2, 0.2, -2.5), (0.2, 1.2, -1.5), (2.4, 1.2, -1.5), (2.4, 0.2, -2.5)], np.float32),
+                             n=np.array([(0.3, 0.7, -0.6), (-0.2, 0.9, -0.3), (-0.3, 0.8, -0.5), (0.4, 0.6, -0.7)], np.float32))
+    return core.GeometricPrimitive(mesh, core.MatteMaterial((0.5, 0.5, 0.5)), None)
+
+
 class Setup:
     """One scene on both sides: `scene` for the device, `restated` for tests/ao_restatement.py.  wide: a camera that also sees past the
     floor, under a constant infinite light (the Le route of an escaped camera ray)."""
 
-    def __init__(self, wide=False):
-        prims = _prims()
+    def __init__(self, wide=False, leaning=False):
+        prims = _prims() + ([_leaning()] if leaning else [])
         self.env = core.InfiniteAreaLight(None, (1.0, 1.0, 1.0), 1, np.full((2, 4, 3), (0.5, 0.6, 0.9), np.float32)) if wide else None
-        accel = core.BVHAccel(prims)
+        accel = self.accel = core.BVHAccel(prims)
         self.scene = core.Scene(accel, accel.lights() + ([self.env] if wide else []))
         self.restated = mrf.build_scene(prims, self.env)
         film = core.ImageFilm(8, 8, core.BoxFilter(0.5, 0.5))
@@ -190,6 +198,32 @@ def test_both_state_layouts_give_the_same_film(yard, layout):
     def run():
         film = yard.device_film((256,), _ld(yard))
         return film, yard.scene._device().last_render_info()
+    got, info = _with_option("STATE_LAYOUT", layout, run)
+    assert info["state_layout"] == layout and _same(got, want)
+
+
+# ---- 5b. every branch of the camera hit's geometry: quadric, triangle with per-vertex N, plain triangle ----
+@pytest.fixture(scope="module")
+def yard_n(gpu):
+    return Setup(leaning=True)
+
+
+@pytest.mark.parametrize("layout", [64, 4])
+def test_a_mesh_with_vertex_normals_among_the_camera_hits(yard_n, layout):
+    want, pixels, vec = yard_n.restated_film((4,), _ld(yard_n), "ld")
+    rcam = mrf.restated_camera(yard_n.camera)
+    hits = [yard_n.restated.bvh.intersect(rcam.generateRay(int(px) + float(v[0]), int(py) + float(v[1]), float(v[2]), float(v[3])))
+            for (px, py), v in zip(np.repeat(pixels, 2, axis=0), vec)]
+    on_mesh = sum(h is not None and abs(h.dg.p.y - (h.dg.p.z + 2.7)) < 1e-3 and 0.2 < h.dg.p.y < 1.2 for h in hits)   # the leaning quad's plane y = z + 2.7
+    on_sphere = sum(h is not None and isinstance(h.prim.shape, ao.dr.Sphere) for h in hits)
+    on_floor = sum(h is not None and h.dg.p.y == 0.0 for h in hits)
+    print("camera hits: %d on the mesh with N, %d on the sphere, %d on the floor" % (on_mesh, on_sphere, on_floor))
+    assert on_mesh >= 2 and on_sphere >= 2 and on_floor >= 2
+    flags = yard_n.accel.tri_shading
+    assert flags is not None and (flags & 1).any() and (flags == 0).any()   # DR_SHADING_N on the mesh's triangles, no record on the others
+
+    def run():
+        return yard_n.device_film((4,), _ld(yard_n)), yard_n.scene._device().last_render_info()
     got, info = _with_option("STATE_LAYOUT", layout, run)
     assert info["state_layout"] == layout and _same(got, want)
 

@@ -231,6 +231,32 @@ def test_both_state_layouts_give_the_same_film(yard, layout):
     assert info["state_layout"] == layout and _same(got, want)
 
 
+@pytest.fixture(scope="module")
+def yard_sphere(gpu):
+    """The yard and a matte sphere of reversed orientation on the floor in front of the blocker: with the plain floor and the leaning quad's
+    per-vertex N, every branch of the camera hit's geometry (quadric, triangle with DR_SHADING_N, plain triangle)."""
+    from dartray_amd import pbrt
+    at = pbrt.Transform.Translate(2.0, 1.5, -2.6)
+    ball = core.GeometricPrimitive(core.Sphere(at.m, at.mInv, True, 1.5), core.MatteMaterial((0.4, 0.5, 0.6)), None)
+    return Setup(_yard_prims() + [ball])
+
+
+@pytest.mark.parametrize("layout", [64, 4])
+def test_a_quadric_among_the_camera_hits(yard_sphere, layout):
+    s = yard_sphere
+    want, pixels, vec = s.restated_film((2, 8), _ld(s), "ld")
+    hits = _camera_hits(s, pixels, vec)
+    on = [sum(h is not None and isinstance(h.prim.shape, cls) for h in hits) for cls in (prt.dr.Sphere, prt.fe.Triangle)]
+    on.append(sum(h is not None and type(h.prim.shape) is prt.dr.Triangle for h in hits))
+    print("camera hits: %d on the sphere, %d on the mesh with N, %d on plain triangles" % tuple(on))
+    assert min(on) >= 2
+
+    def run():
+        return s.device_film((2, 8), _ld(s)), s.scene._device().last_render_info()
+    got, info = _with_option("STATE_LAYOUT", layout, run)
+    assert info["state_layout"] == layout and _same(got, want)
+
+
 @pytest.mark.parametrize("name", ["random", "stratified"])
 def test_other_samplers_equal_the_restatement_fed_their_vectors(yard, name):
     mk = {"stratified": lambda: core.StratifiedSampler(yard.camera, 2, 1, True, SEED), "random": lambda: core.RandomSampler(yard.camera, 2, SEED)}[name]

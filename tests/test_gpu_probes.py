@@ -235,13 +235,16 @@ class Film:
     """The film scene: the room with the leaning mesh, an area light and a point light; the grid is baked on the device over the world bound at
     spacing 2.5 (3 x 2 x 3 cells) -- its equality with the restatement is section 3's -- and both sides read the same array."""
 
-    def __init__(self):
+    def __init__(self, extra=(), grid=None):
         pt = T.Translate(1.6, 2.5, -1.0)
-        self.s = Setup(_prims(emitter=4, leaning=True), None, [core.PointLight(pt.m, (30.0, 26.0, 22.0))])
+        self.s = Setup(_prims(emitter=4, leaning=True) + list(extra), None, [core.PointLight(pt.m, (30.0, 26.0, 22.0))])
+        self.films = {}
+        if grid is not None:   # (a grid baked elsewhere: both sides still read the same array)
+            self.grid = grid
+            return
         self.grid = self.s.r.create_probes(self.s.scene, 2, 2.5, npoints=NPOINTS)
         # a second grid over the small bounds: most hits lie outside it, where the corner clamp holds the edge cells' values
         self.small = self.s.r.create_probes(self.s.scene, 2, GRID_SPACING, GRID_BOUNDS, npoints=NPOINTS)
-        self.films = {}
 
     def renderer(self, grid, sampler):
         return core.SamplerRenderer(sampler, self.s.camera, core.UseProbesIntegrator(grid), core.EmissionIntegrator())
@@ -308,6 +311,37 @@ def test_stratified_sampler_and_both_state_layouts(film):
         assert info["integrator"] == "useprobes" and info["shade_kernels"] == ["k_shade_probes"]
         st = r.last_stats
         assert st["any_launches"] == 0 and st["any_rays"] == 0 and st["closest_launches"] == 1 and 0 < st["shade_vertices"] <= st["camera_samples"]
+
+
+BALL_C, BALL_R = (-1.1, 0.9, 0.6), 0.9
+
+
+@pytest.fixture(scope="module")
+def ball(film):
+    """The film scene and a matte sphere of reversed orientation standing on the floor beside the box: with the room's plain quads and the leaning
+    quad's per-vertex N, every branch of the camera hit's geometry (quadric, triangle with DR_SHADING_N, plain triangle).  The bake refuses a scene
+    with a quadric (it finds no world bound), so the grid is the film scene's: the integrator only reads it."""
+    at = T.Translate(*BALL_C)
+    return Film([core.GeometricPrimitive(core.Sphere(at.m, at.mInv, True, BALL_R), core.MatteMaterial((0.4, 0.5, 0.6)), None)], grid=film.grid)
+
+
+@pytest.mark.parametrize("layout", [64, 4])
+def test_a_quadric_among_the_camera_hits(ball, layout):
+    want, pixels, vec, integ = ball.restated(ball.grid, _ld(ball, 1), ("grid", "ld", 1))
+    rcam = mrf.restated_camera(ball.s.camera)
+    hits = [ball.s.restated.bvh.intersect(rcam.generateRay(int(px) + float(v[0]), int(py) + float(v[1]), float(v[2]), float(v[3]))) for (px, py), v in zip(pixels, vec)]
+    on = [sum(h is not None and isinstance(h.prim.shape, cls) for h in hits) for cls in (prt.dr.Sphere, prt.fe.Triangle)]
+    on.append(sum(h is not None and type(h.prim.shape) is prt.dr.Triangle for h in hits))
+    print("camera hits: %d on the sphere, %d on the mesh with N, %d on plain triangles" % tuple(on))
+    assert min(on) >= 2
+    lib = _abi.lib()
+    try:
+        _abi.check(lib.dr_set_option(b"STATE_LAYOUT", str(layout).encode()))
+        got = ball.renderer(ball.grid, _ld(ball, 1)).render(ball.s.scene).film
+        info = ball.s.scene._device().last_render_info()
+    finally:
+        lib.dr_set_option(b"STATE_LAYOUT", None)
+    assert info["state_layout"] == layout and _same(got, want)
 
 
 def test_halton_sampler_against_the_restatement(film):

@@ -11,6 +11,7 @@ import pytest
 
 from dartray_amd import _abi, core, pbrt, scenes
 
+import prt_restatement as prt
 import whitted_restatement as wr
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -28,7 +29,15 @@ def _quad(p0, p1, p2, p3, material, light=None):
     return core.GeometricPrimitive(mesh, material, light)
 
 
-def _prims(sphere=True, area=True, specular=True):
+def _leaning():
+    """A tilted matte quad near the floor in front of the glass with per-vertex N that lean away from its plane: a shading record with
+    DR_SHADING_N, so its BSDF is built on Triangle.getShadingGeometry's frame."""
+    mesh = core.TriangleMesh(np.array([[0, 1, 2], [0, 2, 3]], np.uint32), np.array([(2.5, -9.5, -4.0), (2.5, -6.0, -0.5), (6.0, -6.0, -0.5), (6.0, -9.5, -4.0)], np.float32),
+                             n=np.array([(0.3, 0.7, -0.6), (-0.2, 0.9, -0.3), (-0.3, 0.8, -0.5), (0.4, 0.6, -0.7)], np.float32))
+    return core.GeometricPrimitive(mesh, core.MatteMaterial((0.6, 0.5, 0.4)), None)
+
+
+def _prims(sphere=True, area=True, specular=True, leaning=False):
     """A closed box of matte quads (the camera is inside) with one emissive triangle under the ceiling, a mirror quad in front of the
     left wall, a glass sphere and a glass triangle mesh."""
     s = 10.0
@@ -44,6 +53,8 @@ def _prims(sphere=True, area=True, specular=True):
         if sphere:
             at = T.Translate(-1.0, -6.5, 2.0)
             prims.append(core.GeometricPrimitive(core.Sphere(at.m, at.mInv, False, 3.0), core.GlassMaterial((1.0, 1.0, 1.0), (1.0, 0.95, 0.9), 1.5)))
+    if leaning:
+        prims.append(_leaning())
     return prims
 
 
@@ -76,6 +87,8 @@ class Setup:
         accel = core.BVHAccel(prims)
         self.scene = core.Scene(accel, accel.lights() + lights + ([self.env] if env else []))
         self.restated = mrf.build_scene(prims, None)
+        if kw.get("leaning"):
+            prt.with_shading_geometry(self.restated, accel)
         self.restated.lights += restated_lights
         if env:
             e = self.env
@@ -231,6 +244,36 @@ def test_both_state_layouts_give_the_same_film(box, layout):
     def run():
         film = box.renderer(5, _ld(box, 2)).render(box.scene).film
         return film, box.scene._device().last_render_info()
+    got, info = _with_option("STATE_LAYOUT", layout, run)
+    assert info["state_layout"] == layout and _same(got, want)
+
+
+@pytest.fixture(scope="module")
+def box_n(gpu):
+    """The box with the leaning quad: with the walls' plain triangles and the glass sphere, every branch of the hit geometry."""
+    return Setup(leaning=True)
+
+
+@pytest.mark.parametrize("layout", [64, 4])
+def test_a_mesh_with_vertex_normals_among_the_hits(box_n, layout, monkeypatch):
+    """The restatement builds its BSDF on Triangle.getShadingGeometry's frame (tests/prt_restatement.py's getBSDF over
+    tests/feature_restatement.py's Triangle); every other shape keeps the geometric frame, as before."""
+    monkeypatch.setattr(wr, "getBSDF", prt.getBSDF)
+    want, pixels, vec = box_n.restated_film(2, _ld(box_n, 2), "ld2")
+    rcam = mrf.restated_camera(box_n.camera)
+    hits = [box_n.restated.bvh.intersect(rcam.generateRay(int(px) + float(v[0]), int(py) + float(v[1]), float(v[2]), float(v[3])))
+            for (px, py), v in zip(np.repeat(pixels, 2, axis=0), vec)]
+    on = [sum(h is not None and isinstance(h.prim.shape, cls) for h in hits) for cls in (wr.dr.Sphere, prt.fe.Triangle)]
+    on.append(sum(h is not None and type(h.prim.shape) is wr.dr.Triangle for h in hits))
+    print("camera hits: %d on the sphere, %d on the mesh with N, %d on plain triangles" % tuple(on))
+    assert min(on) >= 2
+    for h in hits:
+        if h is not None and isinstance(h.prim.shape, prt.fe.Triangle):
+            assert prt.Dot(prt.getBSDF(h).nn, h.dg.nn) < 0.999   # the shading normal is not the geometric one
+
+    def run():
+        film = box_n.renderer(2, _ld(box_n, 2)).render(box_n.scene).film
+        return film, box_n.scene._device().last_render_info()
     got, info = _with_option("STATE_LAYOUT", layout, run)
     assert info["state_layout"] == layout and _same(got, want)
 

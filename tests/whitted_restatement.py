@@ -74,6 +74,8 @@ class SpotLight(PointLight):
 # ---------------------------------------------------------------------------------------------------------------
 def WhittedLi(scene, ray, isect, rng, maxDepth):
     L = RGB(0.0)                                                   # :28
+    # (this module's getBSDF keeps the geometric frame: no golden scene has per-vertex N / S.  tests/test_gpu_whitted.py's case with such a
+    # mesh sets the name to prt_restatement.getBSDF, which applies Triangle.getShadingGeometry first and is the same function elsewhere.)
     bsdf = getBSDF(isect)                                          # :32
     p = bsdf.p                                                     # :35  bsdf.dgShading.p
     n = bsdf.nn                                                    # :36  bsdf.dgShading.nn

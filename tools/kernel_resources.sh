@@ -1,14 +1,21 @@
 #!/bin/bash
-# Per-kernel register / LDS / scratch usage of the library's kernels (hipcc -Rpass-analysis=kernel-resource-usage), both state layouts.
+# Per-kernel register / LDS / scratch usage of the library's kernels (hipcc -Rpass-analysis=kernel-resource-usage): every unit that is
+# compiled per state layout, in both layouts, and dr_probes.hip.
 #   tools/kernel_resources.sh [OUT]     (CPU only: hipcc cross-compiles gfx950)
 set -u
 root="$(cd "$(dirname "$0")/.." && pwd)"
 out="${1:-/dev/stdout}"
 cd "$root/dartray_amd/csrc"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function -x hip -c --cuda-device-only -Rpass-analysis=kernel-resource-usage -o /dev/null"
+# Every source that is compiled per state layout in both layouts, and dr_probes.hip, whose walk shares the shading units' hit geometry,
+# in the one layout it has.  The lists are read, in one call, from __graft_entry__.py, which only defines names when it is imported.
+lists="$(cd "$root" && python3 -c 'import __graft_entry__ as g; print(" ".join(g.SECOND_LAYOUT["sources"])); print(" ".join(g.SECOND_LAYOUT["flags"]))')" || exit 1
+two="$(echo "$lists" | sed -n 1p)"
+sp4="$(echo "$lists" | sed -n 2p)"
 {
-for src in dr_trace.hip dr_kernels.hip dr_sampler_strat.hip dr_sampler_adaptive.hip dr_sampler_halton.hip dr_sampler_random.hip; do
-  for lay in "" "-DDR_SUB=4 -DDR_NS=sp4 -DDR_STATE_WORDS_K=48 -DDR_GROUPED=1"; do
+for src in $two dr_probes.hip; do
+  for lay in "" "$sp4"; do
+    [ "$src" = dr_probes.hip ] && [ -n "$lay" ] && continue
     /opt/rocm/bin/hipcc $F $lay $src 2>&1 | python3 -c '
 import re, sys
 name = None
