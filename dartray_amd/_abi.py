@@ -211,6 +211,14 @@ class DrFireflyParams(C.Structure):
                 ("normal_tol", C.c_float)]
 
 
+DR_GUIDES_MAX = 5
+
+
+class DrGuidesDesc(C.Structure):
+    """The channels of a guide render (dr_render_guides_check / dr_render_guides / dr_render_guides_device): include/dartray_hip.h."""
+    _fields_ = [("count", C.c_int32), ("channels", C.c_int32 * DR_GUIDES_MAX)]
+
+
 class DrNurbsPatch(C.Structure):
     """One NURBS patch (dr_nurbs_dice / dr_nurbs_dice_device): include/dartray_hip.h."""
     _fields_ = [("nu", C.c_int32), ("uorder", C.c_int32), ("uknots", C.c_void_p), ("u0", C.c_float), ("u1", C.c_float),
@@ -305,6 +313,11 @@ EXPORTS = {
     "dr_render": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_device": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_void_p, C.c_void_p]),
     "dr_render_sharded": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.c_int32, C.c_void_p, C.c_void_p]),
+    "dr_render_guides_check": (C.c_int, [C.POINTER(DrRenderDesc), C.POINTER(DrGuidesDesc), C.c_uint64]),
+    "dr_render_guides": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.POINTER(DrGuidesDesc), C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "dr_render_guides_device": (C.c_int, [C.c_void_p, C.POINTER(DrRenderDesc), C.POINTER(DrGuidesDesc), C.c_void_p, C.POINTER(C.c_void_p),
+                                          C.c_void_p]),
     "dr_film_resolve_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "dr_enumerate_pixels": (C.c_int, [C.POINTER(DrRenderDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "dr_scene_get_adaptive_pixels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -44,6 +44,34 @@ def _guides(renderer, scene, normal_channel, sampler=None):
     return normal, np.ascontiguousarray(_rerender(renderer, scene, FeatureIntegrator("depth"), sampler).rgb[..., 0])
 
 
+def _check_one_pass(who, one_pass, renderer=None, scene=None, normal_channel="ns"):
+    """The `one_pass` keyword of a render_* function: a bool, and -- True with a renderer -- one that dr_render_guides_check accepts for
+    `renderer` (its refusal raises ValueError naming the integrator or the sampler, before anything is rendered)."""
+    if one_pass is not True and one_pass is not False:
+        raise ValueError("%s: one_pass must be False or True, got %r" % (who, one_pass))
+    if one_pass and renderer is not None:
+        try:
+            renderer.guides_desc(scene, (normal_channel, "depth"))
+        except ValueError as e:
+            raise ValueError("%s: one_pass=True: %s" % (who, e)) from e
+
+
+def _render_with_guides(renderer, scene, normal_channel):
+    """(beauty OutputImage, normal [h, w, 3], depth [h, w]) from ONE render of `renderer` (SamplerRenderer.render_with_guides):
+    the beauty image render() returns and the two images _guides renders separately."""
+    beauty = renderer.render_with_guides(scene, (normal_channel, "depth"))
+    return beauty, beauty.guides[normal_channel], np.ascontiguousarray(beauty.guides["depth"][..., 0])
+
+
+def _beauty_and_guides(renderer, scene, normal_channel, one_pass):
+    """(beauty, normal, depth): three renders, or with one_pass one."""
+    if one_pass:
+        return _render_with_guides(renderer, scene, normal_channel)
+    beauty = renderer.render(scene)
+    normal, depth = _guides(renderer, scene, normal_channel)
+    return beauty, normal, depth
+
+
 def _whole_film_refusals(who, name, r, what, each=True):
     """What a function that cannot work on a part of the film asks of renderer `r`, called `name` in the refusal.  `what` is the stage's
     noun; each=False names tileCount and taskCount in one refusal."""

@@ -527,6 +527,48 @@ class SamplerRenderer:
         self.last_stats = dev.stats()
         return OutputImage(film.left, film.top, film.width, film.height, out_rgb, out_film)
 
+    def guides_desc(self, scene, channels):
+        """(DrRenderDesc, the arrays it points into, DrGuidesDesc) of render_with_guides(scene, channels), checked: the integrator's and the
+        sampler's own rules (describe), then dr_render_guides_check, whose refusal raises ValueError with the library's text.  Needs no device."""
+        channels = tuple(channels)
+        unknown = [c for c in channels if c not in FeatureIntegrator.CHANNELS]
+        if unknown:
+            raise ValueError("render guides: channel must be one of ng, ns, depth, uv, id (got %r)" % (unknown[0],))
+        d, keep = self.describe()
+        g = _abi.DrGuidesDesc()
+        g.count = len(channels)
+        for i, c in enumerate(channels[:_abi.DR_GUIDES_MAX]):
+            g.channels[i] = FeatureIntegrator.CHANNELS[c]
+        lib = _abi.lib()
+        if lib.dr_render_guides_check(C.byref(d), C.byref(g), len(scene.aggregate.tri_idx)) != _abi.DR_OK:
+            raise ValueError("%s (surface integrator %s, sampler %s)" % (lib.dr_last_error().decode(), type(self.surfaceIntegrator).__name__,
+                                                                       type(self.sampler).__name__))
+        return d, keep, g
+
+    def render_with_guides(self, scene, channels=("ns", "depth")):
+        """render(), and in the same pass the FeatureIntegrator images of `channels` (dr_render_guides): the OutputImage of
+        render() with `guides`, a dict channel -> [h, w, 3] f32, and `guide_films`, channel -> [h, w, 4], on it.  Each equals what a render
+        of FeatureIntegrator(channel) with this renderer's camera, sampler and work split returns.  Path, DirectLighting, Whitted and
+        ambient occlusion integrators; any other, and the adaptive sampler, raise ValueError before anything is rendered."""
+        channels = tuple(channels)
+        d, keep, g = self.guides_desc(scene, channels)
+        film = self.camera.film
+        out_film = np.zeros((film.height, film.width, 4), dtype=np.float32)
+        out_rgb = np.zeros((film.height, film.width, 3), dtype=np.float32)
+        films = [np.zeros((film.height, film.width, 4), dtype=np.float32) for _ in channels]
+        rgbs = [np.zeros((film.height, film.width, 3), dtype=np.float32) for _ in channels]
+        film_ptrs = (C.c_void_p * len(channels))(*[a.ctypes.data for a in films])
+        rgb_ptrs = (C.c_void_p * len(channels))(*[a.ctypes.data for a in rgbs])
+        dev = scene._device()
+        dev.reset_stats()
+        _abi.check(_abi.lib().dr_render_guides(dev.handle, C.byref(d), C.byref(g), out_film.ctypes.data, out_rgb.ctypes.data, film_ptrs, rgb_ptrs))
+        del keep
+        self.last_stats = dev.stats()
+        out = OutputImage(film.left, film.top, film.width, film.height, out_rgb, out_film)
+        out.guides = dict(zip(channels, rgbs))
+        out.guide_films = dict(zip(channels, films))
+        return out
+
     def supersampled_pixels(self, scene):
         """The raster pixels the last render of `scene` traced at maxSamples ([n, 2] int32, no particular order; AdaptiveSampler)."""
         return scene._device().adaptive_pixels()

@@ -299,6 +299,12 @@ int32_t dr_sample_floats(int32_t integrator, uint32_t nlights) {
   return integratorSlots(knownIntegrator(integrator) ? (IntegratorKind)integrator : IntegratorKind::DirectAll, nullptr, nlights).nFloats();
 }
 
+int dr_render_guides_check(const DrRenderDesc* desc, const DrGuidesDesc* guides, uint64_t nprimitives) {
+  int code = DR_OK;
+  if (const char* why = guidesRefusal(desc, guides, nprimitives, &code)) return fail(code, why);
+  return DR_OK;
+}
+
 int dr_feature_check(int32_t channel, uint64_t nprimitives) {
   int code = DR_OK;
   if (const char* why = featureRefusal(channel, nprimitives, &code)) return fail(code, why);
@@ -721,7 +727,8 @@ int planBatches(RenderPlan& P) {
                              (sf.compact ? (uint64_t)(16 * sf.nBlocks + spp - 1) / spp : 0) +  // scramble words + generator states, per (block, pixel)
                              (P.dlSpec ? (uint64_t)std::max(1, rd->max_depth) * sizeof(SpecFrame) + 12 : 0) +
                              (P.prt.lmax ? (uint64_t)sh_terms(P.prt.lmax) * 4 + 8 : 0) +  // diffuse PRT: the slot's transfer coefficients + the round lists
-                             (P.gprt.lmax ? (uint64_t)P.gprt.words * 4 + 4 + 8 : 0);  // glossy PRT: the slot's visibility words, its hit mark + the round lists
+                             (P.gprt.lmax ? (uint64_t)P.gprt.words * 4 + 4 + 8 : 0) +  // glossy PRT: the slot's visibility words, its hit mark + the round lists
+                             (uint64_t)P.guides.n * 12;  // a guide render: a side plane of three floats per channel
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
       const uint64_t have = (uint64_t)sc->ws.cap * ((uint64_t)sc->ws.stateWords * 4 + sc->ws.svWords / 16 + 20);
@@ -816,6 +823,11 @@ int prepareRender(RenderPlan& P) {
     HIP_TRY(sc->ws.gprtMark.alloc((size_t)P.wsCap));
     rc = gprtBsdfMatrix(sc, P.gprt.lmax, 1024, rd->camera.shutter_open, P.s);
     if (rc) return rc;
+  }
+  if (P.guides.n) {
+    // the side planes, [3 * channels][this plan's batch capacity, which planBatches shrank to fit them, in whole tiles]
+    sc->ws.guidesCap = (P.wsCap + 63u) & ~63u;
+    HIP_TRY(sc->ws.guides.alloc(3 * (size_t)P.guides.n * (size_t)sc->ws.guidesCap));
   }
   if (P.envStage) HIP_TRY(sc->ws.envQ.alloc(sc->ws.cap));
   P.tgrid = traceGrid();
@@ -919,12 +931,8 @@ int32_t lastInfoWord(const RenderPlan& P) {
   return -1;
 }
 
-}  // namespace
-
-extern "C" {
-
-int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* hip_stream) {
-  if (!sc || !rd || !film_dev) return fail(DR_ERR_INVALID, "null argument");
+// dr_render_device, and dr_render_guides_device (g set, checked by the caller: the films of its channels in guideFilms).
+int renderDevice(DrScene* sc, const DrRenderDesc* rd, void* film_dev, const DrGuidesDesc* g, void* const* guideFilms, void* hip_stream) {
   RenderPlan P;
   P.sc = sc;
   P.rd = rd;
@@ -932,6 +940,14 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
   P.s = (hipStream_t)hip_stream;
   int rc = planRender(P);
   if (rc) return rc;
+  if (g) {
+    P.guides.n = g->count;
+    for (int i = 0; i < g->count; ++i) P.guides.mask |= 1u << g->channels[i];
+    for (int i = 0; i < g->count; ++i) {
+      P.guides.film[i] = (float*)guideFilms[i];
+      P.guides.plane[i] = __builtin_popcount(P.guides.mask & ((1u << g->channels[i]) - 1u));  // (planes in DR_FEATURE_* order: k_guides)
+    }
+  }
   // recycle the events of earlier renders once they have completed (or when too many are pending)
   if (sc->lastEvent && !sc->traceEvents.empty()) {
     hipError_t q = hipEventQuery(sc->lastEvent);
@@ -997,6 +1013,24 @@ int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* 
   sc->lastInfo[6] = P.tgrid / std::max(1, g_numCU);
   sc->lastInfo[7] = (P.overlapAny ? 1 : 0) | (P.coherentCamera && !sc->d.nquads ? 2 : 0) | (P.lazyGen || lazy2 ? 8 : 0);
   return DR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dr_render_device(DrScene* sc, const DrRenderDesc* rd, void* film_dev, void* hip_stream) {
+  if (!sc || !rd || !film_dev) return fail(DR_ERR_INVALID, "null argument");
+  return renderDevice(sc, rd, film_dev, nullptr, nullptr, hip_stream);
+}
+
+int dr_render_guides_device(DrScene* sc, const DrRenderDesc* rd, const DrGuidesDesc* g, void* film_dev, void* const* guide_films_dev, void* hip_stream) {
+  if (!sc || !rd || !g || !film_dev || !guide_films_dev) return fail(DR_ERR_INVALID, "null argument");
+  int rc = dr_render_guides_check(rd, g, sc->d.ntris);
+  if (rc) return rc;
+  for (int i = 0; i < g->count; ++i)
+    if (!guide_films_dev[i]) return fail(DR_ERR_INVALID, "render guides: a channel's film is null");
+  return renderDevice(sc, rd, film_dev, g, guide_films_dev, hip_stream);
 }
 
 int dr_enumerate_pixels(const DrRenderDesc* rd, int32_t* out_xy, uint64_t cap, uint64_t* n_out) {
@@ -1192,6 +1226,41 @@ int dr_render(DrScene* sc, const DrRenderDesc* rd, float* film_out, float* rgb_o
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(film_out, film.p, 4 * npix * sizeof(float), hipMemcpyDeviceToHost));
   if (rgb_out) HIP_TRY(hipMemcpy(rgb_out, rgb.p, 3 * npix * sizeof(float), hipMemcpyDeviceToHost));
+  return DR_OK;
+}
+
+int dr_render_guides(DrScene* sc, const DrRenderDesc* rd, const DrGuidesDesc* g, float* film_out, float* rgb_out, float* const* guide_films_out,
+                     float* const* guide_rgbs_out) {
+  if (!sc || !rd || !g || !film_out || !guide_films_out) return fail(DR_ERR_INVALID, "null argument");
+  int rc = dr_render_guides_check(rd, g, sc->d.ntris);
+  if (rc) return rc;
+  for (int i = 0; i < g->count; ++i)
+    if (!guide_films_out[i]) return fail(DR_ERR_INVALID, "render guides: a channel's film is null");
+  RenderParams rp;
+  memset(&rp, 0, sizeof(rp));
+  rp_film(rp, rd->film);
+  const int64_t npix = (int64_t)rp.width * rp.height;
+  // the beauty film, then the channels' films, one after the other in one buffer; one more image to resolve into
+  const int n = g->count;
+  DevBuf<float> films, rgb;
+  HIP_TRY(films.alloc((size_t)(n + 1) * 4 * npix));
+  HIP_TRY(hipMemset(films.p, 0, (size_t)(n + 1) * 4 * npix * sizeof(float)));
+  void* guideDev[DR_GUIDES_MAX] = {};
+  for (int i = 0; i < n; ++i) guideDev[i] = films.p + (size_t)(i + 1) * 4 * npix;
+  rc = dr_render_guides_device(sc, rd, g, films.p, guideDev, nullptr);
+  if (rc) return rc;
+  HIP_TRY(rgb.alloc(3 * npix));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(film_out, films.p, 4 * npix * sizeof(float), hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) HIP_TRY(hipMemcpy(guide_films_out[i], guideDev[i], 4 * npix * sizeof(float), hipMemcpyDeviceToHost));
+  for (int i = -1; i < n; ++i) {  // (-1: the beauty image)
+    float* out = i < 0 ? rgb_out : (guide_rgbs_out ? guide_rgbs_out[i] : nullptr);
+    if (!out) continue;
+    rc = dr_film_resolve_device(i < 0 ? (void*)films.p : guideDev[i], npix, rgb.p, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, rgb.p, 3 * npix * sizeof(float), hipMemcpyDeviceToHost));
+  }
   return DR_OK;
 }
 

@@ -19,7 +19,7 @@ struct PilotTimes {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[2];
 };
 
-// One batch through the stage loop: gen_samples -> raygen -> trace(camera) -> [shade(b) -> (env) -> trace_closest || trace_any] -> film,
+// One batch through the stage loop: gen_samples -> raygen -> trace(camera) -> (guides) -> [shade(b) -> (env) -> trace_closest || trace_any] -> film,
 // no host round trips (DirectLighting over mirror / glass: one round of the loop per vertex of a slot's ray tree, one count read back
 // per round).  pilot != null: a calibration batch -- a normal batch whose per-lane traversal launches are also collected in pilot->ev.
 class BatchRunner {
@@ -56,6 +56,7 @@ class BatchRunner {
   GprtArgs gprtArgs() const;  // glossy PRT: the side buffers and the scene's tables
   int stage(int b, int round, const uint32_t* roundQ, const uint32_t* nRound);
   int specRound(int round, const uint32_t*& roundQ, const uint32_t*& nRound, bool& done);
+  void guides();
   int finish();
   int printStageLog();
 
@@ -83,6 +84,7 @@ class BatchRunner {
   int stageCounts = 0;
   bool sideBySide = false;
   std::vector<StageLog> slog;
+  hipEvent_t guides0 = nullptr, guides1 = nullptr;  // k_guides' launch (a guide render's batch), for the stage log
   TraceCounters ctrBase = {};
 };
 
@@ -316,6 +318,16 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
   return DR_OK;
 }
 
+// A guide render, behind the camera rays' traversal and in front of the first shading launch, on the closest-hit stream: the
+// slots still hold the hit record and the camera ray -- what the per-lane kernels and k_trace_pk both leave: F_HPRIM and F_HT written, F_RO and F_RD
+// as k_raygen stored them -- and k_guides writes every requested channel's value to its side plane.  One launch however many channels.
+void BatchRunner::guides() {
+  guides0 = sc->getEvent();
+  (void)hipEventRecord(guides0, s);
+  L.guides(sc->d, st, w.guides.p, w.guidesCap, P.guides.mask, sc->ctr.p, P.sgrid, s);
+  guides1 = timed(TimedKind::Guides, guides0);
+}
+
 // DirectLighting over mirror / glass, the end of a round: k_shade_spec pops / pushes every slot's frame stack and lists the slots
 // whose child ray the next round traces.  done: no slot launched a child.
 int BatchRunner::specRound(int round, const uint32_t*& roundQ, const uint32_t*& nRound, bool& done) {
@@ -373,6 +385,11 @@ int BatchRunner::printStageLog() {
     }
     fprintf(stderr, "\n");
   }
+  if (P.guides.n) {
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, guides0, guides1);
+    fprintf(stderr, "stage_times batch %zu guides: %d channels (mask 0x%x) %.4f ms\n", batch, P.guides.n, P.guides.mask, (double)t);
+  }
   return DR_OK;
 }
 
@@ -389,6 +406,18 @@ int BatchRunner::finish() {
   // render's pixel array, which no later batch reads, move outside every film window)
   if (P.adaptive.pass == 1) L.adaptive_decide(rp, st, np, w.pix.p + p0, w.adaptList.p, w.adaptCount.p, (uint32_t)P.npixTotal, s);
   L.film(rp, st, sc->ws.filterTable.p, np, P.film, s);
+  if (P.guides.n) {
+    // every channel's side plane through the same film kernel -- the same samples, filter table and window -- into the channel's own film.
+    // k_film reads its radiance and its image samples off ONE base pointer (BatchState::tiles), so a plane cannot be handed to it beside the
+    // state's sample region: the plane is moved into the state's radiance plane instead, which the beauty film above was the last to read
+    // (same stream: behind it).  No deferred light term: the state's flags are the beauty render's
+    RenderParams rpG = rp;
+    rpG.deferredNee = 0;
+    for (int i = 0; i < P.guides.n; ++i) {
+      L.guide_plane(st, w.guides.p, w.guidesCap, P.guides.plane[i], P.sgrid, s);
+      L.film(rpG, st, sc->ws.filterTable.p, np, P.guides.film[i], s);
+    }
+  }
   timed(TimedKind::Film, evF);
   sc->stats.batches++;
   if (stageCounts) {
@@ -401,6 +430,14 @@ int BatchRunner::finish() {
 }
 
 int BatchRunner::run() {
+  // a guide render: the one contract of k_guides and of the film step's k_guide_plane launches, which check nothing themselves -- the side
+  // planes exist, hold this batch's slots, and every channel's plane is one of them
+  if (P.guides.n) {
+    if (!w.guides.p || nslots > w.guidesCap || (size_t)3 * P.guides.n * w.guidesCap > w.guides.n)
+      return fail(DR_ERR_HIP, "render guides: a batch larger than the side planes were sized for");
+    for (int i = 0; i < P.guides.n; ++i)
+      if (P.guides.plane[i] < 0 || P.guides.plane[i] >= P.guides.n || !P.guides.film[i]) return fail(DR_ERR_INVALID, "render guides: a channel without a plane or a film");
+  }
   HIP_TRY(hipMemsetAsync(C, 0, CounterLayout::total * sizeof(uint32_t), s));
   int rc = loadSamples();
   if (rc) return rc;
@@ -421,6 +458,7 @@ int BatchRunner::run() {
       logTrace(slog[0], 0);
       readCtrNow(&slog[0].ctr);
     }
+    if (P.guides.n && round == 0) guides();  // (before anything shades: the first shading launch overwrites the camera ray)
     if (P.lazyGen && round == 0) {
       st.markAlive = nullptr;
       genBounce(0);

@@ -83,13 +83,17 @@ struct Workspace {
   } halton;
   DevBuf<float> filterTable, aosSamples;
   DevBuf<float> prt;  // diffuse PRT: the transfer coefficients of every slot, [Terms(lmax)][cap]
+  // guide renders (dr_render_guides*): the side planes k_guides writes, [3 * channels][guidesCap] floats -- a guide render's
+  // channels and batch capacity; never sized by another render
+  DevBuf<float> guides;
+  uint32_t guidesCap = 0;
   DevBuf<uint32_t> gprtBits, gprtMark;  // glossy PRT: one visibility bit per ray and slot, [max(1, nSamples / 32)][cap], and the slots that hit, [cap]
   int spillGrid = 0;
   size_t bytes() const {  // device memory held right now (dr_scene_workspace_bytes): every buffer above
     return tiles.bytes() + scr.bytes() + genState.bytes() + tail.bytes() + tailOff.bytes() + activeA.bytes() + activeB.bytes() + closestQ.bytes() +
            anyQ.bytes() + counters.bytes() + spill.bytes() + envQ.bytes() + alive.bytes() + roundA.bytes() + roundB.bytes() + specFrames.bytes() +
            specSp.bytes() + pix.bytes() + adaptList.bytes() + adaptCount.bytes() + halton.idx.bytes() + halton.keyPix.bytes() + halton.blk.bytes() +
-           filterTable.bytes() + aosSamples.bytes() + prt.bytes() + gprtBits.bytes() + gprtMark.bytes();
+           filterTable.bytes() + aosSamples.bytes() + prt.bytes() + gprtBits.bytes() + gprtMark.bytes() + guides.bytes();
   }
 };
 
@@ -134,6 +138,7 @@ enum class TimedKind : int {
   Film = 4,
   Pilot = 5,           // the calibration batches as a whole (DrRenderStats.pilot_ms)
   CoherentCamera = 6,  // k_trace_pk: part of the closest-hit time, and the pk* figures
+  Guides = 7,          // k_guides (a guide render's one launch per batch): part of the shading time
 };
 
 }  // namespace dr_host
@@ -234,7 +239,7 @@ struct DrScene {
         case TimedKind::Any: stats.any_ms += t; stats.any_launches++; break;
         case TimedKind::Closest: stats.closest_ms += t; stats.closest_launches++; break;
         case TimedKind::CoherentCamera: stats.closest_ms += t; stats.closest_launches++; pkMs += t; pkLaunches++; break;  // k_trace_pk: part of the closest-hit time
-        case TimedKind::Shade: stats.shade_ms += t; break;
+        case TimedKind::Shade: case TimedKind::Guides: stats.shade_ms += t; break;
         case TimedKind::Gen: stats.gen_ms += t; break;
         case TimedKind::Pilot: stats.pilot_ms += t; break;
         case TimedKind::Film: stats.film_ms += t; break;
@@ -286,7 +291,8 @@ struct SampleForm {
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
   X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
-  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(shade_gprt, launch_shade_gprt) X(gprt_finish, launch_gprt_finish) X(shade_probes, launch_shade_probes) X(film, launch_film)
+  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(shade_gprt, launch_shade_gprt) X(gprt_finish, launch_gprt_finish) X(shade_probes, launch_shade_probes) X(film, launch_film) \
+  X(guides, launch_guides) X(guide_plane, launch_guide_plane)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
   DR_LAYOUT_LAUNCHERS(DR_LAYOUT_MEMBER)
@@ -395,6 +401,39 @@ inline const char* featureRefusal(int32_t channel, uint64_t nprims, int* code) {
   return nullptr;
 }
 
+// The refusals of a guide render (dr_render_guides_check, dr_render_guides*): null, or the text and its code.  The integrators that
+// own their camera stage through a kernel of the four below the seam -- Path, DirectLighting "all" and "one", Whitted, ambient occlusion -- are
+// served; every other one is refused by name, and so is the adaptive sampler, which the feature integrator refuses too
+inline const char* guidesRefusal(const DrRenderDesc* rd, const DrGuidesDesc* g, uint64_t nprims, int* code) {
+  *code = DR_ERR_INVALID;
+  if (!rd || !g) return "render guides: null argument";
+  if (!knownIntegrator(rd->integrator)) return "render guides: unknown integrator";
+  *code = DR_ERR_UNSUPPORTED;
+  switch ((IntegratorKind)rd->integrator) {  // (no default: -Wall names a kind this forgets)
+    case IntegratorKind::DirectAll: case IntegratorKind::Path: case IntegratorKind::DirectOne: case IntegratorKind::Whitted:
+    case IntegratorKind::AmbientOcclusion: break;
+    case IntegratorKind::Feature: return "render guides: the feature integrator is not supported (its image is a guide already: render it as it is)";
+    case IntegratorKind::DiffusePRT: return "render guides: the diffuse PRT integrator is not supported (guides beside its side buffer have no test)";
+    case IntegratorKind::GlossyPRT: return "render guides: the glossy PRT integrator is not supported (guides beside its side buffers have no test)";
+    case IntegratorKind::UseProbes: return "render guides: the use probes integrator is not supported (guides under it have no test)";
+  }
+  if (rd->sampler_mode == DR_SAMPLER_ADAPTIVE) return "render guides: the adaptive sampler is not supported (the feature integrator refuses it; a second pass would write its guides twice)";
+  *code = DR_ERR_INVALID;
+  if (g->count < 1) return "render guides: the channel list is empty (count must be 1 to 5)";
+  if (g->count > DR_GUIDES_MAX) return "render guides: more than five channels (count must be 1 to 5)";
+  for (int i = 0; i < g->count; ++i) {
+    if (g->channels[i] < DR_FEATURE_NG || g->channels[i] > DR_FEATURE_ID) return "render guides: unknown channel (DR_FEATURE_NG, _NS, _DEPTH, _UV or _ID)";
+    for (int j = 0; j < i; ++j)
+      if (g->channels[j] == g->channels[i]) return "render guides: a channel is given twice (every DR_FEATURE_* value at most once)";
+  }
+  for (int i = 0; i < g->count; ++i)
+    if (g->channels[i] == DR_FEATURE_ID && nprims >= (1ull << 24)) {
+      *code = DR_ERR_UNSUPPORTED;
+      return "render guides: the id channel needs a scene of fewer than 2^24 primitives (an index + 1 must be exact in the film's f32)";
+    }
+  return nullptr;
+}
+
 // An integrator's sample slots; the floats of a sample vector are computed here and nowhere else.
 struct SlotCounts {
   int n1D, n2D;
@@ -432,6 +471,9 @@ struct RenderPlan {
   // (a round is perRound + 1 stages: CounterLayout::maxStages() bounds it); the rays' extent
   struct { int nSamples = 0, perRound = 0, rounds = 0; double minDist = 0.0, maxDist = 0.0; } ao;
   struct { int channel = 0; } feature;  // Feature: DR_FEATURE_*
+  // A guide render (dr_render_guides_device): n channels (0: none, every other render), the set as k_guides' mask, and per
+  // requested channel its film and its side plane (its rank in the mask).  The side planes cap the batch (planBatches) and are sized by prepareRender
+  struct { int n = 0; uint32_t mask = 0u; float* film[DR_GUIDES_MAX] = {}; int plane[DR_GUIDES_MAX] = {}; } guides;
   // DiffusePRT: the rays in rounds exactly as AmbientOcclusion's; lmax
   struct { int nSamples = 0, perRound = 0, rounds = 0, lmax = 0; } prt;
   // GlossyPRT: the same rounds; words of visibility bits per slot

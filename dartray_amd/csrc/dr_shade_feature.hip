@@ -13,7 +13,8 @@
 // One lane per slot, slots in order (the camera stage has no list), so a wave's reads of the hit record and the camera ray and its store of
 // the radiance are each one run of the tile the state layout was designed around.  The channel is a template parameter: no wave branches on
 // it.  Nothing is queued: the render has one stage and traces nothing but the camera rays.  The geometry comes from dr_device.h's own
-// helpers, through dr_shade_hit.h's pieces; only (u, v) of a quadric, which quadric_dg does not keep, is restated here (feature_quadric_uv).
+// helpers, through dr_shade_hit.h's pieces; only (u, v) of a quadric, which quadric_dg does not keep, is restated (feature_quadric_uv,
+// dr_feature_value.h: the per-channel values, which k_guides stores too).
 // f64 arithmetic, one rounding to the f32 radiance; compiled with -ffp-contract=off, like every unit.
 #include "dr_kernels.h"
 #include "dr_wave.h"
@@ -25,31 +26,9 @@ namespace DR_NS {
 #include "dr_shade_common.h"
 #include "dr_shade_hit.h"
 #include "dr_shade_loop.h"
+#include "dr_feature_value.h"  // the channels' values: shared with k_guides (dr_guides.hip)
 
 #define DR_FEATURE_BLOCK 256
-
-// (u, v) of a quadric hit (sphere.dart:117-120, disk.dart:69-75) at the object-space point quadric_dg_at rebuilds (pointAt(t), the pole fix-up)
-DR_DEV void feature_quadric_uv(const DQuadric& q, F3 o, F3 d, double t, double* u, double* v) {
-  const F3 oo = q_point(q.w2o, o), od = q_vector(q.w2o, d);
-  F3 phit = vadd(oo, vmul(od, t));
-  if (q.kind == DR_QUADRIC_SPHERE && phit.x == 0.0f && phit.y == 0.0f) phit.x = (float)(1.0e-5 * q.radius);
-  const double phi = q_phi(phit);
-  *u = phi / q.phiMax;
-  if (q.kind == DR_QUADRIC_SPHERE) {
-    double r = (double)phit.z / q.radius;
-    r = r < -1.0 ? -1.0 : (r > 1.0 ? 1.0 : r);
-    const double theta = acos(r);
-    *v = (theta - q.thetaMin) / (q.thetaMax - q.thetaMin);
-  } else {
-    const double dist2 = (double)phit.x * (double)phit.x + (double)phit.y * (double)phit.y;
-    const double oneMinusV = (sqrt(dist2) - q.innerRadius) / (q.radius - q.innerRadius);
-    *v = 1.0 - oneMinusV;
-  }
-}
-
-DR_DEV C3 feature_normal(F3 nn) {  // 0.5 * (n + 1), per component
-  return C3{(float)(0.5 * ((double)nn.x + 1.0)), (float)(0.5 * ((double)nn.y + 1.0)), (float)(0.5 * ((double)nn.z + 1.0))};
-}
 
 template <int CHANNEL>
 __global__ void __launch_bounds__(DR_FEATURE_BLOCK) k_shade_feature(DScene sc, BatchState st, TraceCounters* ctr) {
@@ -65,35 +44,24 @@ __global__ void __launch_bounds__(DR_FEATURE_BLOCK) k_shade_feature(DScene sc, B
       ++hits;
       const double t = sr.f64<F_HT>();
       if (CHANNEL == DR_FEATURE_DEPTH) {
-        L = C3{(float)t, (float)t, (float)t};
+        L = feature_depth(t);
       } else {
         if (CHANNEL == DR_FEATURE_ID) {
-          L = C3{(float)((double)prim + 1.0), (float)((double)load_tri(sc, (uint32_t)prim).mat + 1.0), 1.0f};
+          L = feature_id(prim, load_tri(sc, (uint32_t)prim).mat);
         } else {
           const HitRec h = hit_rec(sc, (uint32_t)prim);
-          const Tri& tr = h.tr;
           const ShadeRec srec = hit_srec(sc, h);
           const F3 o = ld3f<F_RO>(sr), d = ld3f<F_RD>(sr);
           DGeo dg = {}, dgs = {};
-          if (CHANNEL == DR_FEATURE_UV && h.isQuad) {
-            feature_quadric_uv(sc.quads[tr.quad], o, d, t, &dg.u, &dg.v);
-          } else if (CHANNEL == DR_FEATURE_UV && !h.hasRec) {
-            // Triangle.getUVs without a uv array (triangle.dart:255-262) and the interpolation of :134-137, on the accepting test's barycentrics
-            double tt, b1 = 0.0, b2 = 0.0;
-            (void)tri_hit(tr.p1, tr.p2, tr.p3, o, d, -DR_INF, DR_INF, &tt, &b1, &b2);
-            const double b0 = 1.0 - b1 - b2;
-            dg.u = b0 * 0.0 + b1 * 1.0 + b2 * 1.0;
-            dg.v = b0 * 0.0 + b1 * 0.0 + b2 * 1.0;
-          } else {
-            hit_dg(sc, h, srec, o, d, t, &dg);
-          }
+          // (u, v) of a quadric and the default uvs are not isect.dg's: dr_feature_value.h
+          if (!(CHANNEL == DR_FEATURE_UV && feature_uv_without_dg(sc, h, o, d, t, &dg.u, &dg.v))) hit_dg(sc, h, srec, o, d, t, &dg);
           if (CHANNEL == DR_FEATURE_NG) {
             L = feature_normal(dg.nn);
           } else if (CHANNEL == DR_FEATURE_NS) {
             hit_dgs(sc, h, srec, dg, &dgs);  // (a quadric's Shape.getShadingGeometry: a copy)
             L = feature_normal(dgs.nn);
           } else {
-            L = C3{(float)dg.u, (float)dg.v, 0.f};
+            L = feature_uv(dg.u, dg.v);
           }
         }
       }

@@ -40,7 +40,7 @@ import math
 import numpy as np
 
 from . import _abi
-from ._image import _check_channel, _entry, _guides, _images, _rerender, _whole_film_refusals
+from ._image import _beauty_and_guides, _check_channel, _check_one_pass, _entry, _guides, _images, _rerender, _whole_film_refusals
 from .core.cameras import PerspectiveCamera
 from .core.renderer import FeatureIntegrator, OutputImage, SamplerRenderer  # noqa: F401  (the first and last: read from here by tools/)
 from .core.samplers import AdaptiveSampler
@@ -85,18 +85,19 @@ def atrous(rgb, normal, depth, iterations=ITERATIONS, sigma_color=SIGMA_COLOR, s
     return out
 
 
-def render_denoised(renderer, scene, normal_channel="ns", firefly=False, **filter_kw):
+def render_denoised(renderer, scene, normal_channel="ns", firefly=False, one_pass=False, **filter_kw):
     """Renders the beauty image with `renderer` as given and two FeatureIntegrator images -- `normal_channel` ("ns" or "ng") and "depth" --
     with the same camera, film, sampler and work split, filters, and returns an OutputImage whose rgb is the result; the three unfiltered
     images stay on it as `noisy` [h, w, 3], `normal` [h, w, 3] and `depth` [h, w].  filter_kw: atrous()'s keywords.  firefly: True, or a
     dict of firefly()'s parameters, clamps the beauty image's outliers before the filter; `noisy` stays the unclamped
-    render and the luminance taken away stays on the result as `removed`."""
+    render and the luminance taken away stays on the result as `removed`.  one_pass=True: the beauty image and both guides come from one
+    render (render_with_guides) instead of three, the same bytes; an integrator it does not serve raises ValueError."""
     _check_channel("render_denoised", normal_channel)
     fkw = _firefly_kw("render_denoised", firefly)
     if isinstance(renderer.sampler, AdaptiveSampler):
         raise ValueError("render_denoised: the adaptive sampler is not supported (the feature integrator refuses it)")
-    beauty = renderer.render(scene)
-    normal, depth = _guides(renderer, scene, normal_channel)
+    _check_one_pass("render_denoised", one_pass, renderer, scene, normal_channel)
+    beauty, normal, depth = _beauty_and_guides(renderer, scene, normal_channel, one_pass)
     clamped, removed = _clamped(fkw, beauty.rgb, normal, depth)
     out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, atrous(clamped, normal, depth, **filter_kw), beauty.film)
     out.noisy, out.normal, out.depth = beauty.rgb, normal, depth
@@ -130,7 +131,7 @@ def pair_seed(seed):
     return int(seed) ^ SEED_B_XOR
 
 
-def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", firefly=False, **filter_kw):
+def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", firefly=False, one_pass=False, **filter_kw):
     """Renders the scene twice -- half A with `renderer` as given, half B with a shallow copy of its sampler whose seed is `seed_b` (default:
     pair_seed of the sampler's seed) -- and the two guides as render_denoised does, all four with the same camera, integrators and work
     split, and filters the halves' mean with atrous_pair.  Returns an OutputImage whose rgb is the result; `a`, `b`, `noisy` (the mean),
@@ -141,7 +142,9 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", fire
 
     firefly: True, or a dict of firefly()'s parameters, clamps each half's outliers before the filter, so that a bright
     pixel of one half no longer inflates the variance estimate its neighbours share; `a`, `b` and `noisy` stay the unclamped renders, and
-    the luminance taken from the halves stays on the result as `removed` = (removed_a, removed_b)."""
+    the luminance taken from the halves stays on the result as `removed` = (removed_a, removed_b).
+
+    one_pass=True: the guides ride on half A's render (render_with_guides) -- three renders instead of four, the same bytes."""
     _check_channel("render_denoised_pair", normal_channel)
     fkw = _firefly_kw("render_denoised_pair", firefly)
     sampler = renderer.sampler
@@ -154,9 +157,14 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", fire
         raise ValueError("render_denoised_pair: seed_b equals the sampler's seed (%d): the two halves would be one render" % (seed_b,))
     sampler_b = copy.copy(sampler)
     sampler_b.seed = seed_b
-    half_a = renderer.render(scene)
-    half_b = _rerender(renderer, scene, renderer.surfaceIntegrator, sampler_b)
-    normal, depth = _guides(renderer, scene, normal_channel)
+    _check_one_pass("render_denoised_pair", one_pass, renderer, scene, normal_channel)
+    if one_pass:
+        half_a, normal, depth = _beauty_and_guides(renderer, scene, normal_channel, True)
+        half_b = _rerender(renderer, scene, renderer.surfaceIntegrator, sampler_b)
+    else:
+        half_a = renderer.render(scene)
+        half_b = _rerender(renderer, scene, renderer.surfaceIntegrator, sampler_b)
+        normal, depth = _guides(renderer, scene, normal_channel)
     filter_kw = dict(filter_kw, return_variance=True)
     (a, removed_a), (b, removed_b) = _clamped(fkw, half_a.rgb, normal, depth), _clamped(fkw, half_b.rgb, normal, depth)
     rgb, variance = atrous_pair(a, b, normal, depth, **filter_kw)
@@ -214,7 +222,7 @@ def _upsample_refusals(who, low, full):
     return factor
 
 
-def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", taps=2, denoise=False, firefly=False, **kw):
+def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", taps=2, denoise=False, firefly=False, one_pass=False, **kw):
     """Renders the beauty image and two FeatureIntegrator images -- `normal_channel` ("ns" or "ng") and "depth" -- with `low_renderer`, whose
     film is 1/2 or 1/4 of `full_renderer`'s in both axes over the same camera pose, the same two guides with `full_renderer`'s sampler and
     camera -- its own surface integrator is never run -- and upsamples.  Returns an OutputImage of the full size whose rgb is the result;
@@ -222,16 +230,17 @@ def render_upsampled(low_renderer, full_renderer, scene, normal_channel="ns", ta
     `normal` and `depth`, and `upsampled` [h, w, 3].  kw: sigma_normal and sigma_depth go to both stages; atrous()'s other keywords need
     denoise=True.  firefly: True, or a dict of firefly()'s parameters, clamps the low-resolution beauty image's outliers under the
     low-resolution guides before it is upsampled; `low` stays the unclamped render, and the luminance taken away stays on
-    the result as `removed` [hl, wl]."""
+    the result as `removed` [hl, wl].  one_pass=True: the low-resolution image and its two guides come from one render (render_with_guides,
+    DESIGN.md 2.26), the same bytes; the full-resolution guides have no beauty render to ride on and stay FeatureIntegrator renders."""
     who = "render_upsampled"
     _check_channel(who, normal_channel)
     fkw = _firefly_kw(who, firefly)
     factor = _upsample_refusals(who, low_renderer, full_renderer)
+    _check_one_pass(who, one_pass, low_renderer, scene, normal_channel)
     guide_kw = {k: kw[k] for k in ("sigma_normal", "sigma_depth") if k in kw}
     if not denoise and len(guide_kw) != len(kw):
         raise ValueError("%s: %s given without denoise=True" % (who, ", ".join(sorted(set(kw) - set(guide_kw)))))
-    low = low_renderer.render(scene)
-    normal_lo, depth_lo = _guides(low_renderer, scene, normal_channel)
+    low, normal_lo, depth_lo = _beauty_and_guides(low_renderer, scene, normal_channel, one_pass)
     normal, depth = _guides(full_renderer, scene, normal_channel)
     low_rgb, removed = _clamped(fkw, low.rgb, normal_lo, depth_lo)
     up = upsample(low_rgb, normal_lo, depth_lo, normal, depth, factor=factor, taps=taps, **guide_kw)
@@ -380,14 +389,15 @@ def _clamped(kw, rgb, normal, depth):
     return (rgb, None) if kw is None else firefly(rgb, normal, depth, **dict(kw, return_removed=True))
 
 
-def render_firefly(renderer, scene, normal_channel="ns", **firefly_kw):
+def render_firefly(renderer, scene, normal_channel="ns", one_pass=False, **firefly_kw):
     """Renders the beauty image and the two guides as render_denoised does and clamps its fireflies.  Returns an OutputImage whose rgb is
-    the result; `noisy` (the unclamped render), `normal`, `depth` and `removed` stay on it.  firefly_kw: firefly()'s keywords."""
+    the result; `noisy` (the unclamped render), `normal`, `depth` and `removed` stay on it.  firefly_kw: firefly()'s keywords.
+    one_pass=True: one render instead of three, as for render_denoised."""
     _check_channel("render_firefly", normal_channel)
     if isinstance(renderer.sampler, AdaptiveSampler):
         raise ValueError("render_firefly: the adaptive sampler is not supported (the feature integrator refuses it)")
-    beauty = renderer.render(scene)
-    normal, depth = _guides(renderer, scene, normal_channel)
+    _check_one_pass("render_firefly", one_pass, renderer, scene, normal_channel)
+    beauty, normal, depth = _beauty_and_guides(renderer, scene, normal_channel, one_pass)
     rgb, removed = firefly(beauty.rgb, normal, depth, **dict(firefly_kw, return_removed=True))
     out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, rgb, beauty.film)
     out.noisy, out.normal, out.depth, out.removed = beauty.rgb, normal, depth, removed
@@ -433,7 +443,7 @@ def atrous_moments(frame, iterations=ITERATIONS, sigma_color=SIGMA_COLOR_PAIR, s
 
 
 def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_tol=DEPTH_TOL, normal_tol=NORMAL_TOL, max_history=MAX_HISTORY,
-                    firefly=False, **kw):
+                    firefly=False, one_pass=False, **kw):
     """Renders one frame per renderer -- one camera pose each, in the order of the animation -- with its beauty image and two
     FeatureIntegrator images, `normal_channel` ("ns" or "ng") and "depth", as render_denoised does, and accumulates each into the history of
     the frames before it with temporal().  Returns the list of frames: OutputImages whose rgb is the accumulated colour, or with denoise=True
@@ -449,7 +459,12 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
     error, and their mean is no better than one of them.  The guides are another matter: they are filtered over the sampler's positions too,
     so where a pixel straddles a silhouette two seeds give two depths, and a static camera would lose its history there in every frame.
     Every frame's guides are therefore rendered with a copy of its sampler that carries the first renderer's seed: at one pose the guides are
-    the same bytes whatever the beauty image's seed."""
+    the same bytes whatever the beauty image's seed.
+
+    one_pass=True: a frame whose sampler carries the guides' seed -- the first frame, and every frame of a sequence that shares one seed or
+    whose sampler has none -- takes its beauty image and its guides from one render (render_with_guides), the same bytes.  A
+    frame with a seed of its own keeps its two FeatureIntegrator renders: its guides are sampled with another seed than its beauty image, so
+    they have no beauty render to ride on."""
     who = "render_sequence"
     _check_channel(who, normal_channel)
     renderers = list(renderers)
@@ -462,6 +477,9 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
         name = "renderers[%d]" % k
         _whole_film_refusals(who, name, r, "accumulation", each=False)
         _camera_refusals(who, name + ".camera", r.camera)
+    _check_one_pass(who, one_pass)
+    for r in renderers if one_pass else ():
+        _check_one_pass(who, one_pass, r, scene, normal_channel)
     mats = [temporal_matrices(r.camera, renderers[max(k - 1, 0)].camera) for k, r in enumerate(renderers)]
 
     guide_seed = getattr(renderers[0].sampler, "seed", None) if renderers else None
@@ -471,8 +489,11 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
         if guide_seed is not None and getattr(guide_sampler, "seed", None) is not None:
             guide_sampler = copy.copy(r.sampler)
             guide_sampler.seed = guide_seed
-        beauty = r.render(scene)
-        normal, depth = _guides(r, scene, normal_channel, guide_sampler)
+        if one_pass and (guide_sampler is r.sampler or guide_sampler.seed == r.sampler.seed):
+            beauty, normal, depth = _beauty_and_guides(r, scene, normal_channel, True)
+        else:
+            beauty = r.render(scene)
+            normal, depth = _guides(r, scene, normal_channel, guide_sampler)
         clamped, removed = _clamped(fkw, beauty.rgb, normal, depth)
         history = temporal(clamped, normal, depth, history, m, depth_tol=depth_tol, normal_tol=normal_tol, max_history=max_history)
         filtered_variance = None

@@ -884,6 +884,32 @@ int dr_render(DrScene* scene, const DrRenderDesc* desc, float* film_out, float* 
  * DR_SAMPLER_ADAPTIVE likewise reads one count between its passes). */
 int dr_render_device(DrScene* scene, const DrRenderDesc* desc, void* film_dev, void* hip_stream);
 
+/* Guide images in the beauty render's own pass.  Behind the camera rays' traversal a batch holds every sample's hit record
+ * and camera ray -- all a DR_INTEGRATOR_FEATURE render reads -- so one more launch per batch (k_guides) writes the requested DR_FEATURE_* channels'
+ * values to side planes, and the batch's film step adds each plane to a film of the channel's own with the beauty film's samples, filter and
+ * window.  A channel's film equals the film of a DR_INTEGRATOR_FEATURE render of that channel with the same camera, film, sampler and work split
+ * (bit for bit wherever two such renders equal each other: a filter that stays inside the pixel and a pixel-bound sampler); the beauty film
+ * equals dr_render's.  Under DirectLighting over mirror / glass the guide is the first hit, as under the feature integrator. */
+#define DR_GUIDES_MAX 5
+typedef struct DrGuidesDesc {
+  int32_t count;                   /* 1 .. DR_GUIDES_MAX */
+  int32_t channels[DR_GUIDES_MAX]; /* DR_FEATURE_* values, each at most once; entries behind `count` are not read */
+} DrGuidesDesc;
+/* What dr_render_guides* would answer to `desc` and `guides` over a scene of `nprimitives` primitives, without a scene or a device: DR_OK, or the
+ * refusal with dr_last_error's text.  Served: DR_INTEGRATOR_PATH, _DIRECT_ALL, _DIRECT_ONE, _WHITTED and _AO under every sampler mode the feature
+ * integrator accepts.  DR_ERR_UNSUPPORTED, by name: DR_INTEGRATOR_FEATURE, _DIFFUSE_PRT, _GLOSSY_PRT, _USE_PROBES; DR_SAMPLER_ADAPTIVE;
+ * DR_FEATURE_ID with 2^24 primitives or more.  DR_ERR_INVALID: an unknown integrator, an empty list, more than DR_GUIDES_MAX channels, an unknown
+ * channel, a channel given twice.  Only desc->integrator and desc->sampler_mode are read: everything else of `desc` is checked by the render. */
+int dr_render_guides_check(const DrRenderDesc* desc, const DrGuidesDesc* guides, uint64_t nprimitives);
+/* dr_render plus the guides: guide_films_out[i] is channel i's film [height*width*4], guide_rgbs_out (optional, as are its entries) channel i's
+ * resolved image [height*width*3].  There is no sharded form; task_* and tile_* work as for dr_render. */
+int dr_render_guides(DrScene* scene, const DrRenderDesc* desc, const DrGuidesDesc* guides, float* film_out, float* rgb_out,
+                     float* const* guide_films_out, float* const* guide_rgbs_out);
+/* dr_render_device's twin: the beauty film accumulates into film_dev and channel i's into guide_films_dev[i] (device addresses in a host array;
+ * the caller zero-initialises every film), with dr_render_device's stream-ordering contract and its waits. */
+int dr_render_guides_device(DrScene* scene, const DrRenderDesc* desc, const DrGuidesDesc* guides, void* film_dev, void* const* guide_films_dev,
+                            void* hip_stream);
+
 /* The raster pixels a DR_SAMPLER_COUNTER render of `desc` traces, in trace
  * order (GetSubWindow rectangle, common.dart:52-73, intersected with this
  * rank's round-robin tiles).  Host-only; out_xy may be NULL to query the count. */
@@ -990,7 +1016,8 @@ const char* dr_version(void);
  * dr_temporal_device; and the moments denoiser: one new struct, DrDenoiseMomentsParams, that only its four new entry points read --
  * dr_denoise_moments_check, dr_denoise_moments_host, dr_denoise_moments and dr_denoise_moments_device; and firefly suppression: one new
  * struct, DrFireflyParams, that only its four new entry points read -- dr_firefly_check, dr_firefly_host, dr_firefly and
- * dr_firefly_device). */
+ * dr_firefly_device; and the one-pass guide render: one new struct, DrGuidesDesc, that only its three new entry points read --
+ * dr_render_guides_check, dr_render_guides and dr_render_guides_device; no field of DrRenderDesc moved). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -1143,6 +1170,8 @@ DR_ABI_OFFSET(DrFireflyParams, threshold, 8);
 DR_ABI_OFFSET(DrFireflyParams, floor, 12);
 DR_ABI_OFFSET(DrFireflyParams, depth_tol, 16);
 DR_ABI_OFFSET(DrFireflyParams, normal_tol, 20);
+DR_ABI_SIZE(DrGuidesDesc, 24);
+DR_ABI_OFFSET(DrGuidesDesc, channels, 4);
 
 #ifdef __cplusplus
 }

@@ -269,6 +269,11 @@ const int SIZEOF_DrProbesDesc = 72, OFF_DrProbesDesc_lmax = 0, OFF_DrProbesDesc_
     OFF_DrProbesDesc_has_bounds = 12, OFF_DrProbesDesc_bounds = 16, OFF_DrProbesDesc_camera_pos = 40, OFF_DrProbesDesc_spacing = 56,
     OFF_DrProbesDesc_time = 64;
 const int DR_FEATURE_NG = 0, DR_FEATURE_NS = 1, DR_FEATURE_DEPTH = 2, DR_FEATURE_UV = 3, DR_FEATURE_ID = 4;
+// DrGuidesDesc (the channels of a guide render, DESIGN.md 2.26): int32 count (1..5), then int32 channels[5], DR_FEATURE_* values, none twice
+const int DR_GUIDES_MAX = 5;
+const int SIZEOF_DrGuidesDesc = 24;
+const int OFF_DrGuidesDesc_count = 0;
+const int OFF_DrGuidesDesc_channels = 4;
 const int DR_SAMPLER_COUNTER = 1;
 const int DR_SAMPLER_STRATIFIED = 2;           // StratifiedSampler on keyed streams; spp = xPixelSamples * yPixelSamples
 const int DR_SAMPLER_STRATIFIED_NOJITTER = 3;  // ... with jitterSamples == false
@@ -388,6 +393,17 @@ typedef _FireflyDeviceD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Voi
 // OFF_DrDisplayParams_* offsets above), out[h][w][4] bytes R, G, B, A.  (Signature only, never compiled, like the rest.)
 typedef _DisplayC = Int32 Function(Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Uint8>);
 typedef _DisplayD = int Function(Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Uint8>);
+// dr_render_guides_check (the refusals, without a scene or a GPU): DrRenderDesc, DrGuidesDesc (24 bytes, the OFF_DrGuidesDesc_* offsets above),
+// the scene's primitive count.  dr_render_guides: dr_render plus, per channel, the address of a film [h*w*4] and (the array or an entry may be
+// null) of a resolved image [h*w*3].  dr_render_guides_device: device addresses and a hipStream_t last.  (Signatures only, never compiled,
+// like the rest.)
+typedef _RenderGuidesCheckC = Int32 Function(Pointer<Uint8>, Pointer<Uint8>, Uint64);
+typedef _RenderGuidesCheckD = int Function(Pointer<Uint8>, Pointer<Uint8>, int);
+// The two arrays of addresses travel as blocks of 8-byte words (_Blob.addr).
+typedef _RenderGuidesC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Uint8>, Pointer<Uint8>);
+typedef _RenderGuidesD = int Function(Pointer<Void>, Pointer<Uint8>, Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Uint8>, Pointer<Uint8>);
+typedef _RenderGuidesDeviceC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Pointer<Uint8>, Pointer<Void>, Pointer<Uint8>, Pointer<Void>);
+typedef _RenderGuidesDeviceD = int Function(Pointer<Void>, Pointer<Uint8>, Pointer<Uint8>, Pointer<Void>, Pointer<Uint8>, Pointer<Void>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -487,6 +503,13 @@ class HipSamplerRenderer extends Renderer {
   }
   static final _SceneCreateD _sceneCreate = _lib.lookupFunction<_SceneCreateC, _SceneCreateD>('dr_scene_create');
   static final _RenderD _render = _lib.lookupFunction<_RenderC, _RenderD>('dr_render');
+  /// The guide images of the denoisers in the beauty render's own pass (DESIGN.md 2.26): `renderGuidesCheck` needs no GPU;
+  /// `renderGuidesDevice` is `renderDevice`'s twin for hosts that keep the films on the device.
+  static final _RenderGuidesCheckD renderGuidesCheck =
+      _lib.lookupFunction<_RenderGuidesCheckC, _RenderGuidesCheckD>('dr_render_guides_check');
+  static final _RenderGuidesD _renderGuides = _lib.lookupFunction<_RenderGuidesC, _RenderGuidesD>('dr_render_guides');
+  static final _RenderGuidesDeviceD renderGuidesDevice =
+      _lib.lookupFunction<_RenderGuidesDeviceC, _RenderGuidesDeviceD>('dr_render_guides_device');
   static final _DestroyD _destroy = _lib.lookupFunction<_DestroyC, _DestroyD>('dr_scene_destroy');
   // the multi-GPU half (include/dartray_hip.h): one process per GPU, ONE film reduce per render
   static final _RenderShardedD _renderSharded = _lib.lookupFunction<_RenderShardedC, _RenderShardedD>('dr_render_sharded');
@@ -671,6 +694,23 @@ class HipSamplerRenderer extends Renderer {
   /// Kd / Kr / Kt / sigma / index are Textures; the device path takes constants (evaluate() of a constant texture
   /// ignores the DifferentialGeometry).
   static final DifferentialGeometry _dg0 = new DifferentialGeometry();
+
+  /// render(), and in the same pass the FeatureIntegrator images of [channels] (DR_FEATURE_* values, at most five, none twice): the
+  /// OutputImage of render(); the guides stay in [lastGuides], one [height * width * 3] image per channel in the order given.  Path,
+  /// DirectLighting, Whitted and ambient occlusion integrators, one process (tileCount 1); the library refuses everything else by name.
+  Future<OutputImage> renderWithGuides(Scene scene, List<int> channels) {
+    _guideChannels = channels;
+    lastGuides = null;
+    try {
+      return render(scene);
+    } finally {
+      _guideChannels = null;
+    }
+  }
+
+  /// The guide images of the last renderWithGuides call (null after a plain render).
+  List<Float32List> lastGuides;
+  List<int> _guideChannels;
 
   Future<OutputImage> render(Scene scene) {
     Completer<OutputImage> completer = new Completer<OutputImage>();
@@ -1151,6 +1191,9 @@ class HipSamplerRenderer extends Renderer {
       final int npix = film.width * film.height;
       lxyzw = calloc<Float>(4 * npix);
       rgb = calloc<Float>(3 * npix);
+      if (_guideChannels != null && tileCount > 1) {
+        _unsupported('renderWithGuides with tileCount > 1 (a sharded guide film)');
+      }
       if (tileCount > 1) {
         // one rank of a multi-GPU render: its tiles, ONE ncclReduce(sum) of the full-frame film onto rank 0, which
         // resolves it (dr_render_sharded; commInit has been called by the process).  Ranks > 0 complete with null,
@@ -1159,6 +1202,36 @@ class HipSamplerRenderer extends Renderer {
         if (_commRank() > 0) {
           completer.complete(null);
           return completer.future;
+        }
+      } else if (_guideChannels != null) {
+        final int nch = _guideChannels.length;
+        _Blob gd = new _Blob(SIZEOF_DrGuidesDesc);
+        blobs.add(gd);
+        gd.i32(OFF_DrGuidesDesc_count, nch);
+        for (int i = 0; i < nch && i < DR_GUIDES_MAX; ++i) {
+          gd.i32(OFF_DrGuidesDesc_channels + 4 * i, _guideChannels[i]);
+        }
+        _check(renderGuidesCheck(rd.ptr, gd.ptr, nprims));  // (the refusals by name, before anything is allocated)
+        // one block of native memory per channel: its film, then its resolved image
+        _Blob guideFilms = new _Blob(8 * nch);
+        _Blob guideRgbs = new _Blob(8 * nch);
+        blobs.add(guideFilms);
+        blobs.add(guideRgbs);
+        List<_Blob> images = [];
+        for (int i = 0; i < nch; ++i) {
+          _Blob film4 = new _Blob(16 * npix);
+          _Blob rgb3 = new _Blob(12 * npix);
+          blobs.add(film4);
+          blobs.add(rgb3);
+          images.add(rgb3);
+          guideFilms.addr(8 * i, film4);
+          guideRgbs.addr(8 * i, rgb3);
+        }
+        _check(_renderGuides(handle.value, rd.ptr, gd.ptr, lxyzw, rgb, guideFilms.ptr, guideRgbs.ptr));
+        lastGuides = [];
+        for (_Blob image in images) {
+          Uint8List bytes = image.ptr.asTypedList(12 * npix);
+          lastGuides.add(new Float32List.fromList(bytes.buffer.asFloat32List(bytes.offsetInBytes, 3 * npix)));
         }
       } else {
         _check(_render(handle.value, rd.ptr, lxyzw, rgb));
