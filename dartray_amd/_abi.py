@@ -20,6 +20,8 @@ DR_INTEGRATOR_FEATURE = 5  # feature_channel; max_depth is not read
 DR_INTEGRATOR_DIFFUSE_PRT = 7  # (6 stays unassigned) prt_nsamples / prt_lmax; max_depth is not read
 DR_INTEGRATOR_GLOSSY_PRT = 9  # (8 stays unassigned) prt_nsamples / prt_lmax; Kd, Ks, roughness by dr_scene_set_glossy_prt; max_depth is not read
 DR_INTEGRATOR_USE_PROBES = 11  # (10 stays unassigned) the grid by dr_scene_set_probes; the scene's DirectLighting "all" slots; max_depth is not read
+DR_INTEGRATOR_MATERIAL = 13  # (12 stays unassigned) material_channel; max_depth is not read
+DR_MATERIAL_CHANNEL_ALBEDO, DR_MATERIAL_CHANNEL_EMISSION = 0, 1
 DR_FEATURE_NG, DR_FEATURE_NS, DR_FEATURE_DEPTH, DR_FEATURE_UV, DR_FEATURE_ID = 0, 1, 2, 3, 4
 DR_TONE_CLAMP, DR_TONE_REINHARD, DR_TONE_FILMIC = 0, 1, 2
 DR_ENCODE_SRGB, DR_ENCODE_GAMMA22, DR_ENCODE_REFERENCE = 0, 1, 2
@@ -152,6 +154,8 @@ class DrRenderDesc(C.Structure):
     # DR_INTEGRATOR_DIFFUSE_PRT's and DR_INTEGRATOR_GLOSSY_PRT's two parameters: union members at the offsets of ao_nsamples and feature_channel (each read under one integrator only)
     prt_nsamples = _Overlay(1324, C.c_int32)
     prt_lmax = _Overlay(1340, C.c_int32)
+    # DR_INTEGRATOR_MATERIAL's channel: a third member of that union
+    material_channel = _Overlay(1340, C.c_int32)
 
 
 class DrGlossyPrtParams(C.Structure):
@@ -209,6 +213,10 @@ class DrTemporalParams(C.Structure):
 class DrFireflyParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float), ("depth_tol", C.c_float),
                 ("normal_tol", C.c_float)]
+
+
+class DrDemodulateParams(C.Structure):
+    _fields_ = [("eps", C.c_float)]
 
 
 DR_GUIDES_MAX = 5
@@ -286,6 +294,13 @@ EXPORTS = {
     "dr_firefly_host": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrFireflyParams)] + [C.c_void_p] * 2),
     "dr_firefly": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrFireflyParams)] + [C.c_void_p] * 2),
     "dr_firefly_device": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrFireflyParams)] + [C.c_void_p] * 3),
+    "dr_demodulate_check": (C.c_int, [C.POINTER(DrDemodulateParams), C.c_int32, C.c_int32]),
+    "dr_demodulate_host": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrDemodulateParams), C.c_void_p]),
+    "dr_demodulate": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrDemodulateParams), C.c_void_p]),
+    "dr_demodulate_device": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrDemodulateParams), C.c_void_p, C.c_void_p]),
+    "dr_remodulate_host": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrDemodulateParams), C.c_void_p]),
+    "dr_remodulate": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrDemodulateParams), C.c_void_p]),
+    "dr_remodulate_device": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32, C.POINTER(DrDemodulateParams), C.c_void_p, C.c_void_p]),
     "dr_scene_create": (C.c_int, [C.POINTER(DrSceneDesc), C.POINTER(C.c_void_p)]),
     "dr_scene_destroy": (None, [C.c_void_p]),
     "dr_scene_get_trace_kernels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 2)]),
@@ -298,6 +313,7 @@ EXPORTS = {
     "dr_sample_floats": (C.c_int32, [C.c_int32, C.c_uint32]),
     "dr_scene_sample_floats": (C.c_int32, [C.c_void_p, C.c_int32]),
     "dr_feature_check": (C.c_int, [C.c_int32, C.c_uint64]),
+    "dr_material_check": (C.c_int, [C.c_int32]),
     "dr_prt_incident": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, C.c_void_p]),
     "dr_sh_evaluate": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "dr_scene_set_glossy_prt": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -38,12 +38,12 @@ from .cameras import EnvironmentCamera, OrthographicCamera, PerspectiveCamera, _
 from .samplers import (ONE_MINUS_EPSILON, AdaptiveSampler, DartRandom, GetSubWindow, HaltonSampler, HostBufferSampler, Lerp,  # noqa: F401
                        LinearPixelSampler, LowDiscrepancySampler, RadicalInverse, RandomPixelSampler, RandomSampler, RoundUpPow2, StratifiedSampler,
                        TilePixelSampler, _latin_hypercube_slots, _pack_tails)
-from .renderer import (AmbientOcclusionIntegrator, DiffusePRTIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, GlossyPRTIntegrator, OutputImage, PathIntegrator,  # noqa: F401
+from .renderer import (AmbientOcclusionIntegrator, DiffusePRTIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, GlossyPRTIntegrator, MaterialIntegrator, OutputImage, PathIntegrator,  # noqa: F401
                        ProbeGrid, SamplerRenderer, UseProbesIntegrator, WhittedIntegrator)
 from .plugins import Plugin, RegisterStandardPlugins  # noqa: F401
 
 # what `from dartray_amd import *` binds: core.py's public names, the five modules it had imported among them (a recorded list: classes added
-# since -- RandomSampler, WhittedIntegrator, AmbientOcclusionIntegrator, FeatureIntegrator, DiffusePRTIntegrator, GlossyPRTIntegrator, UseProbesIntegrator, ProbeGrid -- are reached as core.<name>)
+# since -- RandomSampler, WhittedIntegrator, AmbientOcclusionIntegrator, FeatureIntegrator, DiffusePRTIntegrator, GlossyPRTIntegrator, UseProbesIntegrator, ProbeGrid, MaterialIntegrator -- are reached as core.<name>)
 __all__ = [
     "C", "collections", "math", "np", "os", "DartRayHipError",
     "look_at", "transform_points",

@@ -356,10 +356,12 @@ class _DeviceScene:
                 # arr[3]: -1, or after a WhittedIntegrator / AmbientOcclusionIntegrator / FeatureIntegrator / DiffusePRTIntegrator / GlossyPRTIntegrator render the integrator and its shading kernels
                 "integrator": None if arr[3] < 0 else {_abi.DR_INTEGRATOR_WHITTED: "whitted", _abi.DR_INTEGRATOR_AO: "ambientocclusion",
                                                        _abi.DR_INTEGRATOR_FEATURE: "feature", _abi.DR_INTEGRATOR_DIFFUSE_PRT: "diffuseprt",
-                                                       _abi.DR_INTEGRATOR_GLOSSY_PRT: "glossyprt", _abi.DR_INTEGRATOR_USE_PROBES: "useprobes"}.get(int(arr[3]) & 255),
+                                                       _abi.DR_INTEGRATOR_GLOSSY_PRT: "glossyprt", _abi.DR_INTEGRATOR_USE_PROBES: "useprobes",
+                                                       _abi.DR_INTEGRATOR_MATERIAL: "material"}.get(int(arr[3]) & 255),
                 "shade_kernels": [] if arr[3] < 0 else [k for bit, k in ((8, "k_shade_whitted"), (9, "k_shade_spec"), (10, "k_shade_ao"),
-                                                                         (11, "k_shade_feature"), (15, "k_shade_prt"), (16, "k_shade_gprt"), (16, "k_gprt_finish"), (17, "k_shade_probes")) if (int(arr[3]) >> bit) & 1],
-                "feature_channel": (int(arr[3]) >> 12) & 7 if arr[3] >= 0 and (int(arr[3]) >> 11) & 1 else None}
+                                                                         (11, "k_shade_feature"), (15, "k_shade_prt"), (16, "k_shade_gprt"), (16, "k_gprt_finish"), (17, "k_shade_probes"), (18, "k_shade_material")) if (int(arr[3]) >> bit) & 1],
+                "feature_channel": (int(arr[3]) >> 12) & 7 if arr[3] >= 0 and (int(arr[3]) >> 11) & 1 else None,
+                "material_channel": (int(arr[3]) >> 19) & 1 if arr[3] >= 0 and (int(arr[3]) >> 18) & 1 else None}
 
     def adaptive_pixels(self):
         """Raster pixels ([n, 2] int32, no particular order) the last render of this scene supersampled (dr_scene_get_adaptive_pixels:

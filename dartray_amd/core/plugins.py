@@ -5,7 +5,7 @@ from .cameras import EnvironmentCamera, OrthographicCamera, PerspectiveCamera
 from .film import BoxFilter, GaussianFilter, ImageFilm, LanczosSincFilter, MitchellFilter, TriangleFilter
 from .lights import DiffuseAreaLight
 from .materials import MatteMaterial
-from .renderer import (AmbientOcclusionIntegrator, DiffusePRTIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, GlossyPRTIntegrator, PathIntegrator, SamplerRenderer,
+from .renderer import (AmbientOcclusionIntegrator, DiffusePRTIntegrator, DirectLightingIntegrator, EmissionIntegrator, FeatureIntegrator, GlossyPRTIntegrator, MaterialIntegrator, PathIntegrator, SamplerRenderer,
                        UseProbesIntegrator, WhittedIntegrator)
 from .samplers import (AdaptiveSampler, HaltonSampler, LinearPixelSampler, LowDiscrepancySampler, RandomPixelSampler, RandomSampler,
                        StratifiedSampler, TilePixelSampler)
@@ -33,6 +33,7 @@ def RegisterStandardPlugins():
     Plugin.register("surfaceIntegrator", "whitted", WhittedIntegrator.Create)
     Plugin.register("surfaceIntegrator", "ambientocclusion", AmbientOcclusionIntegrator.Create)
     Plugin.register("surfaceIntegrator", "feature", FeatureIntegrator.Create)
+    Plugin.register("surfaceIntegrator", "material", MaterialIntegrator.Create)
     Plugin.register("surfaceIntegrator", "diffuseprt", DiffusePRTIntegrator.Create)
     Plugin.register("surfaceIntegrator", "glossyprt", GlossyPRTIntegrator.Create)
     Plugin.register("surfaceIntegrator", "useprobes", UseProbesIntegrator.Create)

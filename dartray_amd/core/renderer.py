@@ -375,6 +375,42 @@ class FeatureIntegrator:
         return FeatureIntegrator((params or {}).get("channel", "ng"))
 
 
+class MaterialIntegrator:
+    """The first-hit material integrator (DR_INTEGRATOR_MATERIAL, k_shade_material; the reference has no such class), the
+    feature integrator's sibling for what reads a material or a light: Li is, by `channel`, "albedo" -- the camera hit's material colour, Kd of
+    matte and plastic, Kr of mirror and glass, 0 where the ray hits nothing -- or "emission" -- what Li of the Path, DirectLighting and Whitted
+    integrators adds for the camera ray itself: isect.Le(-ray.d) at a hit, the lights' Le(ray) at a miss."""
+
+    CHANNELS = {"albedo": _abi.DR_MATERIAL_CHANNEL_ALBEDO, "emission": _abi.DR_MATERIAL_CHANNEL_EMISSION}
+
+    def __init__(self, channel="albedo"):
+        if channel not in self.CHANNELS:
+            raise ValueError("material integrator: channel must be one of albedo, emission (got %r)" % (channel,))
+        self.channel = channel
+
+    kind = _abi.DR_INTEGRATOR_MATERIAL
+    maxDepth = 0  # (not read by the device under this integrator; SamplerRenderer.describe marshals every integrator's)
+    li_draws_recorded = False  # (Li draws nothing: a host-buffer replay needs neither tail nor seed)
+
+    def requestSamples(self, sampler, scene):
+        """No slots of its own."""
+        return [], []
+
+    def check_sampler(self, sampler):
+        """SamplerRenderer.describe: what this integrator asks of the renderer's sampler."""
+        if isinstance(sampler, AdaptiveSampler):
+            raise ValueError("material integrator: the adaptive sampler is not supported")
+
+    def to_abi(self, d):
+        """SamplerRenderer.describe, behind the sampler's own fields: the channel (a member of feature_channel's union: include/dartray_hip.h)."""
+        d.material_channel = self.CHANNELS[self.channel]
+
+    @staticmethod
+    def Create(params=None):
+        """`string channel`: albedo (the default) or emission."""
+        return MaterialIntegrator((params or {}).get("channel", "albedo"))
+
+
 class EmissionIntegrator:
     """volume_integrators/emission_integrator.dart with no VolumeRegion: T = 1,
     Lv = 0; its only effect on the path is the two 1-D sample slots it requests."""

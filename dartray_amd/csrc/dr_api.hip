@@ -311,6 +311,11 @@ int dr_feature_check(int32_t channel, uint64_t nprimitives) {
   return DR_OK;
 }
 
+int dr_material_check(int32_t channel) {
+  if (const char* why = materialRefusal(channel)) return fail(DR_ERR_INVALID, why);
+  return DR_OK;
+}
+
 int32_t dr_scene_sample_floats(const DrScene* scene, int32_t integrator) {
   if (!scene) return -1;
   if (!knownIntegrator(integrator)) return dr_sample_floats(integrator, scene->d.nlights);
@@ -605,6 +610,12 @@ int planRender(RenderPlan& P) {
         if (sc->prtMaterials[i] != DR_MATERIAL_MATTE)
           return fail(DR_ERR_UNSUPPORTED, std::string("use probes: material ") + names[std::min(3, std::max(-1, sc->prtMaterials[i])) + 1] + " (material " +
                                               std::to_string(i) + " of the scene) is not supported: only matte with sigma 0 is");
+      P.nStages = 1;
+      break;
+    }
+    case IntegratorKind::Material: {  // the camera hit's material colour or emitted radiance, one stage, nothing traced behind it
+      if (const char* why = materialRefusal(rd->material_channel)) return fail(DR_ERR_INVALID, why);
+      P.material.channel = rd->material_channel;
       P.nStages = 1;
       break;
     }
@@ -927,6 +938,7 @@ int32_t lastInfoWord(const RenderPlan& P) {
     case IntegratorKind::DiffusePRT: return DR_INTEGRATOR_DIFFUSE_PRT | 0x8000;  // bit 15: k_shade_prt
     case IntegratorKind::GlossyPRT: return DR_INTEGRATOR_GLOSSY_PRT | 0x10000;  // bit 16: k_shade_gprt + k_gprt_finish
     case IntegratorKind::UseProbes: return DR_INTEGRATOR_USE_PROBES | 0x20000;  // bit 17: k_shade_probes
+    case IntegratorKind::Material: return DR_INTEGRATOR_MATERIAL | 0x40000 | (P.material.channel << 19);  // bit 18: k_shade_material; bit 19: its channel
   }
   return -1;
 }

@@ -277,6 +277,7 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
       L.shade_probes(sc->d, stS, q, a, P.sgrid, s);
       break;
     }
+    case IntegratorKind::Material: L.shade_material(sc->d, stS, q, P.material.channel, P.sgrid, s); break;  // (the only stage: nothing is traced behind it)
   }
   hipEvent_t evMid = nullptr;
   if (stageCounts && P.envStage) {

@@ -291,7 +291,7 @@ struct SampleForm {
   X(halton_select, launch_halton_select) X(gen_halton, launch_gen_halton) X(gen_random, launch_gen_random) X(mark_alive, launch_mark_alive)   \
   X(sum_alive, launch_sum_alive) X(transpose_samples, launch_transpose_samples) X(raygen, launch_raygen) X(shade_path, launch_shade_path)   \
   X(env, launch_env) X(shade_direct, launch_shade_direct) X(shade_spec, launch_shade_spec) X(shade_whitted, launch_shade_whitted)          \
-  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(shade_gprt, launch_shade_gprt) X(gprt_finish, launch_gprt_finish) X(shade_probes, launch_shade_probes) X(film, launch_film) \
+  X(shade_ao, launch_shade_ao) X(shade_feature, launch_shade_feature) X(shade_prt, launch_shade_prt) X(shade_gprt, launch_shade_gprt) X(gprt_finish, launch_gprt_finish) X(shade_probes, launch_shade_probes) X(shade_material, launch_shade_material) X(film, launch_film) \
   X(guides, launch_guides) X(guide_plane, launch_guide_plane)
 struct LayoutOps {
 #define DR_LAYOUT_MEMBER(member, fn) decltype(&fn) member;
@@ -323,7 +323,7 @@ constexpr SamplerTraits kSamplerTraits[] = {
 // dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
 // source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
 // (no kind 6: the ABI leaves that value unassigned -- see DR_INTEGRATOR_DIFFUSE_PRT in dartray_hip.h -- and knownIntegrator refuses it like any other unknown value)
-enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7, GlossyPRT = 9, UseProbes = 11 };
+enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7, GlossyPRT = 9, UseProbes = 11, Material = 13 };
 struct IntegratorTraits {
   bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
   int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
@@ -361,12 +361,17 @@ constexpr IntegratorTraits kIntegratorTraits[] = {
     {true, 0, 0, false, false, nullptr, nullptr},  // (10: unassigned like 6 and 8 -- what the library answers for it is pinned by tests/test_glossy_prt_integrator.py)
     // UseProbes (use_probes_integrator.dart:74-88): requestSamples asks for the scene's DirectLighting "all" slots although Li never
     // reads them (the grid includes the direct light); one stage, no ray beyond the camera's; max_depth is not read
-    {true, 0, 0, false, false, nullptr, "use probes: the adaptive sampler is not supported (its second pass has no test under this integrator; every other sampler mode is)"}};
+    {true, 0, 0, false, false, nullptr, "use probes: the adaptive sampler is not supported (its second pass has no test under this integrator; every other sampler mode is)"},
+    {true, 0, 0, false, false, nullptr, nullptr},  // (12: unassigned like 6, 8 and 10 -- what the library answers for it is pinned by tests/test_probes_integrator.py and tests/test_guides.py)
+    // Material (no reference class): the feature integrator's row -- no requestSamples, tau + scatter only; one stage, no ray beyond
+    // the camera's; max_depth is not read
+    {false, 2, 0, false, false, nullptr, "material integrator: the adaptive sampler is not supported"}};
 static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
                   (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
                   (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && (int)IntegratorKind::Feature == DR_INTEGRATOR_FEATURE &&
                   (int)IntegratorKind::DiffusePRT == DR_INTEGRATOR_DIFFUSE_PRT && (int)IntegratorKind::GlossyPRT == DR_INTEGRATOR_GLOSSY_PRT &&
-                  (int)IntegratorKind::UseProbes == DR_INTEGRATOR_USE_PROBES && sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 12, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
+                  (int)IntegratorKind::UseProbes == DR_INTEGRATOR_USE_PROBES && (int)IntegratorKind::Material == DR_INTEGRATOR_MATERIAL &&
+                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 14, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
 // The one value inside the table's range that names no integrator: its row is a placeholder.  An integrator added later takes the value behind the
 // last one, not this one -- what the library answers for it is pinned behaviour (tests/test_feature_integrator.py)
 constexpr int32_t kUnassignedIntegrator = 6;
@@ -383,9 +388,14 @@ constexpr int32_t kUnassignedIntegrator3 = 10;
 static_assert(DR_INTEGRATOR_GLOSSY_PRT < kUnassignedIntegrator3 && kUnassignedIntegrator3 < DR_INTEGRATOR_USE_PROBES &&
                   kIntegratorTraits[kUnassignedIntegrator3].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator3].adaptive,
               "the third unassigned value lies between the glossy PRT and the probe integrator and its row is the placeholder");
+// ... and the fourth, between the probe and the material integrator (tests/test_probes_integrator.py pins dr_sample_floats(12, 3), tests/test_guides.py its refusal)
+constexpr int32_t kUnassignedIntegrator4 = 12;
+static_assert(DR_INTEGRATOR_USE_PROBES < kUnassignedIntegrator4 && kUnassignedIntegrator4 < DR_INTEGRATOR_MATERIAL &&
+                  kIntegratorTraits[kUnassignedIntegrator4].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator4].adaptive,
+              "the fourth unassigned value lies between the probe and the material integrator and its row is the placeholder");
 inline bool knownIntegrator(int32_t v) {
   return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && v != kUnassignedIntegrator && v != kUnassignedIntegrator2 &&
-         v != kUnassignedIntegrator3;
+         v != kUnassignedIntegrator3 && v != kUnassignedIntegrator4;
 }
 
 // The feature integrator's refusals (dr_feature_check, planRender): null, or the text and its code
@@ -398,6 +408,13 @@ inline const char* featureRefusal(int32_t channel, uint64_t nprims, int* code) {
     *code = DR_ERR_UNSUPPORTED;
     return "feature integrator: the id channel needs a scene of fewer than 2^24 primitives (an index + 1 must be exact in the film's f32)";
   }
+  return nullptr;
+}
+
+// The material integrator's refusal (dr_material_check, planRender): null, or the text
+inline const char* materialRefusal(int32_t channel) {
+  if (channel != DR_MATERIAL_CHANNEL_ALBEDO && channel != DR_MATERIAL_CHANNEL_EMISSION)
+    return "material integrator: unknown channel (DR_MATERIAL_CHANNEL_ALBEDO or _EMISSION)";
   return nullptr;
 }
 
@@ -416,6 +433,7 @@ inline const char* guidesRefusal(const DrRenderDesc* rd, const DrGuidesDesc* g, 
     case IntegratorKind::DiffusePRT: return "render guides: the diffuse PRT integrator is not supported (guides beside its side buffer have no test)";
     case IntegratorKind::GlossyPRT: return "render guides: the glossy PRT integrator is not supported (guides beside its side buffers have no test)";
     case IntegratorKind::UseProbes: return "render guides: the use probes integrator is not supported (guides under it have no test)";
+    case IntegratorKind::Material: return "render guides: the material integrator is not supported (its image is a guide already: render it as it is)";
   }
   if (rd->sampler_mode == DR_SAMPLER_ADAPTIVE) return "render guides: the adaptive sampler is not supported (the feature integrator refuses it; a second pass would write its guides twice)";
   *code = DR_ERR_INVALID;
@@ -471,6 +489,7 @@ struct RenderPlan {
   // (a round is perRound + 1 stages: CounterLayout::maxStages() bounds it); the rays' extent
   struct { int nSamples = 0, perRound = 0, rounds = 0; double minDist = 0.0, maxDist = 0.0; } ao;
   struct { int channel = 0; } feature;  // Feature: DR_FEATURE_*
+  struct { int channel = 0; } material;  // Material: DR_MATERIAL_CHANNEL_*
   // A guide render (dr_render_guides_device): n channels (0: none, every other render), the set as k_guides' mask, and per
   // requested channel its film and its side plane (its rank in the mask).  The side planes cap the batch (planBatches) and are sized by prepareRender
   struct { int n = 0; uint32_t mask = 0u; float* film[DR_GUIDES_MAX] = {}; int plane[DR_GUIDES_MAX] = {}; } guides;

@@ -48,6 +48,8 @@ void launch_shade_ao(const DScene& sc, const RenderParams& rp, const BatchState&
                      double minDist, double maxDist, int grid, hipStream_t s);
 // dr_shade_feature.hip: the one stage of the feature integrator -- channel DR_FEATURE_* of every slot's camera hit as its radiance (a miss: 0)
 void launch_shade_feature(const DScene& sc, const BatchState& st, const StageQueues& q, int channel, int grid, hipStream_t s);
+// dr_shade_material.hip: the one stage of the material integrator -- channel DR_MATERIAL_CHANNEL_* of every slot's camera ray as its radiance
+void launch_shade_material(const DScene& sc, const BatchState& st, const StageQueues& q, int channel, int grid, hipStream_t s);
 // dr_guides.hip (DESIGN.md 2.26): behind the camera rays' traversal, the DR_FEATURE_* channels of `mask` (bit = channel) of every slot's camera hit
 // into the side planes of `side` ([3 * channels][sideCap] floats; a miss: 0); and, at the batch's film step, plane `plane` (the channel's rank in
 // the mask) into the state's radiance plane, from where launch_film adds it to the channel's film

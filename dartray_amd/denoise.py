@@ -31,6 +31,13 @@ and firefly suppression, the outlier clamp that runs ahead of all of them (DESIG
     render_firefly(renderer, scene, ...)                         renders the beauty image and its two guides, and clamps
     render_denoised / _pair / render_upsampled / render_sequence(..., firefly=True)    ... ahead of the filter, the upsampler, the history
 
+and demodulation, which takes what is known without noise out of the beauty image before all of them and puts it back after the last
+(dr_demodulate*, dr_remodulate*; the images are core.MaterialIntegrator's):
+
+    demodulate(rgb, emission, albedo, ...)                       max(0, rgb - emission) / (albedo + eps)
+    remodulate(rgb, emission, albedo, ...)                       rgb * (albedo + eps) + emission
+    render_denoised / _pair / render_sequence(..., demodulate=True)    ... around the filter: the emitters' pixels are never filtered
+
 The library takes sharpness values k = 1 / sigma^2 (k = 0: the term is off); this module takes the sigmas.
 """
 import copy
@@ -42,7 +49,7 @@ import numpy as np
 from . import _abi
 from ._image import _beauty_and_guides, _check_channel, _check_one_pass, _entry, _guides, _images, _rerender, _whole_film_refusals
 from .core.cameras import PerspectiveCamera
-from .core.renderer import FeatureIntegrator, OutputImage, SamplerRenderer  # noqa: F401  (the first and last: read from here by tools/)
+from .core.renderer import FeatureIntegrator, MaterialIntegrator, OutputImage, SamplerRenderer  # noqa: F401  (the first and last: read from here by tools/)
 from .core.samplers import AdaptiveSampler
 
 # The defaults: five levels reach 2 * 16 pixels to either side; the colour sigma is one unit of radiance at the first
@@ -85,24 +92,35 @@ def atrous(rgb, normal, depth, iterations=ITERATIONS, sigma_color=SIGMA_COLOR, s
     return out
 
 
-def render_denoised(renderer, scene, normal_channel="ns", firefly=False, one_pass=False, **filter_kw):
+def render_denoised(renderer, scene, normal_channel="ns", firefly=False, one_pass=False, demodulate=False, **filter_kw):
     """Renders the beauty image with `renderer` as given and two FeatureIntegrator images -- `normal_channel` ("ns" or "ng") and "depth" --
     with the same camera, film, sampler and work split, filters, and returns an OutputImage whose rgb is the result; the three unfiltered
     images stay on it as `noisy` [h, w, 3], `normal` [h, w, 3] and `depth` [h, w].  filter_kw: atrous()'s keywords.  firefly: True, or a
     dict of firefly()'s parameters, clamps the beauty image's outliers before the filter; `noisy` stays the unclamped
     render and the luminance taken away stays on the result as `removed`.  one_pass=True: the beauty image and both guides come from one
-    render (render_with_guides) instead of three, the same bytes; an integrator it does not serve raises ValueError."""
+    render (render_with_guides) instead of three, the same bytes; an integrator it does not serve raises ValueError.
+    demodulate: True, or a tuple of "emission" and / or "albedo", renders those MaterialIntegrator images with the renderer's own sampler and
+    work split, takes them out of the beauty image before every other stage, the firefly clamp included, and puts them back after the filter
+    (DESIGN.md 2.27); the images stay on the result as `emission` / `albedo`, the demodulated render as `demodulated`.  It runs where the
+    filter runs (filter_kw's `device`).  It cannot be combined with one_pass."""
     _check_channel("render_denoised", normal_channel)
     fkw = _firefly_kw("render_denoised", firefly)
+    dm = _demodulate_kw("render_denoised", demodulate, one_pass)
     if isinstance(renderer.sampler, AdaptiveSampler):
         raise ValueError("render_denoised: the adaptive sampler is not supported (the feature integrator refuses it)")
     _check_one_pass("render_denoised", one_pass, renderer, scene, normal_channel)
     beauty, normal, depth = _beauty_and_guides(renderer, scene, normal_channel, one_pass)
-    clamped, removed = _clamped(fkw, beauty.rgb, normal, depth)
-    out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, atrous(clamped, normal, depth, **filter_kw), beauty.film)
+    mats = _material_images(renderer, scene, dm)
+    on_device = filter_kw.get("device", True)
+    base = _demodulated(dm, mats, beauty.rgb, on_device)
+    clamped, removed = _clamped(fkw, base, normal, depth)
+    rgb = _remodulated(dm, mats, atrous(clamped, normal, depth, **filter_kw), on_device)
+    out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, rgb, beauty.film)
     out.noisy, out.normal, out.depth = beauty.rgb, normal, depth
     if fkw is not None:
         out.removed = removed
+    if dm is not None:
+        _keep_material(out, mats, base)
     return out
 
 
@@ -131,7 +149,7 @@ def pair_seed(seed):
     return int(seed) ^ SEED_B_XOR
 
 
-def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", firefly=False, one_pass=False, **filter_kw):
+def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", firefly=False, one_pass=False, demodulate=False, **filter_kw):
     """Renders the scene twice -- half A with `renderer` as given, half B with a shallow copy of its sampler whose seed is `seed_b` (default:
     pair_seed of the sampler's seed) -- and the two guides as render_denoised does, all four with the same camera, integrators and work
     split, and filters the halves' mean with atrous_pair.  Returns an OutputImage whose rgb is the result; `a`, `b`, `noisy` (the mean),
@@ -144,9 +162,14 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", fire
     pixel of one half no longer inflates the variance estimate its neighbours share; `a`, `b` and `noisy` stay the unclamped renders, and
     the luminance taken from the halves stays on the result as `removed` = (removed_a, removed_b).
 
-    one_pass=True: the guides ride on half A's render (render_with_guides) -- three renders instead of four, the same bytes."""
+    one_pass=True: the guides ride on half A's render (render_with_guides) -- three renders instead of four, the same bytes.
+
+    demodulate: as for render_denoised; the material images are rendered once, with half A's sampler, and each half is demodulated by the
+    same images before its firefly clamp (the images are noise-free: what differs between two seeds is the film's sub-pixel coverage at
+    an edge).  `variance` is then the demodulated colour's; `demodulated` = (a, b) demodulated."""
     _check_channel("render_denoised_pair", normal_channel)
     fkw = _firefly_kw("render_denoised_pair", firefly)
+    dm = _demodulate_kw("render_denoised_pair", demodulate, one_pass)
     sampler = renderer.sampler
     if isinstance(sampler, AdaptiveSampler):
         raise ValueError("render_denoised_pair: the adaptive sampler is not supported (the feature integrator refuses it)")
@@ -165,13 +188,19 @@ def render_denoised_pair(renderer, scene, seed_b=None, normal_channel="ns", fire
         half_a = renderer.render(scene)
         half_b = _rerender(renderer, scene, renderer.surfaceIntegrator, sampler_b)
         normal, depth = _guides(renderer, scene, normal_channel)
+    mats = _material_images(renderer, scene, dm)
+    on_device = filter_kw.get("device", True)
     filter_kw = dict(filter_kw, return_variance=True)
-    (a, removed_a), (b, removed_b) = _clamped(fkw, half_a.rgb, normal, depth), _clamped(fkw, half_b.rgb, normal, depth)
+    base_a, base_b = _demodulated(dm, mats, half_a.rgb, on_device), _demodulated(dm, mats, half_b.rgb, on_device)
+    (a, removed_a), (b, removed_b) = _clamped(fkw, base_a, normal, depth), _clamped(fkw, base_b, normal, depth)
     rgb, variance = atrous_pair(a, b, normal, depth, **filter_kw)
+    rgb = _remodulated(dm, mats, rgb, on_device)
     out = OutputImage(half_a.xOffset, half_a.yOffset, half_a.width, half_a.height, rgb, half_a.film)
     out.a, out.b, out.normal, out.depth, out.variance = half_a.rgb, half_b.rgb, normal, depth, variance
     if fkw is not None:
         out.removed = (removed_a, removed_b)
+    if dm is not None:
+        _keep_material(out, mats, (base_a, base_b))
     with np.errstate(all="ignore"):
         out.noisy = np.float32(0.5) * (out.a + out.b)
     return out
@@ -389,6 +418,83 @@ def _clamped(kw, rgb, normal, depth):
     return (rgb, None) if kw is None else firefly(rgb, normal, depth, **dict(kw, return_removed=True))
 
 
+# Demodulation's one parameter, reasoned and not tuned on any scene.  eps only matters where the albedo is close to 0: the
+# same a + eps divides and multiplies back, so on an unfiltered pixel it cancels up to two roundings.  What it sets is the gain, 1 / (a + eps),
+# with which a dark surface's noise enters the filter: at most 1000.  The darkest common materials reflect about 3 % (a = 0.03: gain 32, which
+# eps changes by 3 %); a surface of a = 0 reflects nothing, so rgb - e is 0 there and the gain multiplies 0.  1e-3 is also far above f32's
+# spacing at 1, so a + eps != a for every albedo up to 1.
+DEMODULATE_EPS = 1.0e-3
+MATERIAL_CHANNELS = ("emission", "albedo")
+
+
+def demodulate_params(eps=DEMODULATE_EPS):
+    return _abi.DrDemodulateParams(float(eps))
+
+
+def _modulate(entry, who, rgb, emission, albedo, eps, device):
+    present = [a for a in (emission, albedo) if a is not None]
+    imgs = _images(who, "rgb, emission and albedo must be [h, w, 3]", [rgb] + present)
+    rgb, rest = imgs[0], iter(imgs[1:])
+    emission = next(rest) if emission is not None else None
+    albedo = next(rest) if albedo is not None else None
+    h, w = rgb.shape[:2]
+    p = demodulate_params(eps)
+    out = np.zeros_like(rgb)
+    _abi.check(_entry(entry, device)(rgb.ctypes.data, emission.ctypes.data if emission is not None else None,
+                                     albedo.ctypes.data if albedo is not None else None, w, h, C.byref(p), out.ctypes.data))
+    return out
+
+
+def demodulate(rgb, emission=None, albedo=None, eps=DEMODULATE_EPS, device=True):
+    """rgb [h, w, 3], emission [h, w, 3] or None, albedo [h, w, 3] or None -> max(0, rgb - emission) / (albedo + eps), [h, w, 3] f32
+    (DESIGN.md 2.27).  An absent emission is 0; an absent albedo makes the divisor 1.  A pixel with a value that is not finite keeps its rgb
+    bits.  device=True: dr_demodulate, on the GPU; device=False: dr_demodulate_host, which needs none and writes the same bytes."""
+    return _modulate("dr_demodulate", "demodulate", rgb, emission, albedo, eps, device)
+
+
+def remodulate(rgb, emission=None, albedo=None, eps=DEMODULATE_EPS, device=True):
+    """The inverse after the filters: rgb * (albedo + eps) + emission, with demodulate()'s images and eps.  device as for demodulate()."""
+    return _modulate("dr_remodulate", "remodulate", rgb, emission, albedo, eps, device)
+
+
+def _demodulate_kw(who, demodulate, one_pass=False):
+    """The `demodulate` keyword of a render_* function as the tuple of material channels to render, or None where the stage is off."""
+    if demodulate is False or demodulate is None:
+        return None
+    if demodulate is True:
+        channels = MATERIAL_CHANNELS
+    elif isinstance(demodulate, (tuple, list)) and demodulate and all(c in MATERIAL_CHANNELS for c in demodulate) \
+            and len(set(demodulate)) == len(demodulate):
+        channels = tuple(c for c in MATERIAL_CHANNELS if c in demodulate)
+    else:
+        raise ValueError("%s: demodulate must be False, True or a tuple of \"emission\" and / or \"albedo\", got %r" % (who, demodulate))
+    if one_pass:
+        raise ValueError("%s: one_pass=True together with demodulate is not supported (the one-pass guide render has no material channels: "
+                         "render the guides separately)" % (who,))
+    return channels
+
+
+def _material_images(renderer, scene, channels, sampler=None):
+    """{channel: [h, w, 3]} of the MaterialIntegrator renders of `channels` (None: {}) with `renderer`'s camera, sampler and work split."""
+    return {c: _rerender(renderer, scene, MaterialIntegrator(c), sampler).rgb for c in (channels or ())}
+
+
+def _demodulated(channels, mats, rgb, device=True):
+    """rgb after demodulate() by the rendered images -- or rgb itself where the stage is off (channels None)."""
+    return rgb if channels is None else demodulate(rgb, mats.get("emission"), mats.get("albedo"), device=device)
+
+
+def _remodulated(channels, mats, rgb, device=True):
+    return rgb if channels is None else remodulate(rgb, mats.get("emission"), mats.get("albedo"), device=device)
+
+
+def _keep_material(out, mats, demodulated):
+    """The material images and the demodulated render(s), beside the other parts on a render_* function's result."""
+    for c, img in mats.items():
+        setattr(out, c, img)
+    out.demodulated = demodulated
+
+
 def render_firefly(renderer, scene, normal_channel="ns", one_pass=False, **firefly_kw):
     """Renders the beauty image and the two guides as render_denoised does and clamps its fireflies.  Returns an OutputImage whose rgb is
     the result; `noisy` (the unclamped render), `normal`, `depth` and `removed` stay on it.  firefly_kw: firefly()'s keywords.
@@ -443,7 +549,7 @@ def atrous_moments(frame, iterations=ITERATIONS, sigma_color=SIGMA_COLOR_PAIR, s
 
 
 def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_tol=DEPTH_TOL, normal_tol=NORMAL_TOL, max_history=MAX_HISTORY,
-                    firefly=False, one_pass=False, **kw):
+                    firefly=False, one_pass=False, demodulate=False, **kw):
     """Renders one frame per renderer -- one camera pose each, in the order of the animation -- with its beauty image and two
     FeatureIntegrator images, `normal_channel` ("ns" or "ng") and "depth", as render_denoised does, and accumulates each into the history of
     the frames before it with temporal().  Returns the list of frames: OutputImages whose rgb is the accumulated colour, or with denoise=True
@@ -464,11 +570,19 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
     one_pass=True: a frame whose sampler carries the guides' seed -- the first frame, and every frame of a sequence that shares one seed or
     whose sampler has none -- takes its beauty image and its guides from one render (render_with_guides), the same bytes.  A
     frame with a seed of its own keeps its two FeatureIntegrator renders: its guides are sampled with another seed than its beauty image, so
-    they have no beauty render to ride on."""
+    they have no beauty render to ride on.
+
+    demodulate: as for render_denoised.  Each frame's material images are rendered with the frame's own sampler, the frame is demodulated
+    before its firefly clamp and temporal(), and the filter's output (or, without a filter, the accumulated colour) is remodulated by the
+    frame's own images: the history -- `accumulated`, `m2`, `variance`, `history` -- holds demodulated colour, so an emitter that comes into
+    view is never blended with what the history saw there before.  The images stay on each frame as `emission` / `albedo`.  Measured on C2
+    with a seed per frame this makes the moments filter worse, not better (MEASUREMENTS.md, "Demodulation": the history's frames were
+    demodulated by their own images and are remodulated by the last frame's alone)."""
     who = "render_sequence"
     _check_channel(who, normal_channel)
     renderers = list(renderers)
     fkw = _firefly_kw(who, firefly)
+    dm = _demodulate_kw(who, demodulate, one_pass)
     if not any(denoise is v for v in (False, True)) and denoise != "moments":
         raise ValueError("%s: denoise must be False, True or \"moments\", got %r" % (who, denoise))
     if kw and not denoise:
@@ -494,13 +608,17 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
         else:
             beauty = r.render(scene)
             normal, depth = _guides(r, scene, normal_channel, guide_sampler)
-        clamped, removed = _clamped(fkw, beauty.rgb, normal, depth)
+        mats = _material_images(r, scene, dm)
+        on_device = kw.get("device", True)
+        base = _demodulated(dm, mats, beauty.rgb, on_device)
+        clamped, removed = _clamped(fkw, base, normal, depth)
         history = temporal(clamped, normal, depth, history, m, depth_tol=depth_tol, normal_tol=normal_tol, max_history=max_history)
         filtered_variance = None
         if denoise == "moments":
             rgb, filtered_variance = atrous_moments(history, **dict(kw, return_variance=True, return_estimate=False))
         else:
             rgb = atrous(history.rgb, normal, depth, **kw) if denoise else history.rgb
+        rgb = _remodulated(dm, mats, rgb, on_device)
         out = OutputImage(beauty.xOffset, beauty.yOffset, beauty.width, beauty.height, rgb, beauty.film)
         if filtered_variance is not None:
             out.filtered_variance = filtered_variance
@@ -508,5 +626,7 @@ def render_sequence(renderers, scene, normal_channel="ns", denoise=False, depth_
         out.m2, out.len, out.variance, out.history = history.m2, history.len, history.variance, history
         if fkw is not None:
             out.removed = removed
+        if dm is not None:
+            _keep_material(out, mats, base)
         frames.append(out)
     return frames

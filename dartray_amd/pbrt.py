@@ -1088,13 +1088,17 @@ def _write_pfm(path, rgb):
 
 def main(argv=None):
     """python -m dartray_amd.pbrt scene.pbrt [-o out.pfm|out.npy|out.png|out.ppm] [--spp N] [--xres W --yres H] [--upsample 2|4]
-    [--firefly] [--exposure auto|SCALE] [--tonemap clamp|reinhard|filmic] [--encode srgb|gamma22|reference]
+    [--firefly] [--demodulate] [--exposure auto|SCALE] [--tonemap clamp|reinhard|filmic] [--encode srgb|gamma22|reference]
 
     --upsample F traces the beauty image at 1/F of the film's resolution per axis and brings it to the full resolution under full-resolution
     normal and depth images (denoise.render_upsampled).
 
     --firefly clamps the beauty image's outliers under its normal and depth images with the default parameters (denoise.render_firefly;
     DESIGN.md 2.25); with --upsample, the low-resolution image's before it is upsampled.
+
+    --demodulate renders the albedo and emission images beside the beauty image, takes them out of it, filters the rest with the a-trous
+    denoiser under its normal and depth images and puts them back, so that emitters in view are never filtered
+    (denoise.render_denoised(demodulate=True)); with --firefly the clamp runs on the demodulated image.  Not with --upsample.
 
     .png and .ppm go through the display transform (dartray_amd/display.py), which the three last flags choose; .npy and
     every other suffix hold the linear f32 radiance."""
@@ -1108,11 +1112,15 @@ def main(argv=None):
     ap.add_argument("--yres", type=int)
     ap.add_argument("--upsample", type=int, choices=[2, 4], help="trace 1/2 or 1/4 of the resolution per axis and upsample under full-resolution guides")
     ap.add_argument("--firefly", action="store_true", help="clamp pixels far brighter than their same-surface neighbours (two more feature renders)")
+    ap.add_argument("--demodulate", action="store_true",
+                    help="denoise with the emitted light and the albedo taken out before the filter and put back after it (four more first-hit renders)")
     ap.add_argument("--exposure", default="auto", help=".png / .ppm: auto (the median luminance goes to 0.18), or the scale as a number")
     ap.add_argument("--tonemap", default="reinhard", choices=["clamp", "reinhard", "filmic"])
     ap.add_argument("--encode", default="srgb", choices=["srgb", "gamma22", "reference"])
     a = ap.parse_args(argv)
     displayed = bool(a.output) and a.output.endswith((".png", ".ppm"))
+    if a.demodulate and a.upsample:
+        ap.error("--demodulate cannot be combined with --upsample (render_upsampled has no demodulation stage)")
     if displayed and a.exposure != "auto":
         try:
             float(a.exposure)
@@ -1131,6 +1139,10 @@ def main(argv=None):
         from . import denoise
         out = denoise.render_upsampled(api.lowRendererObject, api.rendererObject, api.scene, firefly=a.firefly)
         st = api.lowRendererObject.last_stats
+    elif a.demodulate:
+        from . import denoise
+        out = denoise.render_denoised(api.rendererObject, api.scene, firefly=a.firefly, demodulate=True)
+        st = api.rendererObject.last_stats
     elif a.firefly:
         from . import denoise
         out = denoise.render_firefly(api.rendererObject, api.scene)

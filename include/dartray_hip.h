@@ -271,6 +271,14 @@ typedef struct DrFilm {
  * (requestSamples asks for them; Li does not read them).  No grid on the scene: DR_ERR_INVALID; a grid with includeDirect 0, a material other
  * than matte with sigma 0, DR_SAMPLER_ADAPTIVE: DR_ERR_UNSUPPORTED, by name.  max_depth is not read. */
 #define DR_INTEGRATOR_USE_PROBES 11 /* (10, like 6 and 8, stays unassigned) */
+/* The first-hit material integrator (the reference has none): the feature integrator's sibling for the two quantities
+ * that integrator does not have because it reads no material and no light by contract.  The radiance of a sample is, by
+ * DrRenderDesc.material_channel, the camera hit's material colour (albedo) or what Li of the Path, DirectLighting and Whitted integrators adds
+ * for the camera ray itself (emission: isect.Le(-ray.d) at a hit, the sum of the lights' Le(ray) at a miss) -- noise-free images aligned with
+ * the beauty image sample for sample, which dr_demodulate* takes out of it ahead of the filters.  max_depth is not read, no sample slots are
+ * requested (dr_sample_floats: 7), nothing is drawn inside Li.  One stage, no ray beyond the camera's.  An unknown channel is DR_ERR_INVALID
+ * (dr_material_check says so without a scene), DR_SAMPLER_ADAPTIVE with it DR_ERR_UNSUPPORTED; every other sampler mode is served. */
+#define DR_INTEGRATOR_MATERIAL 13 /* (12, like 6, 8 and 10, stays unassigned) */
 /* DrRenderDesc.feature_channel: R, G, B at a hit.  Every value is >= 0 (the renderer blacks out a sample of negative luminance). */
 #define DR_FEATURE_NG 0    /* 0.5 * (isect.dg.nn + 1): the geometric normal, world space, reverseOrientation applied */
 #define DR_FEATURE_NS 1    /* 0.5 * (bsdf.dgShading.nn + 1): Triangle.getShadingGeometry (per-vertex N / S); else the geometric one */
@@ -278,6 +286,9 @@ typedef struct DrFilm {
 #define DR_FEATURE_UV 3    /* dg.u, dg.v, 0 */
 #define DR_FEATURE_ID 4    /* primitive index + 1, material index + 1, 1 (indices of dr_scene_create's arrays); B is the coverage mask.
                             * Meaningful per sample, or with a box filter of width 0.5 at 1 spp: any other film averages ids */
+/* DrRenderDesc.material_channel: R, G, B of a camera sample.  Every value is >= 0 for colours and radiances that are. */
+#define DR_MATERIAL_CHANNEL_ALBEDO 0   /* the hit's material colour after Spectrum.clamp(): Kd of matte and plastic, Kr of mirror and glass; a miss: 0 */
+#define DR_MATERIAL_CHANNEL_EMISSION 1 /* isect.Le(-ray.d): Lemit of the hit's area light where Dot(dg.nn, -ray.d) > 0, else 0; a miss: the lights' Le(ray) */
 
 #define DR_SAMPLER_HOST_BUFFER 0 /* caller supplies sample vectors (+ the in-Li RNG draws) */
 #define DR_SAMPLER_COUNTER 1     /* on-device LD sampler, keyed per (pixel, block) / (pixel, sample) */
@@ -362,6 +373,7 @@ typedef struct DrRenderDesc {
   union {
     int32_t feature_channel; /* DR_INTEGRATOR_FEATURE: DR_FEATURE_* (the former padding at offset 1340: read under that integrator only) */
     int32_t prt_lmax;        /* DR_INTEGRATOR_DIFFUSE_PRT: lmax, 1 .. 8; DR_INTEGRATOR_GLOSSY_PRT: 1 .. 4 (reference default 4), read under those two only */
+    int32_t material_channel; /* DR_INTEGRATOR_MATERIAL: DR_MATERIAL_CHANNEL_*, read under that integrator only */
   };
   /* Optional packed form of `tail` (round 5): tail_offsets[nsamples + 1], non-decreasing; sample s owns
    * tail[tail_offsets[s] .. tail_offsets[s + 1]) -- the values it actually drew, in draw order (position p of the fixed
@@ -651,6 +663,35 @@ int dr_firefly(const float* rgb, const float* normal, const float* depth, int32_
 int dr_firefly_device(const void* rgb_dev, const void* normal_dev, const void* depth_dev, int32_t w, int32_t h, const DrFireflyParams* params,
                       void* out_dev, void* removed_dev, void* hip_stream);
 
+/* Demodulation: what is known per sample without noise is taken out of the beauty image before any other image stage
+ * and put back after the last.  rgb[h][w][3] is the beauty image; emission[h][w][3] and albedo[h][w][3] are the images of
+ * DR_INTEGRATOR_MATERIAL, and either may be NULL: an absent emission is 0, an absent albedo makes the divisor 1.  Per pixel and colour
+ * channel, f32 with one rounding per operator:
+ *   dr_demodulate*:  out = max(0, rgb - e) / (a + eps)        (the subtraction's result where it is > 0, else 0.0f)
+ *   dr_remodulate*:  out = f * (a + eps) + e                  (rgb is the filtered, demodulated image f)
+ * A pixel with a value of rgb, emission or albedo that is not finite is copied from rgb bit for bit by both.  out must not overlap an
+ * input.  The entry points of one operation write the same bytes. */
+typedef struct DrDemodulateParams {
+  float eps; /* finite, > 0: added to the albedo, so that a black surface divides by eps and not by 0 */
+} DrDemodulateParams; /* 4 bytes */
+/* Refused with DR_ERR_INVALID, by name: a null pointer (emission and albedo excepted), w or h < 1, w * h >= 2^31, an eps that is not
+ * finite or not positive, out overlapping an input.  dr_demodulate_check states those of the parameters and the size without an image. */
+int dr_demodulate_check(const DrDemodulateParams* params, int32_t w, int32_t h);
+/* Host buffers, a serial loop, no GPU needed -- the fallback and the device version's checker. */
+int dr_demodulate_host(const float* rgb, const float* emission, const float* albedo, int32_t w, int32_t h, const DrDemodulateParams* params,
+                       float* out);
+int dr_remodulate_host(const float* rgb, const float* emission, const float* albedo, int32_t w, int32_t h, const DrDemodulateParams* params,
+                       float* out);
+/* The same ON THE GPU (dr_demodulate_device.hip), host buffers: uploads, one launch, copies back.  Needs dr_init. */
+int dr_demodulate(const float* rgb, const float* emission, const float* albedo, int32_t w, int32_t h, const DrDemodulateParams* params, float* out);
+int dr_remodulate(const float* rgb, const float* emission, const float* albedo, int32_t w, int32_t h, const DrDemodulateParams* params, float* out);
+/* The same on device buffers, asynchronous on the given hipStream_t: one kernel launch (k_demodulate / k_remodulate), no scratch buffer and
+ * no size query, as for dr_firefly_device; the parameters are copied at the call. */
+int dr_demodulate_device(const void* rgb_dev, const void* emission_dev, const void* albedo_dev, int32_t w, int32_t h,
+                         const DrDemodulateParams* params, void* out_dev, void* hip_stream);
+int dr_remodulate_device(const void* rgb_dev, const void* emission_dev, const void* albedo_dev, int32_t w, int32_t h,
+                         const DrDemodulateParams* params, void* out_dev, void* hip_stream);
+
 /* The variance-guided a-trous denoiser over a temporal history (the variance estimate of Schied et al. 2017,
  * section 4.2, in front of the levels of section 2.19): rgb[h][w][3], m2[h][w] and len[h][w] are what dr_temporal* wrote last -- the
  * accumulated colour, the accumulated second moment of its luminance and the history length -- and normal and depth that frame's guides.
@@ -752,10 +793,10 @@ int dr_scene_set_trace_kernels(DrScene* scene, const uint32_t kernels[2]);
 int dr_scene_get_pilot(const DrScene* scene, float ms_per_gb_out[6]);
 /* Diagnostics: what the scene's LAST dr_render_device call actually ran with, switches (dr_set_option / environment)
  * included -- out[0] path-state layout (64 / 4), out[1] / out[2] the traversal kernel of its closest-hit / any-hit launches
- * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED, DR_INTEGRATOR_AO, DR_INTEGRATOR_FEATURE or DR_INTEGRATOR_DIFFUSE_PRT render the integrator and its shading
+ * (2, 3, 5 as above), out[3] -1, or after a DR_INTEGRATOR_WHITTED, DR_INTEGRATOR_AO, DR_INTEGRATOR_FEATURE, DR_INTEGRATOR_MATERIAL or DR_INTEGRATOR_DIFFUSE_PRT render the integrator and its shading
  * kernels: bits 0-7 the DR_INTEGRATOR_* constant, bit 8 k_shade_whitted ran, bit 9 k_shade_spec ran (the scene has mirror / glass), bit 10
  * k_shade_ao ran, bit 11 k_shade_feature ran (bits 12-14: its DR_FEATURE_* channel), bit 15 k_shade_prt ran, bit 16 k_shade_gprt and k_gprt_finish
- * ran (DR_INTEGRATOR_GLOSSY_PRT); out[4] the
+ * ran (DR_INTEGRATOR_GLOSSY_PRT), bit 17 k_shade_probes ran, bit 18 k_shade_material ran (bit 19: its DR_MATERIAL_CHANNEL_* channel); out[4] the
  * calibration batches it ran (0: no pilot), out[5] its batches, out[6] workgroups per CU of a persistent traversal
  * launch, out[7] bit 0: a stage's any-hit launch ran beside its closest-hit launch, bit 1: the camera rays went through the
  * wave-coherent kernel (k_trace_pk), bit 3: the device sampler generated bounce b's blocks only for the pixel
@@ -803,6 +844,9 @@ int32_t dr_scene_sample_floats(const DrScene* scene, int32_t integrator);
  * DR_ERR_INVALID (no such channel) or DR_ERR_UNSUPPORTED (DR_FEATURE_ID with 2^24 primitives or more: an index would no longer be exact in the
  * film's f32), with dr_last_error's text.  dr_render* apply the same rule to their scene. */
 int dr_feature_check(int32_t channel, uint64_t nprimitives);
+/* What a DR_INTEGRATOR_MATERIAL render of `channel` would answer, without a scene or a device: DR_OK, or DR_ERR_INVALID (no such channel)
+ * with dr_last_error's text.  dr_render* apply the same rule. */
+int dr_material_check(int32_t channel);
 /* DiffusePRTIntegrator.preprocess on the device: the scene's incident-light coefficients c_in for `lmax`, after
  * ReduceRinging, as out[(lmax + 1)^2][3] (RGB) -- what a DR_INTEGRATOR_DIFFUSE_PRT render of the scene uses (computed once per scene and lmax).
  * shutter_open is the reference's sample time; no light of the device path reads it.  lmax below 1 or above 8: DR_ERR_INVALID. */
@@ -1017,7 +1061,10 @@ const char* dr_version(void);
  * dr_denoise_moments_check, dr_denoise_moments_host, dr_denoise_moments and dr_denoise_moments_device; and firefly suppression: one new
  * struct, DrFireflyParams, that only its four new entry points read -- dr_firefly_check, dr_firefly_host, dr_firefly and
  * dr_firefly_device; and the one-pass guide render: one new struct, DrGuidesDesc, that only its three new entry points read --
- * dr_render_guides_check, dr_render_guides and dr_render_guides_device; no field of DrRenderDesc moved). */
+ * dr_render_guides_check, dr_render_guides and dr_render_guides_device; no field of DrRenderDesc moved; and DR_INTEGRATOR_MATERIAL: a new
+ * constant whose channel is a third member of feature_channel's union, read under that constant only, and one new entry point,
+ * dr_material_check; and demodulation: one new struct, DrDemodulateParams, that only its seven new entry points read -- dr_demodulate_check,
+ * dr_demodulate_host, dr_demodulate, dr_demodulate_device, dr_remodulate_host, dr_remodulate and dr_remodulate_device). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 
@@ -1123,6 +1170,7 @@ DR_ABI_OFFSET(DrRenderDesc, tail, 1328);
 DR_ABI_OFFSET(DrRenderDesc, ao_mindist, 1328);
 DR_ABI_OFFSET(DrRenderDesc, max_tail, 1336);
 DR_ABI_OFFSET(DrRenderDesc, feature_channel, 1340);
+DR_ABI_OFFSET(DrRenderDesc, material_channel, 1340);
 DR_ABI_OFFSET(DrRenderDesc, prt_nsamples, 1324);
 DR_ABI_OFFSET(DrRenderDesc, prt_lmax, 1340);
 DR_ABI_OFFSET(DrRenderDesc, tail_offsets, 1344);
@@ -1164,6 +1212,7 @@ DR_ABI_OFFSET(DrDenoiseMomentsParams, k_color, 4);
 DR_ABI_OFFSET(DrDenoiseMomentsParams, var_floor, 16);
 DR_ABI_OFFSET(DrDenoiseMomentsParams, min_history, 20);
 DR_ABI_OFFSET(DrDenoiseMomentsParams, radius, 24);
+DR_ABI_SIZE(DrDemodulateParams, 4);
 DR_ABI_SIZE(DrFireflyParams, 24);
 DR_ABI_OFFSET(DrFireflyParams, rank, 4);
 DR_ABI_OFFSET(DrFireflyParams, threshold, 8);

@@ -160,6 +160,7 @@ const int OFF_DrRenderDesc_tail = 1328;
 const int OFF_DrRenderDesc_ao_mindist = 1328;  // DR_INTEGRATOR_AO only: a double in the tail pointer's storage (that integrator reads no tail)
 const int OFF_DrRenderDesc_max_tail = 1336;
 const int OFF_DrRenderDesc_feature_channel = 1340;  // DR_INTEGRATOR_FEATURE only (the former padding)
+const int OFF_DrRenderDesc_material_channel = 1340;  // DR_INTEGRATOR_MATERIAL only (a member of the same union)
 const int OFF_DrRenderDesc_prt_nsamples = 1324;  // DR_INTEGRATOR_DIFFUSE_PRT only: a union member at ao_nsamples' offset
 const int OFF_DrRenderDesc_prt_lmax = 1340;  // DR_INTEGRATOR_DIFFUSE_PRT only: a union member at feature_channel's offset
 const int OFF_DrRenderDesc_ao_maxdist = 1344;  // likewise, in the storage of tail_offsets
@@ -268,6 +269,11 @@ const int DR_INTEGRATOR_USE_PROBES = 11;  // UseProbesIntegrator (10 is unassign
 const int SIZEOF_DrProbesDesc = 72, OFF_DrProbesDesc_lmax = 0, OFF_DrProbesDesc_include_indirect = 4, OFF_DrProbesDesc_npoints = 8,
     OFF_DrProbesDesc_has_bounds = 12, OFF_DrProbesDesc_bounds = 16, OFF_DrProbesDesc_camera_pos = 40, OFF_DrProbesDesc_spacing = 56,
     OFF_DrProbesDesc_time = 64;
+const int DR_INTEGRATOR_MATERIAL = 13;  // the first-hit material integrator (MaterialIntegrator below; 12 is unassigned): DrRenderDesc.material_channel
+const int DR_MATERIAL_CHANNEL_ALBEDO = 0, DR_MATERIAL_CHANNEL_EMISSION = 1;
+// DrDemodulateParams (demodulation around the image stages, DESIGN.md 2.27): f32 eps (finite, > 0; 1e-3 by default)
+const int SIZEOF_DrDemodulateParams = 4;
+const int OFF_DrDemodulateParams_eps = 0;
 const int DR_FEATURE_NG = 0, DR_FEATURE_NS = 1, DR_FEATURE_DEPTH = 2, DR_FEATURE_UV = 3, DR_FEATURE_ID = 4;
 // DrGuidesDesc (the channels of a guide render, DESIGN.md 2.26): int32 count (1..5), then int32 channels[5], DR_FEATURE_* values, none twice
 const int DR_GUIDES_MAX = 5;
@@ -404,6 +410,17 @@ typedef _RenderGuidesC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Pointer<U
 typedef _RenderGuidesD = int Function(Pointer<Void>, Pointer<Uint8>, Pointer<Uint8>, Pointer<Float>, Pointer<Float>, Pointer<Uint8>, Pointer<Uint8>);
 typedef _RenderGuidesDeviceC = Int32 Function(Pointer<Void>, Pointer<Uint8>, Pointer<Uint8>, Pointer<Void>, Pointer<Uint8>, Pointer<Void>);
 typedef _RenderGuidesDeviceD = int Function(Pointer<Void>, Pointer<Uint8>, Pointer<Uint8>, Pointer<Void>, Pointer<Uint8>, Pointer<Void>);
+// dr_material_check (what a DR_INTEGRATOR_MATERIAL render of a channel would answer, without a scene or a device)
+typedef _MaterialCheckC = Int32 Function(Int32);
+typedef _MaterialCheckD = int Function(int);
+// dr_demodulate_check, and dr_demodulate / dr_remodulate with their _host forms (DESIGN.md 2.27): rgb[h][w][3], emission[h][w][3] or null,
+// albedo[h][w][3] or null, w, h, DrDemodulateParams (4 bytes), out[h][w][3].  The _device forms take device addresses and a hipStream_t
+typedef _DemodulateCheckC = Int32 Function(Pointer<Uint8>, Int32, Int32);
+typedef _DemodulateCheckD = int Function(Pointer<Uint8>, int, int);
+typedef _DemodulateC = Int32 Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, Int32, Int32, Pointer<Uint8>, Pointer<Float>);
+typedef _DemodulateD = int Function(Pointer<Float>, Pointer<Float>, Pointer<Float>, int, int, Pointer<Uint8>, Pointer<Float>);
+typedef _DemodulateDeviceC = Int32 Function(Pointer<Void>, Pointer<Void>, Pointer<Void>, Int32, Int32, Pointer<Uint8>, Pointer<Void>, Pointer<Void>);
+typedef _DemodulateDeviceD = int Function(Pointer<Void>, Pointer<Void>, Pointer<Void>, int, int, Pointer<Uint8>, Pointer<Void>, Pointer<Void>);
 typedef _DestroyC = Void Function(Pointer<Void>);
 typedef _DestroyD = void Function(Pointer<Void>);
 typedef _ErrC = Pointer<Utf8> Function();
@@ -423,6 +440,23 @@ class FeatureIntegrator extends SurfaceIntegrator {
 
   Spectrum Li(Scene scene, Renderer renderer, RayDifferential ray, Intersection isect, Sample sample, RNG rng) {
     throw new UnsupportedError('feature integrator: evaluated on the device (HipSamplerRenderer)');
+  }
+
+  final int channel;
+}
+
+/// The first-hit material integrator (DESIGN.md 2.27), the feature integrator's sibling for what reads a material or a light: Li is channel
+/// DR_MATERIAL_CHANNEL_ALBEDO (the camera hit's material colour; 0 at a miss) or _EMISSION (isect.Le(-ray.d) at a hit, the lights' Le(ray) at a
+/// miss).  It exists on the device only (DR_INTEGRATOR_MATERIAL, k_shade_material), like FeatureIntegrator.
+class MaterialIntegrator extends SurfaceIntegrator {
+  MaterialIntegrator(this.channel) {
+    if (channel != DR_MATERIAL_CHANNEL_ALBEDO && channel != DR_MATERIAL_CHANNEL_EMISSION) {
+      throw new ArgumentError('material integrator: unknown channel (DR_MATERIAL_CHANNEL_ALBEDO or _EMISSION)');
+    }
+  }
+
+  Spectrum Li(Scene scene, Renderer renderer, RayDifferential ray, Intersection isect, Sample sample, RNG rng) {
+    throw new UnsupportedError('material integrator: evaluated on the device (HipSamplerRenderer)');
   }
 
   final int channel;
@@ -486,6 +520,16 @@ class HipSamplerRenderer extends Renderer {
   static final _FireflyD fireflyHost = _lib.lookupFunction<_FireflyC, _FireflyD>('dr_firefly_host');
   static final _FireflyD firefly = _lib.lookupFunction<_FireflyC, _FireflyD>('dr_firefly');
   static final _FireflyDeviceD fireflyDevice = _lib.lookupFunction<_FireflyDeviceC, _FireflyDeviceD>('dr_firefly_device');
+  /// Demodulation: the emission and albedo images of MaterialIntegrator are taken out of the beauty image ahead of every other image stage
+  /// (`demodulate`) and put back after the last (`remodulate`); the `Device` forms after dr_init, the `Host` forms and the checks without a GPU.
+  static final _MaterialCheckD materialCheck = _lib.lookupFunction<_MaterialCheckC, _MaterialCheckD>('dr_material_check');
+  static final _DemodulateCheckD demodulateCheck = _lib.lookupFunction<_DemodulateCheckC, _DemodulateCheckD>('dr_demodulate_check');
+  static final _DemodulateD demodulateHost = _lib.lookupFunction<_DemodulateC, _DemodulateD>('dr_demodulate_host');
+  static final _DemodulateD demodulate = _lib.lookupFunction<_DemodulateC, _DemodulateD>('dr_demodulate');
+  static final _DemodulateDeviceD demodulateDevice = _lib.lookupFunction<_DemodulateDeviceC, _DemodulateDeviceD>('dr_demodulate_device');
+  static final _DemodulateD remodulateHost = _lib.lookupFunction<_DemodulateC, _DemodulateD>('dr_remodulate_host');
+  static final _DemodulateD remodulate = _lib.lookupFunction<_DemodulateC, _DemodulateD>('dr_remodulate');
+  static final _DemodulateDeviceD remodulateDevice = _lib.lookupFunction<_DemodulateDeviceC, _DemodulateDeviceD>('dr_remodulate_device');
   /// The display transform: linear f32 radiance to RGBA8 through exposure, a tone curve and an 8-bit encode (after dr_init).
   static final _DisplayD displayImage = _lib.lookupFunction<_DisplayC, _DisplayD>('dr_display');
   /// DR_ABI_VERSION of the include/dartray_hip.h these offsets were written against: the structs carry no size field, so a
@@ -1134,6 +1178,11 @@ class HipSamplerRenderer extends Renderer {
         rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_FEATURE);
         rd.i32(OFF_DrRenderDesc_max_depth, 0);
         rd.i32(OFF_DrRenderDesc_feature_channel, feat.channel);
+      } else if (surfaceIntegrator is MaterialIntegrator) {  // max_depth is not read
+        final MaterialIntegrator mat = surfaceIntegrator;
+        rd.i32(OFF_DrRenderDesc_integrator, DR_INTEGRATOR_MATERIAL);
+        rd.i32(OFF_DrRenderDesc_max_depth, 0);
+        rd.i32(OFF_DrRenderDesc_material_channel, mat.channel);
       } else {
         _unsupported('surface integrator ${surfaceIntegrator.runtimeType}');
       }
