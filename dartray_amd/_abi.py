@@ -359,6 +359,7 @@ EXPORTS = {
     "dr_version": (C.c_char_p, []),
     "dr_abi_version": (C.c_int32, []),
     "dr_scene_workspace_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "dr_scene_get_table_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32 * 6)]),
 }
 
 _lib = None

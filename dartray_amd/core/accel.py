@@ -379,6 +379,14 @@ class _DeviceScene:
         _abi.check(_abi.lib().dr_scene_workspace_bytes(self.handle, C.byref(n)))
         return int(n.value)
 
+    def table_counts(self):
+        """What the shading kernels' light and material tables hold (dr_scene_get_table_counts): their byte sizes decide whether the
+        kernels read them from LDS or from global memory."""
+        arr = (C.c_uint32 * 6)()
+        _abi.check(_abi.lib().dr_scene_get_table_counts(self.handle, C.byref(arr)))
+        return {"nlights": int(arr[0]), "nltris": int(arr[1]), "ncdf": int(arr[2]), "nmats": int(arr[3]),
+                "sizeof_DLight": int(arr[4]), "sizeof_DLightTri": int(arr[5])}
+
     def coherent_stats(self):
         """The part of stats()' closest-hit totals that k_trace_pk (coherent waves: the camera rays) traced."""
         arr = (C.c_double * 5)()

@@ -380,6 +380,17 @@ int dr_scene_workspace_bytes(const DrScene* sc, uint64_t* bytes_out) {
   return DR_OK;
 }
 
+int dr_scene_get_table_counts(const DrScene* sc, uint32_t out[6]) {
+  if (!sc || !out) return fail(DR_ERR_INVALID, "null argument");
+  out[0] = sc->d.nlights;
+  out[1] = sc->d.nltris;
+  out[2] = sc->d.ncdf;
+  out[3] = sc->d.nmats;
+  out[4] = (uint32_t)sizeof(DLight);
+  out[5] = (uint32_t)sizeof(DLightTri);
+  return DR_OK;
+}
+
 int dr_scene_get_state_layout(const DrScene* sc, int32_t* layout_out, float* density_out) {
   if (!sc || !layout_out) return fail(DR_ERR_INVALID, "null argument");
   *layout_out = sc->stateLayout;

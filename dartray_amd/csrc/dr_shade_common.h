@@ -49,6 +49,8 @@ DR_DEV void shade_count(PushStage& sm, TraceCounters* ctr, uint32_t nIn) {
 #define SHADE_WAVES_OF(general) ((general) ? DR_SHADE_WAVES_GEN : DR_SHADE_WAVES)
 // LDS copy of the light tables and (when it is small too) the material table, behind the queue-staging block of the
 // dynamic LDS; a workgroup-wide copy + barrier.
+// Which tables go where at what sizes, and the test on either side of each cap: DESIGN.md section 3, "Where the tables live" (what
+// dr_device.h sums up as "large emissive meshes keep the global tables"; that file's hash is pinned by the committed profiles).
 #define DR_LDS_LIGHT_BYTES (24 * 1024)  // light tables up to this size are staged in LDS (the queue staging takes ~96 KB of the 160)
 #define DR_LDS_MAT_BYTES (24 * 1024)    // likewise the material table (64 B per material)
 __host__ __device__ inline size_t light_table_bytes(const DScene& sc) {  // (+ 48 B per triangle: its f64 edges, LdsLights::ledges)

@@ -816,6 +816,12 @@ int dr_scene_get_sampler_stats(DrScene* scene, double out[2]);
 /* Device memory the scene's path-state workspace holds right now (tiles, queues, sample storage; it is allocated by the first render,
  * grows when a later render needs more and is freed with the scene): what a host budgets next to its own allocations. */
 int dr_scene_workspace_bytes(const DrScene* scene, uint64_t* bytes_out);
+/* Diagnostics: what the shading kernels' light and material tables of this scene hold -- out[0] light records, out[1] light-triangle
+ * records (a quadric emitter counts one), out[2] entries of the lights' area CDFs (triangles + 1 per area light; 1 where there is none),
+ * out[3] material records, out[4] / out[5] the bytes of one light / one light-triangle record.  Their byte sizes decide per scene whether
+ * the shading kernels read the tables from LDS or from global memory ("Where the tables live"): results never
+ * depend on it, and a test that means to cover one side says so with these counts. */
+int dr_scene_get_table_counts(const DrScene* scene, uint32_t counts_out[6]);
 /* The path-state layout of this scene's path-traced renders, next to the traversal kernels and measured the same way: the
  * first big render's first pilot batch counts how many of its slots are still alive at the second bounce (density_out;
  * -1 before); below one half the renders use four-slot, line-grouped sub-tiles (layout 4: stage lists that thin out touch
@@ -1064,7 +1070,8 @@ const char* dr_version(void);
  * dr_render_guides_check, dr_render_guides and dr_render_guides_device; no field of DrRenderDesc moved; and DR_INTEGRATOR_MATERIAL: a new
  * constant whose channel is a third member of feature_channel's union, read under that constant only, and one new entry point,
  * dr_material_check; and demodulation: one new struct, DrDemodulateParams, that only its seven new entry points read -- dr_demodulate_check,
- * dr_demodulate_host, dr_demodulate, dr_demodulate_device, dr_remodulate_host, dr_remodulate and dr_remodulate_device). */
+ * dr_demodulate_host, dr_demodulate, dr_demodulate_device, dr_remodulate_host, dr_remodulate and dr_remodulate_device; and dr_scene_get_table_counts:
+ * one new read-only entry point, no struct). */
 #define DR_ABI_VERSION 9
 int32_t dr_abi_version(void);
 

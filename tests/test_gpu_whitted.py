@@ -12,6 +12,7 @@ import pytest
 from dartray_amd import _abi, core, pbrt, scenes
 
 import prt_restatement as prt
+import table_placement as tp
 import whitted_restatement as wr
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -37,13 +38,18 @@ def _leaning():
     return core.GeometricPrimitive(mesh, core.MatteMaterial((0.6, 0.5, 0.4)), None)
 
 
-def _prims(sphere=True, area=True, specular=True, leaning=False):
+def _prims(sphere=True, area=True, specular=True, leaning=False, emitter=None, floor=None):
     """A closed box of matte quads (the camera is inside) with one emissive triangle under the ceiling, a mirror quad in front of the
-    left wall, a glass sphere and a glass triangle mesh."""
+    left wall, a glass sphere and a glass triangle mesh.  emitter: a primitive in the emissive triangle's place; floor: a list of
+    primitives in the floor quad's place."""
     s = 10.0
     white = core.MatteMaterial((0.75, 0.75, 0.75))
     prims = scenes.cornell_walls() + [_quad((-s, -s, -s), (-s, s, -s), (s, s, -s), (s, -s, -s), white)]  # + the wall behind the camera
-    if area:
+    if floor is not None:
+        prims = prims[1:] + list(floor)
+    if emitter is not None:
+        prims.append(emitter)
+    elif area:
         tri = core.TriangleMesh(np.array([[0, 1, 2]], np.uint32), np.array([(-3, 9.5, -2), (3, 9.5, -2), (0, 9.5, 4)], np.float32))
         prims.append(core.GeometricPrimitive(tri, core.MatteMaterial((0.5, 0.5, 0.5)), core.DiffuseAreaLight((40.0, 36.0, 30.0), 1)))
     if specular:
@@ -83,6 +89,7 @@ class Setup:
         lights, restated_lights = _delta_lights()
         self.env = _constant_env() if env else None
         if env:  # open the box: no ceiling, so that camera and child rays escape
+            assert kw.get("floor") is None
             prims = [p for i, p in enumerate(prims) if i != 1]
         accel = core.BVHAccel(prims)
         self.scene = core.Scene(accel, accel.lights() + lights + ([self.env] if env else []))
@@ -146,6 +153,39 @@ def test_depth_changes_the_image(box):
     """The mirror and the glass show: each depth adds radiance somewhere."""
     f = {d: box.restated_film(d, _ld(box, 2), "ld2")[0] for d in (1, 2, 5)}
     assert not _same(f[1], f[2]) and not _same(f[2], f[5])
+
+
+# ---- 1b. both forms of the kernel: light tables in LDS and in global memory (DESIGN.md section 3, "Where the tables live") ----
+@pytest.fixture(scope="module")
+def table_sizes(gpu):
+    """(the largest fan for which k_shade_whitted<true> runs, the smallest for which k_shade_whitted<false> does, the tile count one over
+    the material cap), by tests/table_placement.py's formula from the counts of the box with a fan of two triangles over its floor quad."""
+    c = tp.table_counts(Setup(emitter=tp.fan_emitter(2)).scene)
+    n_lds, n_global = tp.fan_sizes(c, "whitted", 2)
+    k_over = 1 + max(k for k in range(1, 1000) if tp.mat_table_bytes(tp.with_tiles(c, k, 1)))
+    return c, n_lds, n_global, k_over
+
+
+_placed = {}
+
+
+@pytest.mark.parametrize("case", ["fan_smallest-global", "fan_largest-lds", "tiles_over_cap-lds_lights_global_mats"])
+def test_film_equals_the_restatement_on_both_sides_of_the_table_caps(table_sizes, case):
+    """The restatement walks every light triangle in Python: the fan stays at the two sizes next to the cap, at 2 samples per pixel and
+    maxDepth 2, and each configuration's restated film is computed once."""
+    c, n_lds, n_global, k_over = table_sizes
+    what, want = case.split("-")
+    if case not in _placed:
+        _placed[case] = {"fan_smallest": lambda: Setup(emitter=tp.fan_emitter(n_global)), "fan_largest": lambda: Setup(emitter=tp.fan_emitter(n_lds)),
+                         "tiles_over_cap": lambda: Setup(emitter=tp.fan_emitter(2), floor=tp.tiled_floor(k_over))}[what]()
+    s = _placed[case]
+    counts = {"fan_smallest": tp.with_fan(c, n_global, 2), "fan_largest": tp.with_fan(c, n_lds, 2), "tiles_over_cap": tp.with_tiles(c, k_over, 1)}[what]
+    assert tp.table_counts(s.scene) == counts and n_global == n_lds + 1
+    assert tp.placement(s.scene, "whitted") == want
+    want_film = s.restated_film(2, _ld(s, 2), "ld2")[0]
+    got = s.renderer(2, _ld(s, 2)).render(s.scene).film
+    assert np.isfinite(got).all() and got[..., :3].max() > 0.0
+    assert _same(got, want_film)
 
 
 # ---- 2. the infinite light: an escaped child ray adds Le ----
