@@ -318,10 +318,6 @@ int SceneBuilder::pairsOnDevice() {
       sc->d.npairs = pout.npairs;
       sc->d.topPairs = pout.topPairs;
       sc->d.rootRef = r.nprims ? (PREF_LEAF | ((uint32_t)r.nprims << 26) | r.offset) : ((uint32_t)r.axis << 29);  // (the root's pair is slot 0 in either order)
-      for (int k = 0; k < 3; ++k) {
-        sc->d.rootBox[k] = r.bmin[k];
-        sc->d.rootBox[3 + k] = r.bmax[k];
-      }
     } else {
       sc->pairs.release();
     }
@@ -416,10 +412,6 @@ int SceneBuilder::pairsOnHost() {
       sc->d.pairs = sc->pairs.p;
       sc->d.npairs = np;
       sc->d.rootRef = packRef(0);
-      for (int k = 0; k < 3; ++k) {
-        sc->d.rootBox[k] = N[0].bmin[k];
-        sc->d.rootBox[3 + k] = N[0].bmax[k];
-      }
     }
   }
   return DR_OK;
@@ -805,6 +797,12 @@ int SceneBuilder::finish() {
   sc->d.ltris = sc->ltris.p;
   sc->d.lcdf = sc->lcdf.p;
   sc->d.nnodes = (uint32_t)desc->nnodes;
+  // the world bound: node 0's box, whether or not the tree takes the pair layout (diffuse / glossy PRT project the lights at its centre, the
+  // probe bake walks inside its bounding sphere and lays its default grid over it); a scene without nodes keeps six zeros
+  for (int k = 0; k < 3 && desc->nnodes; ++k) {
+    sc->d.rootBox[k] = desc->nodes[0].bmin[k];
+    sc->d.rootBox[3 + k] = desc->nodes[0].bmax[k];
+  }
   sc->d.ntris = (uint32_t)desc->ntris;
   sc->d.nlights = desc->nlights;
   sc->d.nmats = desc->nmaterials;

@@ -319,8 +319,8 @@ BALL_C, BALL_R = (-1.1, 0.9, 0.6), 0.9
 @pytest.fixture(scope="module")
 def ball(film):
     """The film scene and a matte sphere of reversed orientation standing on the floor beside the box: with the room's plain quads and the leaning
-    quad's per-vertex N, every branch of the camera hit's geometry (quadric, triangle with DR_SHADING_N, plain triangle).  The bake refuses a scene
-    with a quadric (it finds no world bound), so the grid is the film scene's: the integrator only reads it."""
+    quad's per-vertex N, every branch of the camera hit's geometry (quadric, triangle with DR_SHADING_N, plain triangle).  The grid is
+    the film scene's: the integrator only reads it.  (The bake of a scene with a quadric is tests/test_gpu_world_bound.py's.)"""
     at = T.Translate(*BALL_C)
     return Film([core.GeometricPrimitive(core.Sphere(at.m, at.mInv, True, BALL_R), core.MatteMaterial((0.4, 0.5, 0.6)), None)], grid=film.grid)
 
