@@ -207,7 +207,7 @@ void BatchRunner::logTrace(StageLog& g, int any) {
 }
 
 GprtArgs BatchRunner::gprtArgs() const {
-  return GprtArgs{P.gprt.nSamples, P.gprt.lmax, P.wsCap, (uint32_t)P.gprt.words, w.gprtBits.p, w.gprtMark.p, sc->prt.K.p, sc->prt.cin.p, sc->gprt.B.p};
+  return GprtArgs{P.rounds.nSamples, P.gprt.lmax, P.wsCap, (uint32_t)P.gprt.words, w.gprtBits.p, w.gprtMark.p, sc->prt.K.p, sc->prt.cin.p, sc->gprt.B.p};
 }
 
 StageQueues BatchRunner::stageQueues(int b, const uint32_t* roundQ, const uint32_t* nRound) {
@@ -246,31 +246,30 @@ int BatchRunner::stage(int b, int round, const uint32_t* roundQ, const uint32_t*
   // the integrator's shading launcher, and the rays it queues: closest-hit (continuation / MIS) and any-hit (shadow) rays, or -- a Whitted stage --
   // one shadow ray per slot and nothing else (no MIS ray, no continuation: the child rays are the rounds')
   bool shadowRaysOnly = false;
+  // the integrators whose rays go in rounds (Rounds; zeros under every other), stage b of round `round`: ray b - 1 of the round folded in, ray b
+  // queued (the last stage only folds)
+  const Rounds& R = P.rounds;
+  const int folded = b > 0 ? round * R.perRound + b - 1 : -1, queued = b < R.perRound ? round * R.perRound + b : -1;
   switch (P.integrator) {  // (no default: -Wall names a kind this forgets)
     case IntegratorKind::Path: L.shade_path(sc->d, rp, stS, q, b, P.sgrid, s); break;
     case IntegratorKind::DirectAll: case IntegratorKind::DirectOne: L.shade_direct(sc->d, rp, stS, q, b, P.sgrid, s); break;
     case IntegratorKind::Whitted: L.shade_whitted(sc->d, rp, stS, q, b, P.sgrid, s); shadowRaysOnly = true; break;
-    case IntegratorKind::AmbientOcclusion: {  // stage b of round `round`: ray b - 1 of the round folded in, ray b queued (the last stage only folds)
-      const int first = round * P.ao.perRound;
-      L.shade_ao(sc->d, rp, stS, q, P.ao.nSamples, b > 0 ? first + b - 1 : -1, b < P.ao.perRound ? first + b : -1, P.ao.minDist, P.ao.maxDist, P.sgrid, s);
+    case IntegratorKind::AmbientOcclusion:
+      L.shade_ao(sc->d, rp, stS, q, R.nSamples, folded, queued, P.ao.minDist, P.ao.maxDist, P.sgrid, s);
       shadowRaysOnly = true;
       break;
-    }
     case IntegratorKind::Feature: L.shade_feature(sc->d, stS, q, P.feature.channel, P.sgrid, s); break;  // (the only stage: nothing is traced behind it)
     case IntegratorKind::DiffusePRT: {  // the stages and rounds of ambient occlusion; the fold adds to the slot's transfer coefficients (Workspace::prt)
-      const int first = round * P.prt.perRound;
-      const PrtArgs a = {P.prt.nSamples, P.prt.lmax, P.wsCap, 0u, w.prt.p, sc->prt.K.p, sc->prt.cin.p};
-      L.shade_prt(sc->d, rp, stS, q, a, b > 0 ? first + b - 1 : -1, b < P.prt.perRound ? first + b : -1, P.sgrid, s);
+      const PrtArgs a = {R.nSamples, P.prt.lmax, P.wsCap, 0u, w.prt.p, sc->prt.K.p, sc->prt.cin.p};
+      L.shade_prt(sc->d, rp, stS, q, a, folded, queued, P.sgrid, s);
       shadowRaysOnly = true;
       break;
     }
-    case IntegratorKind::GlossyPRT: {  // the same stages and rounds; the fold records one visibility bit (Workspace::gprtBits)
-      const int first = round * P.gprt.perRound;
-      L.shade_gprt(sc->d, rp, stS, q, gprtArgs(), b > 0 ? first + b - 1 : -1, b < P.gprt.perRound ? first + b : -1, P.sgrid, s);
-      if (b + 1 == P.nStages && round + 1 == P.gprt.rounds) L.gprt_finish(stS, gprtArgs(), s);  // behind the last fold: the rest of Li, one wave per slot
+    case IntegratorKind::GlossyPRT:  // the same stages and rounds; the fold records one visibility bit (Workspace::gprtBits)
+      L.shade_gprt(sc->d, rp, stS, q, gprtArgs(), folded, queued, P.sgrid, s);
+      if (b + 1 == P.nStages && round + 1 == R.rounds) L.gprt_finish(stS, gprtArgs(), s);  // behind the last fold: the rest of Li, one wave per slot
       shadowRaysOnly = true;
       break;
-    }
     case IntegratorKind::UseProbes: {  // (the only stage: nothing is traced behind it)
       const auto& g = sc->probes;
       const ProbeArgs a = {g.lmax, {g.n[0], g.n[1], g.n[2]}, {g.b[0], g.b[1], g.b[2]}, {g.b[3], g.b[4], g.b[5]}, g.cin.p, g.K.p};

@@ -1,5 +1,6 @@
 // dr_host.h -- what the host units of the library share (internal; not part of the C ABI):
-//   dr_api.hip          options, the render planner (RenderPlan: planRender, planBatches, prepareRender), the entry points
+//   dr_api.hip          options, prepareRender (what a RenderPlan needs on the device), the entry points
+//   dr_plan.hip         the render planner (RenderPlan: planRender in units, planBatches, secondPass)
 //   dr_scene_build.hip  dr_scene_create / dr_scene_destroy (SceneBuilder)
 //   dr_batch.hip        one batch through the stage loop (BatchRunner), the batch loop, the pilot
 // Whatever has external linkage here lives in namespace dr_host (each unit says `using namespace dr_host;`); what a single unit uses
@@ -22,6 +23,7 @@
 namespace dr_host {
 
 extern int g_device;  // dr_init's device (-1 before it)
+extern int g_numCU;   // its compute units (256 before it)
 
 int fail(int code, const std::string& msg);  // dr_api.hip: sets dr_last_error(), returns code
 #define HIP_TRY(expr)                                                                              \
@@ -302,7 +304,8 @@ struct LayoutOps {
 extern const LayoutOps kLayout64, kLayoutSp4;  // dr_api.hip
 
 // The sampler modes of the C ABI (DrRenderDesc.sampler_mode) as the planner sees them, and what each one declares: every decision of
-// dr_api.hip / dr_batch.hip that depends on the mode reads one of these facts.  A new mode adds a row, its plan function and its case in genSamples.
+// dr_plan.hip / dr_api.hip / dr_batch.hip that depends on the mode reads one of these facts.  A new mode adds a row, its case in planSampler (its
+// own rules), its function in planPixelSource where its pixels come from somewhere new (dr_plan.hip), and its case in genSamples.
 enum class SamplerKind : int { HostBuffer, LowDiscrepancy, Stratified, Adaptive, Halton, Random };
 struct SamplerTraits {
   bool deviceGenerated;  // the device sampler runs (else the caller's vectors are uploaded per batch)
@@ -320,11 +323,18 @@ constexpr SamplerTraits kSamplerTraits[] = {
     {true, true, true, true, "random sampler: a light's nsamples must be a power of two (RandomSampler.roundSize is the identity, the scene's sample layout is the rounded one)"}};  // Random
 
 // The surface integrators of the C ABI (DrRenderDesc.integrator) as the planner sees them, and what each one declares: every decision of
-// dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planRender's stage
-// source, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases, its launcher in DR_LAYOUT_LAUNCHERS.
-// (no kind 6: the ABI leaves that value unassigned -- see DR_INTEGRATOR_DIFFUSE_PRT in dartray_hip.h -- and knownIntegrator refuses it like any other unknown value)
-enum class IntegratorKind : int { DirectAll, Path, DirectOne, Whitted, AmbientOcclusion, Feature, DiffusePRT = 7, GlossyPRT = 9, UseProbes = 11, Material = 13 };
+// dr_plan.hip / dr_api.hip / dr_batch.hip that depends on the integrator reads one of these facts or is a case of a switch over the kind (planStages,
+// sideBufferBytesPerSlot / allocSideBuffers, BatchRunner::stage's launcher and rays, lastInfoWord).  A new integrator adds a row, its cases -- in planStages
+// a call of its own plan function where it has rules (dr_plan.hip) --, its launcher in DR_LAYOUT_LAUNCHERS.
+// The kinds ARE the ABI's values.  (No kind 6, 8, 10, 12: the ABI leaves those values unassigned -- see DR_INTEGRATOR_DIFFUSE_PRT in dartray_hip.h -- and
+// knownIntegrator refuses them like any other unknown value.)
+enum class IntegratorKind : int {
+  DirectAll = DR_INTEGRATOR_DIRECT_ALL, Path = DR_INTEGRATOR_PATH, DirectOne = DR_INTEGRATOR_DIRECT_ONE, Whitted = DR_INTEGRATOR_WHITTED,
+  AmbientOcclusion = DR_INTEGRATOR_AO, Feature = DR_INTEGRATOR_FEATURE, DiffusePRT = DR_INTEGRATOR_DIFFUSE_PRT, GlossyPRT = DR_INTEGRATOR_GLOSSY_PRT,
+  UseProbes = DR_INTEGRATOR_USE_PROBES, Material = DR_INTEGRATOR_MATERIAL
+};
 struct IntegratorTraits {
+  bool assigned;         // the row's index names an integrator (else: a value the ABI leaves unassigned, kUnassignedIntegratorRow)
   bool sceneSlots;       // the sample slots are the scene's DirectLighting layout (the lights' nsamples decide: dlN1D / dlNFloats / dlBlocks), n1D / n2D unused
   int n1D, n2D;          // else: the 1-D and 2-D slots behind the five camera floats, the volume integrator's tau + scatter among the 1-D ones
   bool pathStages;       // k_shade_path's stages, max_depth + 2 of them: deferred NEE, RNG draws beyond the sample vector, the blocks the path reads
@@ -333,70 +343,56 @@ struct IntegratorTraits {
   const char* depthBelowOne;  // max_depth counts the camera vertex, so it is at least 1: the refusal's text, else null
   const char* adaptive;       // the adaptive sampler is not supported: the refusal's text, else null
 };
+// The row of a value inside the table's range that names no integrator: never read -- knownIntegrator says no -- and spelt as DirectAll, which an
+// unknown value counts as.  An integrator added later takes the value behind the last one, not one of these: what the library answers for them is
+// pinned behaviour (tests/test_feature_integrator.py, test_prt_integrator.py, test_glossy_prt_integrator.py, test_probes_integrator.py, test_guides.py)
+constexpr IntegratorTraits kUnassignedIntegratorRow = {false, true, 0, 0, false, false, nullptr, nullptr};
 constexpr IntegratorTraits kIntegratorTraits[] = {
-    {true, 0, 0, false, true, nullptr, nullptr},    // DirectAll: per light a light and a BSDF slot pair of roundSize(nsamples) entries (2n + 2 and 2n slots at nsamples 1)
-    {false, 14, 9, true, false, nullptr, nullptr},  // Path: 3 x (light 1D+2D, lightNum 1D, bsdf 1D+2D, path 1D+2D) + tau + scatter
+    {true, true, 0, 0, false, true, nullptr, nullptr},    // DirectAll: per light a light and a BSDF slot pair of roundSize(nsamples) entries (2n + 2 and 2n slots at nsamples 1)
+    {true, false, 14, 9, true, false, nullptr, nullptr},  // Path: 3 x (light 1D+2D, lightNum 1D, bsdf 1D+2D, path 1D+2D) + tau + scatter
     // DirectOne (direct_lighting_integrator.dart:82-87): light component, lightNum, BSDF component + tau + scatter; light position, BSDF direction
-    {false, 5, 2, false, true, nullptr, nullptr},
+    {true, false, 5, 2, false, true, nullptr, nullptr},
     // Whitted (whitted_integrator.dart:26-72): no requestSamples -- tau + scatter only; one stage per light, any-hit rays only
-    {false, 2, 0, false, true, "whitted integrator: max_depth must be at least 1 (maxdepth counts the camera vertex: ray.depth + 1 < maxDepth)",
+    {true, false, 2, 0, false, true, "whitted integrator: max_depth must be at least 1 (maxdepth counts the camera vertex: ray.depth + 1 < maxDepth)",
      "whitted integrator: the adaptive sampler is not supported (its second pass over the rounds of the specular recursion has no test; every other sampler mode is)"},
     // AmbientOcclusion (ambient_occlusion_integrator.dart:28-53): no requestSamples -- tau + scatter only; one any-hit ray per stage,
     // nsamples of them per camera hit in rounds of the stage loop; max_depth is not read
-    {false, 2, 0, false, false, nullptr,
+    {true, false, 2, 0, false, false, nullptr,
      "ambient occlusion integrator: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"},
     // Feature (no reference class): no requestSamples -- tau + scatter only; one stage, no ray beyond the camera's; max_depth and
     // the lights are not read
-    {false, 2, 0, false, false, nullptr, "feature integrator: the adaptive sampler is not supported"},
-    {true, 0, 0, false, false, nullptr, nullptr},  // (6: unassigned, never read -- knownIntegrator says no -- and spelt as DirectAll, which an unknown value counts as)
+    {true, false, 2, 0, false, false, nullptr, "feature integrator: the adaptive sampler is not supported"},
+    kUnassignedIntegratorRow,  // (6)
     // DiffusePRT (diffuse_prt_integrator.dart:42-81): an empty requestSamples -- tau + scatter only; one any-hit ray per stage, nsamples of
     // them per camera hit in rounds of the stage loop, as for AmbientOcclusion; max_depth is not read
-    {false, 2, 0, false, false, nullptr,
+    {true, false, 2, 0, false, false, nullptr,
      "diffuse PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"},
-    {true, 0, 0, false, false, nullptr, nullptr},  // (8: unassigned like 6 -- what the library answers for it is pinned by tests/test_prt_integrator.py)
+    kUnassignedIntegratorRow,  // (8)
     // GlossyPRT (glossy_prt_integrator.dart:53-116): an empty requestSamples -- tau + scatter only; DiffusePRT's stages and rounds,
     // then one finish launch per batch; max_depth is not read
-    {false, 2, 0, false, false, nullptr,
+    {true, false, 2, 0, false, false, nullptr,
      "glossy PRT: the adaptive sampler is not supported (its second pass over the rounds of occlusion rays has no test; every other sampler mode is)"},
-    {true, 0, 0, false, false, nullptr, nullptr},  // (10: unassigned like 6 and 8 -- what the library answers for it is pinned by tests/test_glossy_prt_integrator.py)
+    kUnassignedIntegratorRow,  // (10)
     // UseProbes (use_probes_integrator.dart:74-88): requestSamples asks for the scene's DirectLighting "all" slots although Li never
     // reads them (the grid includes the direct light); one stage, no ray beyond the camera's; max_depth is not read
-    {true, 0, 0, false, false, nullptr, "use probes: the adaptive sampler is not supported (its second pass has no test under this integrator; every other sampler mode is)"},
-    {true, 0, 0, false, false, nullptr, nullptr},  // (12: unassigned like 6, 8 and 10 -- what the library answers for it is pinned by tests/test_probes_integrator.py and tests/test_guides.py)
+    {true, true, 0, 0, false, false, nullptr, "use probes: the adaptive sampler is not supported (its second pass has no test under this integrator; every other sampler mode is)"},
+    kUnassignedIntegratorRow,  // (12)
     // Material (no reference class): the feature integrator's row -- no requestSamples, tau + scatter only; one stage, no ray beyond
     // the camera's; max_depth is not read
-    {false, 2, 0, false, false, nullptr, "material integrator: the adaptive sampler is not supported"}};
-static_assert((int)IntegratorKind::DirectAll == DR_INTEGRATOR_DIRECT_ALL && (int)IntegratorKind::Path == DR_INTEGRATOR_PATH &&
-                  (int)IntegratorKind::DirectOne == DR_INTEGRATOR_DIRECT_ONE && (int)IntegratorKind::Whitted == DR_INTEGRATOR_WHITTED &&
-                  (int)IntegratorKind::AmbientOcclusion == DR_INTEGRATOR_AO && (int)IntegratorKind::Feature == DR_INTEGRATOR_FEATURE &&
-                  (int)IntegratorKind::DiffusePRT == DR_INTEGRATOR_DIFFUSE_PRT && (int)IntegratorKind::GlossyPRT == DR_INTEGRATOR_GLOSSY_PRT &&
-                  (int)IntegratorKind::UseProbes == DR_INTEGRATOR_USE_PROBES && (int)IntegratorKind::Material == DR_INTEGRATOR_MATERIAL &&
-                  sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]) == 14, "kIntegratorTraits is indexed by DrRenderDesc.integrator");
-// The one value inside the table's range that names no integrator: its row is a placeholder.  An integrator added later takes the value behind the
-// last one, not this one -- what the library answers for it is pinned behaviour (tests/test_feature_integrator.py)
-constexpr int32_t kUnassignedIntegrator = 6;
-static_assert(DR_INTEGRATOR_FEATURE < kUnassignedIntegrator && kUnassignedIntegrator < DR_INTEGRATOR_DIFFUSE_PRT &&
-                  kIntegratorTraits[kUnassignedIntegrator].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator].adaptive,
-              "the unassigned value lies between the feature and the diffuse PRT integrator and its row is the placeholder");
-// ... and the second one, between the two PRT integrators, for the same reason (tests/test_prt_integrator.py pins dr_sample_floats(8, 3))
-constexpr int32_t kUnassignedIntegrator2 = 8;
-static_assert(DR_INTEGRATOR_DIFFUSE_PRT < kUnassignedIntegrator2 && kUnassignedIntegrator2 < DR_INTEGRATOR_GLOSSY_PRT &&
-                  kIntegratorTraits[kUnassignedIntegrator2].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator2].adaptive,
-              "the second unassigned value lies between the diffuse and the glossy PRT integrator and its row is the placeholder");
-// ... and the third, between the glossy PRT and the probe integrator (tests/test_glossy_prt_integrator.py pins dr_sample_floats(10, 3))
-constexpr int32_t kUnassignedIntegrator3 = 10;
-static_assert(DR_INTEGRATOR_GLOSSY_PRT < kUnassignedIntegrator3 && kUnassignedIntegrator3 < DR_INTEGRATOR_USE_PROBES &&
-                  kIntegratorTraits[kUnassignedIntegrator3].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator3].adaptive,
-              "the third unassigned value lies between the glossy PRT and the probe integrator and its row is the placeholder");
-// ... and the fourth, between the probe and the material integrator (tests/test_probes_integrator.py pins dr_sample_floats(12, 3), tests/test_guides.py its refusal)
-constexpr int32_t kUnassignedIntegrator4 = 12;
-static_assert(DR_INTEGRATOR_USE_PROBES < kUnassignedIntegrator4 && kUnassignedIntegrator4 < DR_INTEGRATOR_MATERIAL &&
-                  kIntegratorTraits[kUnassignedIntegrator4].sceneSlots && !kIntegratorTraits[kUnassignedIntegrator4].adaptive,
-              "the fourth unassigned value lies between the probe and the material integrator and its row is the placeholder");
-inline bool knownIntegrator(int32_t v) {
-  return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && v != kUnassignedIntegrator && v != kUnassignedIntegrator2 &&
-         v != kUnassignedIntegrator3 && v != kUnassignedIntegrator4;
+    {true, false, 2, 0, false, false, nullptr, "material integrator: the adaptive sampler is not supported"}};
+// The one check of the table against the ABI: 14 rows, and the assigned ones are exactly the ten DR_INTEGRATOR_* values (the kinds)
+constexpr bool integratorTableMatchesAbi() {
+  constexpr IntegratorKind kinds[] = {IntegratorKind::DirectAll, IntegratorKind::Path, IntegratorKind::DirectOne, IntegratorKind::Whitted, IntegratorKind::AmbientOcclusion,
+                                      IntegratorKind::Feature, IntegratorKind::DiffusePRT, IntegratorKind::GlossyPRT, IntegratorKind::UseProbes, IntegratorKind::Material};
+  constexpr int rows = sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0]);
+  int assigned = 0;
+  for (int v = 0; v < rows; ++v) assigned += kIntegratorTraits[v].assigned ? 1 : 0;
+  for (IntegratorKind k : kinds)
+    if ((int)k < 0 || (int)k >= rows || !kIntegratorTraits[(int)k].assigned) return false;
+  return rows == 14 && assigned == 10;
 }
+static_assert(integratorTableMatchesAbi(), "kIntegratorTraits is indexed by DrRenderDesc.integrator: a row per value up to the last DR_INTEGRATOR_*, the unassigned ones placeholders");
+inline bool knownIntegrator(int32_t v) { return v >= 0 && v < (int32_t)(sizeof(kIntegratorTraits) / sizeof(kIntegratorTraits[0])) && kIntegratorTraits[v].assigned; }
 
 // The feature integrator's refusals (dr_feature_check, planRender): null, or the text and its code
 inline const char* featureRefusal(int32_t channel, uint64_t nprims, int* code) {
@@ -464,6 +460,20 @@ inline SlotCounts integratorSlots(IntegratorKind k, const DrScene* sc, uint32_t 
   return sc ? SlotCounts{sc->dlN1D, (sc->dlNFloats - 5 - sc->dlN1D) / 2} : SlotCounts{2 * (int)nlights + 2, 2 * (int)nlights};
 }
 
+// The rays of an integrator that sends one any-hit ray per stage (ambient occlusion, diffuse and glossy PRT): nSamples = RoundUpPow2(requested) rays per
+// camera hit.  A render holds at most CounterLayout::maxStages() stages, so the rays go in rounds of the stage loop, 128 to a round (a power of two: it
+// divides every larger nSamples): perRound of them in each of `rounds` rounds.
+struct Rounds {
+  int nSamples = 0, perRound = 0, rounds = 0;
+  static Rounds of(int requested) {  // 1 <= requested <= 4096 (the plan functions refuse every other count by name)
+    Rounds r;
+    for (r.nSamples = 1; r.nSamples < requested;) r.nSamples <<= 1;  // RoundUpPow2 (common.dart:117-125)
+    r.perRound = std::min(r.nSamples, 128);
+    r.rounds = r.nSamples / r.perRound;
+    return r;
+  }
+};
+
 struct RenderPlan {
   DrScene* sc = nullptr;
   const DrRenderDesc* rd = nullptr;
@@ -485,19 +495,18 @@ struct RenderPlan {
   // Halton: a "pixel" of this plan is an INDEX of the task's sequence (npixTotal = wanted, spp = 1: one slot per accepted sample); a
   // batch is a range of indices, selected on the device before it runs.  win: the task's window: left, top, right, bottom (inclusive), delta = max(width, height)
   struct { int32_t win[5] = {0, 0, 0, 0, 0}; } halton;
-  // AmbientOcclusion: nSamples occlusion rays per camera hit, perRound of them in each of `rounds` rounds of the stage loop
-  // (a round is perRound + 1 stages: CounterLayout::maxStages() bounds it); the rays' extent
-  struct { int nSamples = 0, perRound = 0, rounds = 0; double minDist = 0.0, maxDist = 0.0; } ao;
+  // AmbientOcclusion, DiffusePRT, GlossyPRT: the running integrator's occlusion rays in rounds of the stage loop (a round is perRound + 1 stages);
+  // every other integrator: none, zeros
+  Rounds rounds;
+  int shadowRounds() const { return rounds.rounds; }  // rounds of one-ray stages (else 0)
+  struct { double minDist = 0.0, maxDist = 0.0; } ao;  // AmbientOcclusion: the rays' extent
   struct { int channel = 0; } feature;  // Feature: DR_FEATURE_*
   struct { int channel = 0; } material;  // Material: DR_MATERIAL_CHANNEL_*
   // A guide render (dr_render_guides_device): n channels (0: none, every other render), the set as k_guides' mask, and per
-  // requested channel its film and its side plane (its rank in the mask).  The side planes cap the batch (planBatches) and are sized by prepareRender
+  // requested channel its film and its side plane (its rank in the mask).  The side planes cap the batch (sideBufferBytesPerSlot) and are sized by allocSideBuffers
   struct { int n = 0; uint32_t mask = 0u; float* film[DR_GUIDES_MAX] = {}; int plane[DR_GUIDES_MAX] = {}; } guides;
-  // DiffusePRT: the rays in rounds exactly as AmbientOcclusion's; lmax
-  struct { int nSamples = 0, perRound = 0, rounds = 0, lmax = 0; } prt;
-  // GlossyPRT: the same rounds; words of visibility bits per slot
-  struct { int nSamples = 0, perRound = 0, rounds = 0, lmax = 0, words = 0; } gprt;
-  int shadowRounds() const { return integrator == IntegratorKind::DiffusePRT ? prt.rounds : integrator == IntegratorKind::GlossyPRT ? gprt.rounds : ao.rounds; }  // rounds of one-ray stages (else 0)
+  struct { int lmax = 0; } prt;              // DiffusePRT
+  struct { int lmax = 0, words = 0; } gprt;  // GlossyPRT: words of visibility bits per slot
   // the device sampler's launches for one batch (BatchRunner::loadSamples, the two sample dumps)
   void genSamples(const RenderParams& rpB, const BatchState& st, uint32_t np) const;
   // what the workspace is sized for (prepareRender): this plan's batches; adaptive: both passes'
@@ -531,6 +540,13 @@ struct PilotResult {
 
 // ---- what the units call across files ----
 BatchState makeState(Workspace& w, const SampleForm& sf, const int2* pix, uint32_t nslots, bool useTail, int stateWords);  // dr_api.hip
+uint64_t sideBufferBytesPerSlot(const RenderPlan& P);  // dr_api.hip: what the integrator's side buffers add to a slot (beside allocSideBuffers)
+int planRender(RenderPlan& P);                                                                                              // dr_plan.hip
+int planBatches(RenderPlan& P);                                                                                             // dr_plan.hip
+RenderPlan secondPass(const RenderPlan& P, uint32_t nFlagged);                                                              // dr_plan.hip
+bool lazyGenFor(const RenderPlan& P);                                                                                       // dr_plan.hip
+void rp_film(RenderParams& rp, const DrFilm& f);                                                                            // dr_plan.hip
+void enumeratePixels(const RenderParams& rp, const DrRenderDesc* rd, std::vector<int2>& pixels);                            // dr_plan.hip
 int runBatches(RenderPlan& plan, const int2* pixDev, size_t firstPixel);                                                    // dr_batch.hip
 int runPilot(RenderPlan& P, PilotResult& R);                                                                                // dr_batch.hip
 // DR_SAMPLER_HALTON: the accepted indices of [k0, k0 + n) into the workspace (halton.idx), their number read back (the mode's host wait)

@@ -57,6 +57,40 @@ def test_of_two_broken_rules_the_same_one_wins(box):
     # the adaptive refusal in front of the camera's
     refused(adaptive(), core.WhittedIntegrator(5), UNSUPPORTED, "whitted integrator: the adaptive sampler is not supported", absent="camera",
             camera_type=UNKNOWN)
+
+    # ---- one pair per seam between the planner's units (dr_plan.hip): sampler, integrator in general, camera and film, the integrator's own
+    # rules, the pixel source ----
+    path = core.PathIntegrator(5)
+    strat = lambda: core.StratifiedSampler(cam, 2, 2, True, SEED)  # (spp 4: strat_xsamples=3 does not divide it)
+    ao, prt = lambda: core.AmbientOcclusionIntegrator(8), lambda: core.DiffusePRTIntegrator(2, 8)
+    # the sampler kind's own rules in front of the integrator
+    refused(core.HaltonSampler(cam, 4, SEED), path, UNSUPPORTED, "halton sampler: tile_count > 1", absent="unknown integrator", integrator=UNKNOWN,
+            tile_count=2)
+    refused(adaptive(), path, INVALID, "adaptive sampler: minSamples", absent="unknown integrator", integrator=UNKNOWN, strat_xsamples=3)
+    # an unknown sampler mode is refused late, where the pixel source is chosen
+    refused(ld(), path, INVALID, "unknown integrator", absent="sampler mode", integrator=UNKNOWN, sampler_mode=UNKNOWN)
+    refused(ld(), path, INVALID, "unknown sampler mode", sampler_mode=UNKNOWN)
+    # the integrator's general rules in front of the camera
+    refused(ld(), path, INVALID, "max_depth out of range", absent="camera", max_depth=65, camera_type=UNKNOWN)
+    # the camera in front of the integrator's own rules
+    refused(ld(), ao(), INVALID, "unknown camera type", absent="nsamples must be at least 1", camera_type=UNKNOWN, ao_nsamples=0)
+    refused(ld(), core.FeatureIntegrator("ng"), INVALID, "unknown camera type", absent="unknown channel", camera_type=UNKNOWN, feature_channel=UNKNOWN)
+    refused(ld(), prt(), INVALID, "unknown camera type", absent="lmax must be at least 1", camera_type=UNKNOWN, prt_lmax=0)
+    refused(ld(), core.MaterialIntegrator("albedo"), INVALID, "unknown camera type", absent="unknown channel", camera_type=UNKNOWN,
+            material_channel=UNKNOWN)
+    # the integrator's own rules in front of the pixel source
+    refused(strat(), ao(), INVALID, "ambient occlusion integrator: nsamples must be at least 1", absent="strat_xsamples", strat_xsamples=3, ao_nsamples=0)
+    refused(strat(), ao(), INVALID, "maxdist must be greater", absent="strat_xsamples", strat_xsamples=3, ao_maxdist=0.0)
+    refused(strat(), prt(), UNSUPPORTED, "diffuse PRT: material", absent="strat_xsamples", strat_xsamples=3)  # (the box has a mirror and glass)
+    refused(strat(), core.GlossyPRTIntegrator(lmax=2, nSamples=8), INVALID, "glossy PRT: lmax above 4", absent="strat_xsamples", strat_xsamples=3, prt_lmax=5)
+    refused(strat(), core.UseProbesIntegrator(), INVALID, "use probes: no probe grid", absent="strat_xsamples", strat_xsamples=3)
+    refused(strat(), core.MaterialIntegrator("albedo"), INVALID, "material integrator: unknown channel", absent="strat_xsamples", strat_xsamples=3,
+            material_channel=UNKNOWN)
+    # within an integrator: its parameters in front of the scene's materials
+    refused(ld(), prt(), INVALID, "lmax must be at least 1", absent="material", prt_lmax=0)
+    # the pixel source's own rules
+    refused(strat(), path, INVALID, "strat_xsamples must be positive and divide spp", strat_xsamples=3)
+    refused(ld(), path, INVALID, "host-buffer sampler: nsamples must be a positive multiple", sampler_mode=_abi.DR_SAMPLER_HOST_BUFFER, nsamples=0)
     assert not film.any()
 
 

@@ -10,7 +10,7 @@ SP4="-DDR_SUB=4 -DDR_NS=sp4 -DDR_STATE_WORDS_K=48 -DDR_GROUPED=1"
 for spec in "$@"; do
   name="${spec%%:*}"; flags="${spec#*:}"
   ( objs=""
-    for s in dr_kernels.hip dr_sampler_strat.hip dr_sampler_adaptive.hip dr_sampler_halton.hip dr_sampler_random.hip dr_trace.hip dr_api.hip dr_scene_build.hip dr_batch.hip; do
+    for s in dr_kernels.hip dr_sampler_strat.hip dr_sampler_adaptive.hip dr_sampler_halton.hip dr_sampler_random.hip dr_trace.hip dr_api.hip dr_plan.hip dr_scene_build.hip dr_batch.hip; do
       $CC $flags -x hip -c "$s" -o "_obj/va_${name}_$s.o" 2>/dev/null &
       objs="$objs _obj/va_${name}_$s.o"
     done
